@@ -11,7 +11,9 @@ Workload at N=1: BASELINE.json configs[1] — batch 32 AudioCaps-shaped prompts,
 10 s clips (latent 20x312, mel 80x624, 159,744 samples @16 kHz).  Weights are the seeded
 synthetic recipe (no checkpoints offline).
 
-Prints ONE JSON line (rank 0).  See DESIGN.md §Measurement for the roofline fields.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline; --full adds
+the roofline pass, the other configs, components and precision policies and the CPU baseline.
+--dump-outputs DIR saves what the last timed step returned, for comparing two builds output for output.
 """
 from __future__ import annotations
 
@@ -48,8 +50,18 @@ def parse():
                     help="precision policy (DESIGN.md §3): mixed = fp16 MFMA on the parity-tolerant layers + "
                          "bf16x3 elsewhere (waveform parity <= 1e-3, tests/test_gpu_models.py); split = bf16x3 "
                          "everywhere (fp32 parity); bf16 = one bf16 MFMA everywhere (misses the parity bar)")
-    ap.add_argument("--also-other-mode", type=int, default=1, help="N=1: also time the other precision policies")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this benchmark measures: the roofline pass "
+                         "(per-launch HIP events), the C4 / C5 configs, the SURVEY §8(f) components, the other "
+                         "precision policies and the CPU-oracle baseline (each still switched by its own flag below); "
+                         "without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: after the timed steps save what the last timed step returned (latent, mel, wav; wav "
+                         "is the gathered one at N>1) as DIR/<name>.npy in float32, at most 64 MB in all (a fixed "
+                         "seeded sample of an array that would not fit)")
+    ap.add_argument("--also-other-mode", type=int, default=1,
+                    help="--full, N=1: also time the other precision policies")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full, N=1: also time the CPU oracle")
     ap.add_argument("--cpu-clips", type=int, default=4,
                     help="prompts in each batched CPU-oracle run (a bounded sample of the configs[1] batch: ~30 s per "
                          "run on 16 EPYC 9575F threads; 32 = the whole batch, ~225 s per run)")
@@ -64,12 +76,15 @@ def parse():
                     help="N>1 rehearsal: comma-separated GPU index per LOCAL_RANK (default: GPU = LOCAL_RANK)")
     ap.add_argument("--dump-wav", default=None, help="rank 0: save the gathered waveforms of the last step (.npy)")
     ap.add_argument("--extra-configs", type=int, default=1,
-                    help="N=1: also time BASELINE configs[3] (C4: B=64, 4 steps + CFG) and configs[4] (C5: B=16, "
+                    help="--full, N=1: also time BASELINE configs[3] (C4: B=64, 4 steps + CFG) and configs[4] (C5: B=16, "
                          "30 s decode) and report them beside the headline")
     ap.add_argument("--components", type=int, default=1,
-                    help="N=1: also time the SURVEY §8(f) components at the configs[1] batch (text encoders, "
+                    help="--full, N=1: also time the SURVEY §8(f) components at the configs[1] batch (text encoders, "
                          "log-mel front-end + Encoder1D), each with its roofline")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def log(msg: str) -> None:
@@ -220,6 +235,26 @@ def cpu_baseline(clips: int, latent_len: int, lcm_steps: int, budget_s: float, r
                        f"({', '.join(f'{t:.1f}' for t in runs)} s) after a batch-1 warm-up")
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, arrays, limit: int = DUMP_LIMIT_BYTES) -> None:
+    """--dump-outputs: save `arrays` (name -> tensor) as path/<name>.npy in float32.  When they would exceed `limit`
+    bytes in all, every array keeps the same fraction of its elements: a sorted sample of flat indices drawn without
+    replacement by a generator seeded with the array's element count alone, so two builds given the same arguments
+    save the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        x = t.detach().to(torch.float32).cpu().numpy()
+        if total > limit:
+            keep = max(1, int(x.size * limit / total))
+            idx = np.sort(np.random.default_rng(x.size).choice(x.size, size=keep, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(x))
+
+
 def pmc_traffic(kernel: str):
     """HBM bytes per launch of `kernel` from the newest committed PMC pass (profiles/<tag>/kernels.json,
     written by scripts/prof_summary.py from separate FETCH_SIZE / WRITE_SIZE runs of this bench)."""
@@ -358,8 +393,6 @@ def main():
     from audiolcm_amd.pipeline import AudioLCMPipeline
     import torch.distributed as dist
 
-    from audiolcm_amd import roofline as RL
-    model_roof = RL.summary(RL.path_layers(B=a.batch, S=a.lcm_steps, T=a.latent_len))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     dev = int(a.device_map.split(",")[local]) if a.device_map else local
     rank, world, local = init_from_env(a.dist_backend, device=dev, force=bool(a.force_collective))
@@ -372,6 +405,7 @@ def main():
     clip_sec = T * 2 * HOP / SR
 
     gathered = {}
+    last = {}  # what the newest step returned (--dump-outputs)
     inflight = []  # the previous step's waveform all-gather (RCCL, async): overlaps this step's kernels
 
     def settle():
@@ -388,6 +422,7 @@ def main():
             inflight.append(work)
         else:
             gathered["wav"] = out["wav"]
+        last["out"] = out
         return out
 
     def timed(k, profile):
@@ -417,67 +452,73 @@ def main():
     # headline: the production schedule (BigVGAN resblock chains on three streams), no per-launch events
     log(f"rank {rank}/{world}: pipeline ready, headline pass ({a.warmup} warm-up + {a.steps} timed steps)")
     dt, _ = timed(a.steps, False)
-    log(f"headline {1e3 * dt / a.steps:.2f} ms/step; roofline pass")
+    log(f"headline {1e3 * dt / a.steps:.2f} ms/step")
     if a.dump_wav and rank == 0:
         import numpy as np
         np.save(a.dump_wav, gathered["wav"].float().cpu().numpy())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(last["out"], wav=gathered["wav"]))
     value = world * B * clip_sec * a.steps / dt
-    # roofline pass: the same steps with live HIP-event timing of every launch and the resblock streams
-    # serialised, so a kernel's measured duration is its own (concurrent kernels would share the chip)
-    pipe.vocoder.set_resblock_streams(False)
-    dt_prof, prof = timed(a.steps, True)
-    pipe.vocoder.set_resblock_streams(True)
-    gpu_ms = sum(p["total_ms"] for p in prof)
-    dom = max(prof, key=lambda p: p["total_ms"]) if prof else None
-    roofline = None
-    if dom:
-        mfma = dom["flops"] / max(dom["bytes"], 1) > _hip.PEAK_BF16_FLOPS / _hip.PEAK_HBM_BYTES
-        sec = dom["total_ms"] / 1e3
-        if mfma:
-            ach, peak, unit = dom["flops"] / sec / 1e12, _hip.PEAK_BF16_FLOPS / 1e12, "TFLOP/s"
-        else:
-            ach, peak, unit = dom["bytes"] / sec / 1e9, _hip.PEAK_HBM_BYTES / 1e9, "GB/s"
-        roofline = dict(bound="mfma" if mfma else "hbm", achieved=round(ach, 2), peak=peak, unit=unit,
-                        frac=round(ach / peak, 4), traffic=None, kernel=dom["name"], launches=dom["launches"],
-                        avg_launch_us=round(1e3 * dom["total_ms"] / dom["launches"], 2),
-                        per_launch_algorithmic=round((dom["flops"] if mfma else dom["bytes"]) / dom["launches"], 1),
-                        kernel_share_of_gpu_time=round(dom["total_ms"] / max(gpu_ms, 1e-9), 4),
-                        path_roofline_frac_model=round(model_roof["t_roof_ms"] / (1e3 * dt / a.steps), 4),
-                        path_roofline_model=dict(
-                            t_roof_ms=round(model_roof["t_roof_ms"], 3), gflop=round(model_roof["gflop"], 1),
-                            gbytes=round(model_roof["gbytes"], 2),
-                            ideal_value=round(B * clip_sec / model_roof["t_roof_ms"] * 1e3, 1),
-                            note="SURVEY.md §8(d) model (audiolcm_amd/roofline.py): bf16 layer-boundary bytes, "
-                                 "sum over layers of max(F/2.5PF, B/8TB/s); frac = t_roof / ms_per_step"),
-                        path_roofline_frac_build=round(sum(p["roof_ms"] for p in prof) / (1e3 * dt), 4),
-                        path_roofline_note_build="sum over this build's kernel launches of max(F/2.5PF, B/8TB/s) "
-                                                 "(fp32 activations, unfused byte counts) / headline wall",
-                        measured_in=f"separate timed pass of the same {a.steps} steps, per-launch HIP events on the "
-                                    f"launch streams, resblock streams serialised ({1e3 * dt_prof / a.steps:.2f} "
-                                    f"ms/step)")
-        hb = sum(p["hbm_bytes"] for p in prof)
-        hms = sum(p["hbm_ms"] for p in prof)
-        if hms > 0:  # the HBM fraction of the HBM-bound subset of launches
-            roofline["hbm_subset"] = dict(
-                achieved=round(hb / (hms / 1e3) / 1e9, 1), peak=_hip.PEAK_HBM_BYTES / 1e9, unit="GB/s",
-                frac=round(hb / (hms / 1e3) / _hip.PEAK_HBM_BYTES, 4),
-                launches_per_step=round(sum(p["hbm_launches"] for p in prof) / a.steps, 1),
-                ms_per_step=round(hms / a.steps, 3), share_of_gpu_time=round(hms / max(gpu_ms, 1e-9), 4),
-                algorithmic_gb_per_step=round(hb / a.steps / 1e9, 3),
-                note="launches whose algorithmic flops/bytes < 2.5 PF / 8 TB/s: sum of this build's algorithmic bytes "
-                     "/ (sum of their event time x 8 TB/s)",
-                # the same time against the §8(d) model's bytes (bf16 layer boundaries, Activation1d fused), so the
-                # fraction cannot rise by moving more bytes
-                model_gb_per_step=round(model_roof["hbm_bound_gbytes"], 3),
-                frac_model_bytes=round(model_roof["hbm_bound_gbytes"] * 1e9 / (hms / a.steps / 1e3) /
-                                       _hip.PEAK_HBM_BYTES, 4),
-                path_frac_model_bytes=round(model_roof["gbytes"] * 1e9 / (dt / a.steps) / _hip.PEAK_HBM_BYTES, 4),
-                note_model="frac_model_bytes: the §8(d) model's bytes of its HBM-bound layers / (the same event time x "
-                           "8 TB/s); path_frac_model_bytes: all of the model's bytes / (headline wall x 8 TB/s)")
-        tr = pmc_traffic(dom["name"])
-        if tr:  # HBM bytes per launch from the committed PMC passes of this kernel
-            roofline["traffic"] = tr["bytes_per_launch"]
-            roofline["traffic_source"] = tr["source"]
+    roofline, prof = None, []
+    if a.full:
+        from audiolcm_amd import roofline as RL
+        model_roof = RL.summary(RL.path_layers(B=B, S=S, T=T))
+        log("roofline pass")
+        # roofline pass: the same steps with live HIP-event timing of every launch and the resblock streams
+        # serialised, so a kernel's measured duration is its own (concurrent kernels would share the chip)
+        pipe.vocoder.set_resblock_streams(False)
+        dt_prof, prof = timed(a.steps, True)
+        pipe.vocoder.set_resblock_streams(True)
+        gpu_ms = sum(p["total_ms"] for p in prof)
+        dom = max(prof, key=lambda p: p["total_ms"]) if prof else None
+        if dom:
+            mfma = dom["flops"] / max(dom["bytes"], 1) > _hip.PEAK_BF16_FLOPS / _hip.PEAK_HBM_BYTES
+            sec = dom["total_ms"] / 1e3
+            if mfma:
+                ach, peak, unit = dom["flops"] / sec / 1e12, _hip.PEAK_BF16_FLOPS / 1e12, "TFLOP/s"
+            else:
+                ach, peak, unit = dom["bytes"] / sec / 1e9, _hip.PEAK_HBM_BYTES / 1e9, "GB/s"
+            roofline = dict(bound="mfma" if mfma else "hbm", achieved=round(ach, 2), peak=peak, unit=unit,
+                            frac=round(ach / peak, 4), traffic=None, kernel=dom["name"], launches=dom["launches"],
+                            avg_launch_us=round(1e3 * dom["total_ms"] / dom["launches"], 2),
+                            per_launch_algorithmic=round((dom["flops"] if mfma else dom["bytes"]) / dom["launches"], 1),
+                            kernel_share_of_gpu_time=round(dom["total_ms"] / max(gpu_ms, 1e-9), 4),
+                            path_roofline_frac_model=round(model_roof["t_roof_ms"] / (1e3 * dt / a.steps), 4),
+                            path_roofline_model=dict(
+                                t_roof_ms=round(model_roof["t_roof_ms"], 3), gflop=round(model_roof["gflop"], 1),
+                                gbytes=round(model_roof["gbytes"], 2),
+                                ideal_value=round(B * clip_sec / model_roof["t_roof_ms"] * 1e3, 1),
+                                note="SURVEY.md §8(d) model (audiolcm_amd/roofline.py): bf16 layer-boundary bytes, "
+                                     "sum over layers of max(F/2.5PF, B/8TB/s); frac = t_roof / ms_per_step"),
+                            path_roofline_frac_build=round(sum(p["roof_ms"] for p in prof) / (1e3 * dt), 4),
+                            path_roofline_note_build="sum over this build's kernel launches of max(F/2.5PF, B/8TB/s) "
+                                                     "(fp32 activations, unfused byte counts) / headline wall",
+                            measured_in=f"separate timed pass of the same {a.steps} steps, per-launch HIP events on the "
+                                        f"launch streams, resblock streams serialised ({1e3 * dt_prof / a.steps:.2f} "
+                                        f"ms/step)")
+            hb = sum(p["hbm_bytes"] for p in prof)
+            hms = sum(p["hbm_ms"] for p in prof)
+            if hms > 0:  # the HBM fraction of the HBM-bound subset of launches
+                roofline["hbm_subset"] = dict(
+                    achieved=round(hb / (hms / 1e3) / 1e9, 1), peak=_hip.PEAK_HBM_BYTES / 1e9, unit="GB/s",
+                    frac=round(hb / (hms / 1e3) / _hip.PEAK_HBM_BYTES, 4),
+                    launches_per_step=round(sum(p["hbm_launches"] for p in prof) / a.steps, 1),
+                    ms_per_step=round(hms / a.steps, 3), share_of_gpu_time=round(hms / max(gpu_ms, 1e-9), 4),
+                    algorithmic_gb_per_step=round(hb / a.steps / 1e9, 3),
+                    note="launches whose algorithmic flops/bytes < 2.5 PF / 8 TB/s: sum of this build's algorithmic bytes "
+                         "/ (sum of their event time x 8 TB/s)",
+                    # the same time against the §8(d) model's bytes (bf16 layer boundaries, Activation1d fused), so the
+                    # fraction cannot rise by moving more bytes
+                    model_gb_per_step=round(model_roof["hbm_bound_gbytes"], 3),
+                    frac_model_bytes=round(model_roof["hbm_bound_gbytes"] * 1e9 / (hms / a.steps / 1e3) /
+                                           _hip.PEAK_HBM_BYTES, 4),
+                    path_frac_model_bytes=round(model_roof["gbytes"] * 1e9 / (dt / a.steps) / _hip.PEAK_HBM_BYTES, 4),
+                    note_model="frac_model_bytes: the §8(d) model's bytes of its HBM-bound layers / (the same event time x "
+                               "8 TB/s); path_frac_model_bytes: all of the model's bytes / (headline wall x 8 TB/s)")
+            tr = pmc_traffic(dom["name"])
+            if tr:  # HBM bytes per launch from the committed PMC passes of this kernel
+                roofline["traffic"] = tr["bytes_per_launch"]
+                roofline["traffic_source"] = tr["source"]
     line = dict(metric=METRIC, value=round(value, 2), unit="audio-s/s",
                 n_gpus=dist.get_world_size() if dist.is_initialized() else world, steps=a.steps,
                 warmup=a.warmup, ms_per_step=round(1e3 * dt / a.steps, 2), higher_is_better=True, scaling="weak",
@@ -490,13 +531,13 @@ def main():
                             parallelism=f"dp{world} (prompt shards, RCCL all-gather of waveforms)",
                             dist_backend=dist.get_backend() if dist.is_initialized() else None),
                 roofline=roofline)
-    if world == 1 and a.extra_configs:
+    if a.full and world == 1 and a.extra_configs:
         log("other configs (C4, C5)")
         line["other_configs"] = extra_configs(pipe, a)
-    if world == 1 and a.components:
+    if a.full and world == 1 and a.components:
         log("SURVEY §8(f) components (text encoders, mel + Encoder1D)")
         line["components"] = components(a)
-    if world == 1 and a.also_other_mode:
+    if a.full and world == 1 and a.also_other_mode:
         log("other precision policies")
         for other in ("mixed", "split", "bf16"):
             if other == a.mode:
@@ -506,11 +547,12 @@ def main():
             line[f"{other}_mode"] = dict(value=round(B * clip_sec * a.steps / dt2, 2),
                                          ms_per_step=round(1e3 * dt2 / a.steps, 2), dtype=DTYPES[other])
         pipe.set_split(a.mode)
-    if rank == 0 and world == 1 and a.cpu_baseline:
+    if a.full and rank == 0 and world == 1 and a.cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(a.cpu_clips, T, S, a.cpu_budget_s)
     if rank == 0:
-        line["kernels"] = sorted(({k: (round(v, 3) if isinstance(v, float) else v) for k, v in p.items()}
-                                  for p in prof), key=lambda p: -p["total_ms"])[:8]
+        if a.full:
+            line["kernels"] = sorted(({k: (round(v, 3) if isinstance(v, float) else v) for k, v in p.items()}
+                                      for p in prof), key=lambda p: -p["total_ms"])[:8]
         if os.environ.get("ALCM_BENCH_ALL_KERNELS"):
             for p in sorted(prof, key=lambda p: -p["total_ms"]):
                 print(f"{p['name'][:72]:72s} n={p['launches']:5d} {p['total_ms'] / a.steps:8.3f} ms/step "

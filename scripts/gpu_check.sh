@@ -1,9 +1,11 @@
 #!/bin/bash
-# GPU-box check: the full -m gpu suite then the default bench line.  Usage: bash scripts/gpu_check.sh <tag>
+# GPU check: the whole -m gpu suite, then the bench line with everything in it (--full).
+# Usage: bash scripts/gpu_check.sh <tag>
 tag=${1:-check}
-mkdir -p gpurun_out/$tag
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -s > gpurun_out/$tag/tests.log 2>&1
+out=${OUT:-out}/$tag  # results folder: OUT (default ./out) / tag
+mkdir -p $out
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -s > $out/tests.log 2>&1
 rc=$?
-echo "TESTS EXIT $rc" >> gpurun_out/$tag/tests.log
+echo "TESTS EXIT $rc" >> $out/tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py > gpurun_out/$tag/bench.log 2>&1
+timeout -k 10 400 python -u bench.py --full > $out/bench.log 2>&1

@@ -4,7 +4,7 @@
 tag=${1:-comp}
 variants=${2:-"-"}
 out=gpurun_out/$tag; mkdir -p $out
-ARGS="--steps 5 --warmup 2 --also-other-mode 0 --cpu-baseline 0 --extra-configs 0 --components 1"
+ARGS="--full --steps 5 --warmup 2 --also-other-mode 0 --cpu-baseline 0 --extra-configs 0 --components 1"
 for round in 1 2; do
   for v in $variants; do
     envs=""

@@ -22,7 +22,7 @@ for m in $micro; do
   timeout -k 10 600 python -u scripts/microbench.py $m > $out/micro_$m.txt 2>&1 || exit $?
   cat $out/micro_$m.txt
 done
-ARGS="--steps 5 --warmup 2 --also-other-mode 0 --cpu-baseline 0 --extra-configs 0 --components 0"
+ARGS="--full --steps 5 --warmup 2 --also-other-mode 0 --cpu-baseline 0 --extra-configs 0 --components 0"
 for round in 1 2; do
   for v in $variants; do
     envs=""

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU-box validation of HEAD in two calls (each fits gpurun's limit):
 #   bash scripts/gpu_validate.sh <tag> tests   -> the whole -m gpu suite, smoke(), rocprofv3 stats + PMC passes
-#   bash scripts/gpu_validate.sh <tag> bench   -> the driver's bench command (default cpu_baseline included)
+#   bash scripts/gpu_validate.sh <tag> bench   -> the bench command with --full (roofline pass, other configs, cpu_baseline)
 tag=${1:-validate}; what=${2:-tests}
 out=gpurun_out/$tag; mkdir -p $out
 if [ "$what" = tests ]; then
@@ -14,6 +14,6 @@ if [ "$what" = tests ]; then
   tail -3 $out/smoke.log
   bash scripts/profile_bench.sh $tag || exit $?
 else
-  timeout -k 10 700 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit $?
+  timeout -k 10 700 python3 -u bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench.json 2> $out/bench.err || exit $?
   cat $out/bench.json
 fi

@@ -79,7 +79,7 @@ def main():
     json.dump(out, open(os.path.join(dst, "kernels.json"), "w"), indent=1)
     with open(os.path.join(dst, "SUMMARY.md"), "w") as fh:
         fh.write(f"# rocprofv3 summary ({os.path.basename(dst)})\n\n"
-                 "Source: `scripts/profile_bench.sh` (rocprofv3 kernel-trace --stats over `bench.py --steps 2 --warmup 1` "
+                 "Source: `scripts/profile_bench.sh` (rocprofv3 kernel-trace --stats over `bench.py --full --steps 2 --warmup 1` "
                  "with ALCM_SERIAL_RESBLOCKS=1 — the bench's headline pass plus its roofline pass — then separate "
                  "`--pmc FETCH_SIZE`, `--pmc WRITE_SIZE` and MFMA passes over one step).  HBM read = "
                  "2 x FETCH_SIZE (gfx950 correction), write = WRITE_SIZE, averaged per launch.  MFMA busy % = "

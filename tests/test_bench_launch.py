@@ -98,3 +98,22 @@ def test_spawn_ranks_propagates_failure(tmp_path, monkeypatch):
     script.write_text(RANK_SCRIPT)
     monkeypatch.setenv("FAIL_RANK", "1")
     assert bench.spawn_ranks(2, [], script=str(script)) != 0
+
+
+def test_dump_outputs_float32_and_size_cap(tmp_path):
+    """--dump-outputs: one float32 .npy per array; over the byte limit every array keeps the same share of its
+    elements at positions that depend on nothing but its size (two builds save the same sample)."""
+    import numpy as np
+    import torch
+    arrays = {"wav": torch.arange(6000, dtype=torch.float64).reshape(6, 1000), "mel": torch.ones(2, 500)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    w = np.load(tmp_path / "whole" / "wav.npy")
+    assert w.dtype == np.float32 and w.shape == (6, 1000) and np.array_equal(w, arrays["wav"].numpy())
+    assert np.load(tmp_path / "whole" / "mel.npy").shape == (2, 500)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=7000)
+    wa, wb = np.load(tmp_path / "a" / "wav.npy"), np.load(tmp_path / "b" / "wav.npy")
+    ma = np.load(tmp_path / "a" / "mel.npy")
+    assert wa.dtype == np.float32 and wa.shape == (1500,) and ma.shape == (250,)
+    assert wa.nbytes + ma.nbytes <= 7000
+    assert np.array_equal(wa, wb) and np.all(np.diff(wa) > 0)  # same, sorted, distinct positions

@@ -85,8 +85,8 @@ def test_bench_rccl_world1_collectives(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     bench = os.path.join(REPO, "bench.py")
-    one = _run([sys.executable, bench, "--gpus", "1", "--batch", "32", "--dump-wav", str(tmp_path / "w1.npy")]
-               + ARGS, tmp_path, "plain")
+    one = _run([sys.executable, bench, "--gpus", "1", "--batch", "32", "--dump-wav", str(tmp_path / "w1.npy"),
+                "--dump-outputs", str(tmp_path / "outs")] + ARGS, tmp_path, "plain")
     rc = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                "--master-addr=127.0.0.1", "--master-port=29587", bench, "--gpus", "1", "--batch", "32",
                "--dist-backend", "nccl", "--force-collective", "1", "--dump-wav", str(tmp_path / "wr.npy")] + ARGS,
@@ -97,3 +97,9 @@ def test_bench_rccl_world1_collectives(tmp_path):
     w1, wr = np.load(tmp_path / "w1.npy"), np.load(tmp_path / "wr.npy")
     assert w1.shape == wr.shape == (32, 159744)
     assert np.array_equal(w1, wr), log[-3000:]
+    # --dump-outputs: what the last timed step returned, float32; a plain run's line carries no roofline pass
+    outs = {n: np.load(tmp_path / "outs" / f"{n}.npy") for n in ("latent", "mel", "wav")}
+    assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in outs.values())
+    assert outs["latent"].shape == (32, 20, 312) and outs["mel"].shape == (32, 80, 624)
+    assert np.array_equal(outs["wav"], w1)
+    assert one["roofline"] is None and "kernels" not in one and "cpu_baseline" not in one

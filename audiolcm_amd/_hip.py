@@ -85,6 +85,9 @@ _SIGS = [
     ("alcm_opconv_sum", C.c_int, [C.POINTER(OpConvArgs), C.c_int, vp]),
     ("alcm_opconv_dense", C.c_int, [C.POINTER(OpConvArgs), vp]),
     ("alcm_flash_attention", C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_flash_attention_ex", C.c_int, [fp, vp, fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, C.c_int,
+                                          C.c_float, vp]),
+    ("alcm_softmax_rows_bias", C.c_int, [fp, C.c_int, C.c_int, i64, C.c_int, C.c_int, fp, C.c_int, vp]),
     ("alcm_layer_norm_plane", C.c_int, [fp, C.c_int, C.c_int, i64, C.c_float, fp, fp, vp, C.c_int, vp]),
     ("alcm_lcm_step", C.c_int, [fp, fp, fp, C.POINTER(C.c_float), fp, fp, i64, vp]),
     ("alcm_lcm_step_cfg", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), fp, fp, i64, vp]),

@@ -37,6 +37,19 @@ __device__ __forceinline__ u16 fa_cvt(float v) {
   else return __builtin_bit_cast(u16, (__bf16)v);
 }
 
+// plane element of the output o * inv.  Contract (chosen, not a matter of accuracy): a plane holds exactly the fp32
+// output rounded to the operand format, so the plane and fp32 forms of one call agree bit for bit
+// (tests/test_gpu_attention.py::test_plane_forms_agree_bitwise) and a consumer may take either.  Left to the compiler,
+// fp16 becomes one v_fma_mixlo_f16, which rounds the exact product once: no less accurate, but an fp16 ulp away from
+// the fp32 form wherever the fp32 value is a tie (~1e-4 of the elements).  The empty asm keeps the fp32 product in a
+// register of its own (one more VALU op per stored element); do not fold it back.
+template <int PREC>
+__device__ __forceinline__ u16 fa_cvt_out(float o, float inv) {
+  float r = o * inv;
+  asm volatile("" : "+v"(r));
+  return fa_cvt<PREC>(r);
+}
+
 template <int PREC>
 __global__ __launch_bounds__(256) void flash_attn_kernel(const float* __restrict__ qkv, float* __restrict__ O,
                                                          u16* __restrict__ Op, int L, int H, int nh, int dh,
@@ -172,7 +185,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const float* __restrict
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int d = 16 * db + 4 * g + r;
-        if (d < dh) Op[ob + d] = fa_cvt<PREC>(o[db][r] * inv);
+        if (d < dh) Op[ob + d] = fa_cvt_out<PREC>(o[db][r], inv);
       }
     return;
   }
@@ -408,7 +421,7 @@ __global__ __launch_bounds__(FR_THREADS) void flash_attn_res_kernel(const void* 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int d = 16 * db + 4 * g + r;
-          if (d < dh) Op[ob + d] = fa_cvt<PREC>(o[db][r] * inv);
+          if (d < dh) Op[ob + d] = fa_cvt_out<PREC>(o[db][r], inv);
         }
     } else {
 #pragma unroll
@@ -496,4 +509,11 @@ int flash_attention(const float* qkv, float* O, int B, int L, int H, int nh, int
 extern "C" int alcm_flash_attention(const float* qkv, float* out, int B, int L, int H, int heads, int prec,
                                     alcm_stream_t stream) {
   return alcm::flash_attention(qkv, out, B, L, H, heads, prec, (hipStream_t)stream);
+}
+
+extern "C" int alcm_flash_attention_ex(const float* qkv, const void* qkv_plane, float* out, void* out_plane, int B, int L,
+                                       int H, int heads, int prec, const float* bias, int bld, float scale,
+                                       alcm_stream_t stream) {
+  return alcm::flash_attention(qkv, out, B, L, H, heads, prec, (hipStream_t)stream, out_plane, bias, bld, scale,
+                               qkv_plane);
 }

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void softmax_bias_kernel(float* x, int rows, i
 
 int softmax_rows_bias(float* x, int rows, int n, int64_t ld, int L, int heads, const float* bias, int bld,
                       hipStream_t s) {
-  if (!x || !bias || rows <= 0 || n <= 0 || ld < n || L <= 0 || heads <= 0 || bld < n)
+  if (!x || !bias || rows <= 0 || n <= 0 || ld < n || L <= 0 || heads <= 0 || bld < n || bld < L)  // bias rows i < L
     return set_error(ALCM_E_INVALID, "softmax_rows_bias: bad arguments");
   hipLaunchKernelGGL(softmax_bias_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, rows, n, ld, L, heads, bias, bld);
   ALCM_HIP(hipGetLastError());
@@ -198,3 +198,8 @@ int softmax_rows_bias(float* x, int rows, int n, int64_t ld, int L, int heads, c
 }
 
 }  // namespace alcm
+
+extern "C" int alcm_softmax_rows_bias(float* x, int rows, int n, int64_t ld, int L, int heads, const float* bias, int bld,
+                                      alcm_stream_t stream) {
+  return alcm::softmax_rows_bias(x, rows, n, ld, L, heads, bias, bld, (hipStream_t)stream);
+}

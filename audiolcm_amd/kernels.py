@@ -262,11 +262,34 @@ def layer_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: fl
     return y
 
 
-def softmax_(x: torch.Tensor) -> torch.Tensor:
-    """In-place softmax over the last dim of a contiguous tensor."""
+def _score_rows(x: torch.Tensor, ld: Optional[int]) -> Tuple[int, int, int]:
+    """(rows, n, ld) of a score tensor: contiguous (ld None), or the first n columns ``buf[:, :n]`` of a contiguous
+    (rows, ld) buffer."""
     n = x.shape[-1]
-    rows = x.numel() // n
-    check(lib().alcm_softmax_rows(ptr(x), rows, n, n, stream_handle()), "softmax_rows")
+    if ld is None:
+        assert x.is_contiguous()    # the kernel walks rows of pitch n: a strided view was silently misread before
+        return x.numel() // n, n, n
+    assert x.dim() == 2 and ld >= n and x.stride(1) == 1 and (x.shape[0] == 1 or x.stride(0) == ld)
+    return x.shape[0], n, int(ld)
+
+
+def softmax_(x: torch.Tensor, ld: Optional[int] = None) -> torch.Tensor:
+    """In-place softmax over the last dim of a contiguous tensor.  With ``ld``, x is the first n columns
+    ``buf[:, :n]`` of a contiguous (rows, ld) buffer, whose columns [n, ld) are zeroed."""
+    rows, n, ld = _score_rows(x, ld)
+    check(lib().alcm_softmax_rows(ptr(x), rows, n, ld, stream_handle()), "softmax_rows")
+    return x
+
+
+def softmax_bias_(x: torch.Tensor, bias: torch.Tensor, L: int, ld: Optional[int] = None) -> torch.Tensor:
+    """In-place softmax(x + bias[h, i, :n]) of T5's scores: rows (z, i) with i < L and head h = z % heads, bias
+    (heads, bld, bld) fp32.  ``ld`` as in softmax_."""
+    rows, n, ld = _score_rows(x, ld)
+    heads, bld = bias.shape[0], bias.shape[-1]
+    assert bias.dtype == torch.float32 and tuple(bias.shape) == (heads, bld, bld) and bias.is_contiguous()
+    assert rows % L == 0
+    check(lib().alcm_softmax_rows_bias(ptr(x), rows, n, ld, int(L), heads, ptr(bias), bld, stream_handle()),
+          "softmax_rows_bias")
     return x
 
 
@@ -483,14 +506,39 @@ def opconv(planes: torch.Tensor, C_real: int, w: torch.Tensor, bias: Optional[to
     return out
 
 
-def flash_attention(qkv: torch.Tensor, heads: int, prec: int) -> torch.Tensor:
-    """(B, L, 3H) fp32 [q | k | v] rows -> (B, L, H) multi-head softmax(q k^T / sqrt(dh)) v (fused kernel)."""
-    B, L, H3 = qkv.shape
+def flash_attention(qkv: Optional[torch.Tensor], heads: int, prec: int, *, bias: Optional[torch.Tensor] = None,
+                    scale: float = 0.0, qkv_plane: Optional[torch.Tensor] = None,
+                    out_plane: bool = False) -> torch.Tensor:
+    """(B, L, 3H) fp32 [q | k | v] rows -> (B, L, H) multi-head softmax(q k^T / sqrt(dh)) v (fused kernel).
+
+    The keywords reach the forms the models launch (alcm_flash_attention_ex): ``bias`` (heads, bld, bld) fp32 added
+    to the scores, ``scale`` > 0 instead of dh^-1/2, ``qkv_plane`` (B, L, 3H) int16 operand rows (fp16 / bf16 bits of
+    ``prec``) instead of ``qkv``, ``out_plane``: the result as an int16 (B, L, H) operand plane instead of fp32."""
+    if bias is None and scale == 0.0 and qkv_plane is None and not out_plane:
+        # the plain call stays on alcm_flash_attention, so that the older entry keeps being exercised by the tests
+        B, L, H3 = qkv.shape
+        H = H3 // 3
+        qkv = qkv.contiguous()
+        out = torch.empty((B, L, H), device=qkv.device)
+        check(lib().alcm_flash_attention(ptr(qkv), ptr(out), B, L, H, heads, int(prec), stream_handle()),
+              "flash_attention")
+        return out
+    src = qkv_plane if qkv_plane is not None else qkv
+    B, L, H3 = src.shape
     H = H3 // 3
-    qkv = qkv.contiguous()
-    out = torch.empty((B, L, H), device=qkv.device)
-    check(lib().alcm_flash_attention(ptr(qkv), ptr(out), B, L, H, heads, int(prec), stream_handle()),
-          "flash_attention")
+    if qkv is not None:
+        assert qkv.dtype == torch.float32 and tuple(qkv.shape) == (B, L, H3)
+        qkv = qkv.contiguous()
+    if qkv_plane is not None:
+        assert qkv_plane.dtype == torch.int16 and qkv_plane.is_contiguous()
+    bld = 0
+    if bias is not None:
+        bld = bias.shape[-1]
+        assert bias.dtype == torch.float32 and tuple(bias.shape) == (heads, bld, bld) and bias.is_contiguous()
+    out = torch.empty((B, L, H), device=src.device, dtype=torch.int16 if out_plane else torch.float32)
+    check(lib().alcm_flash_attention_ex(ptr(qkv), ptr(qkv_plane), None if out_plane else ptr(out),
+                                        ptr(out) if out_plane else None, B, L, H, heads, int(prec), ptr(bias), bld,
+                                        float(scale), stream_handle()), "flash_attention_ex")
     return out
 
 

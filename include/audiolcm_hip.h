@@ -248,6 +248,25 @@ int alcm_opconv_dense(const alcm_opconv_args* args, alcm_stream_t stream);
  * qkv: (B, L, 3H) fp32 DEVICE rows [q | k | v] (16-byte aligned), out: (B, L, H) fp32; dh = H / heads <= 72;
  * prec: ALCM PREC_F16 (2) or PREC_BF16 (0) operand rounding of q, k, v and the probabilities. */
 int alcm_flash_attention(const float* qkv, float* out, int B, int L, int H, int heads, int prec, alcm_stream_t stream);
+/* alcm_flash_attention_ex: the same fused attention with every form the models launch — the DiT self-attention
+ * (ldm/modules/new_attention.py:89-130) and, inside FrozenCLAPFLANEmbedder.encode (ldm/modules/encoders/modules.py:
+ * 567-582), HF BertSelfAttention (no bias, dh^-1/2) and HF T5Attention (position bias, unscaled scores):
+ * out[b, i, h*dh:(h+1)*dh] = softmax_j(scale * q_i . k_j + bias[h][i][j]) v_j.
+ *   input, exactly one of: qkv (B, L, 3H) fp32 rows (16-byte aligned), or qkv_plane (B, L, 3H) rows of 2-byte operand
+ *     elements in the format of prec (row pitch 3H, 8-byte aligned, L <= 512);
+ *   output: out_plane != NULL: (B, L, H) rows of 2-byte elements in the format of prec (row pitch H, the result
+ *     rounded once more), out is not written; otherwise out (B, L, H) fp32;
+ *   bias: NULL, or fp32 [heads][bld][bld] with bld >= L, element (h, i, j) added to the score of query i and key j
+ *     (L <= 512); scale: 0 = dh^-1/2, > 0 replaces it (L <= 512).
+ * dh = H / heads <= 72, dh % 4 == 0; prec ALCM_PREC_F16 (2) or ALCM_PREC_BF16 (0).  ALCM_E_INVALID otherwise. */
+int alcm_flash_attention_ex(const float* qkv, const void* qkv_plane, float* out, void* out_plane, int B, int L, int H,
+                            int heads, int prec, const float* bias, int bld, float scale, alcm_stream_t stream);
+/* alcm_softmax_rows_bias: in-place softmax of HF T5Attention's scores + position_bias (the split-policy text
+ * tower of FrozenCLAPFLANEmbedder.encode, ldm/modules/encoders/modules.py:567-582): rows = Z*L rows of pitch ld,
+ * row r = (z, i) with i = r % L, head h = z % heads: x[r][j] = softmax_j(x[r][j] + bias[(h*bld + i)*bld + j]) for
+ * j < n, and x[r][n..ld) = 0 (the K padding the P.V GEMM reads).  bld >= max(n, L), ld >= n. */
+int alcm_softmax_rows_bias(float* x, int rows, int n, int64_t ld, int L, int heads, const float* bias, int bld,
+                           alcm_stream_t stream);
 
 /* ---------------------------------------------------------------- LCM scheduler pieces */
 /* coeffs (HOST array of 6): {sqrt_a, sqrt_b, c_out, c_skip, sqrt_a_prev, sqrt_b_prev};

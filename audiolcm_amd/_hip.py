@@ -55,6 +55,11 @@ class OpConvArgs(C.Structure):
                 ("ksplit_ws", fp), ("ksplit_ws_floats", i64)]
 
 
+class ConvPlanInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 160), ("kernel", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("grid", i64),
+                ("ksplit", C.c_int), ("n_major", C.c_int), ("ncu", C.c_int)]
+
+
 class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", vp), ("ndim", C.c_int), ("shape", i64 * 4)]
 
@@ -102,6 +107,9 @@ _SIGS = [
     ("alcm_reload_knobs", C.c_int, []),
     ("alcm_debug_tconv_trace", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     ("alcm_debug_tconv_wg_times", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
+    ("alcm_debug_conv_plan", C.c_int, [C.POINTER(OpConvArgs), C.c_int, C.c_int, C.c_int, C.POINTER(ConvPlanInfo),
+                                       C.POINTER(C.c_int)]),
+    ("alcm_debug_ksplit_parts", C.c_int, [i64, i64, C.c_int, C.c_double, C.c_double]),
     ("alcm_dit_workspace_bytes", C.c_size_t, [vp, C.c_int, C.c_int]),
     ("alcm_dit_embed_context", C.c_int, [vp, fp, C.c_int, fp, vp, C.c_size_t, vp]),
     ("alcm_dit_forward", C.c_int, [vp, fp, vp, fp, fp, fp, C.c_int, C.c_int, vp, C.c_size_t, vp]),
@@ -196,6 +204,22 @@ def debug_tconv_wg_times(n_wg: int) -> list:
     if n < 0:
         check(n, "alcm_debug_tconv_wg_times")
     return [tuple(out[4 * i: 4 * i + 4]) for i in range(n)]
+
+
+CONV_KERNELS = ("lin_plane", "wconv3", "wconv3_sum", "wconv2", "nconv", "opconv_kernel")
+
+
+def debug_conv_plan(args, n: int = 1, as_sum: bool = False, ncu: int = 0) -> list:
+    """Diagnostics: the launches alcm_opconv (one OpConvArgs) or alcm_opconv_sum (as_sum: an array of n) would make under
+    the current ALCM_* switches on ncu compute units (0 = the current device's), one dict per launch; raises HipError
+    with the call's own error.  Host only: nothing is launched or dereferenced (alcm_debug_conv_plan)."""
+    out = (ConvPlanInfo * 3)()
+    nl = C.c_int(0)
+    a = args if as_sum else C.byref(args)
+    check(lib().alcm_debug_conv_plan(a, n, int(as_sum), ncu, out, C.byref(nl)), "alcm_debug_conv_plan")
+    return [dict(name=out[i].name.decode(), kernel=CONV_KERNELS[out[i].kernel], bm=out[i].bm, bn=out[i].bn,
+                 grid=int(out[i].grid), ksplit=out[i].ksplit, n_major=out[i].n_major, ncu=out[i].ncu)
+            for i in range(nl.value)]
 
 
 PEAK_BF16_FLOPS = 2.5e15   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, spec)

@@ -4,6 +4,7 @@
 // so the conv output never makes an fp32 round trip through HBM before the next conv reads it.
 #pragma once
 #include "alcm_common.h"
+#include "alcm_convplan.h"  // ACT_EPI_HALO
 
 namespace alcm {
 
@@ -161,7 +162,20 @@ struct ActEpiDev {
   Taps12O f;
 };
 
-constexpr int ACT_EPI_HALO = 8;  // conv tile rows computed beyond each side of the emitted rows
+// the fused-Activation1d parameters of an alcm_opconv call (reads the host filter arrays)
+inline ActEpiDev act_epi_of(const alcm_opconv_args& a) {
+  ActEpiDev E{};
+  E.plane = (u16*)a.act_plane;
+  E.plane_lo = a.act_plane_lo_off;
+  E.Cp = (a.N + 31) / 32 * 32;
+  E.aexp = a.act_alpha_exp;
+  E.ibeta = a.act_inv_beta;
+  for (int k = 0; k < 12; ++k) {
+    E.f.up[k] = 2.0f * a.act_up_filter[k];
+    E.f.dn[k] = a.act_down_filter[k];
+  }
+  return E;
+}
 
 // Activation1d of an LDS-staged fp32 tile, R output rows per work item (the caller picks R so that
 // (emitted rows / R) x channel pairs fills its threads: fewer, longer runs also cut the halo recompute,

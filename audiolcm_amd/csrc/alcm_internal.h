@@ -6,6 +6,8 @@
 #include <string>
 
 #include "audiolcm_hip.h"
+#include "alcm_convplan.h"
+#include "alcm_knobs.h"
 
 namespace alcm {
 
@@ -69,8 +71,6 @@ int act_mfma(const void* x, bool x16, void* y, int B, int T, int C, int Cp, cons
 int activation1d_op_h16(const void* x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
                         const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
                         hipStream_t s);
-int nconv_try(const alcm_opconv_args& a, const unsigned short* wplane, const void* actepi, double flops, double bytes,
-              hipStream_t s);
 int opconv(const alcm_opconv_args& a, hipStream_t s);
 // o_plane != nullptr: write the output as an fp16 / bf16 operand plane [B][L][H] instead of fp32 O
 // bias != nullptr: + bias[(head * bld + query) * bld + key] on the scores (L <= 512); scale > 0 replaces 1/sqrt(dh);
@@ -80,11 +80,13 @@ int flash_attention(const float* qkv, float* O, int B, int L, int H, int nh, int
                     const void* qkv_plane = nullptr);
 // whether opconv can fuse Activation1d into its epilogue for N output channels at this precision
 bool opconv_act_supported(int prec, int N, int Cp_in);
-bool wconv3_sum_ok(const alcm_opconv_args* a, int n);
-int wconv3_sum_try(const alcm_opconv_args* a, int n, hipStream_t s);
 int opconv_sum(const alcm_opconv_args* a, int n, hipStream_t s);
-int wconv_try(const alcm_opconv_args& a, const unsigned short* wplane, double flops, double bytes,
-              hipStream_t s);
+// the launches of a ConvPlan (alcm_convplan.h), one per kernel file: fill the kernel's argument struct, pick the
+// instantiation the plan names, launch, record the profile row
+int lin_plane_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s);                    // alcm_sgemm.hip
+int wconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s);                        // alcm_wconv.hip
+int wconv3_sum_launch(const ConvPlan& pl, const alcm_opconv_args* a, int n, hipStream_t s);            // alcm_wconv.hip
+int nconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s);                        // alcm_nconv.hip
 
 // narrow AMPBlock conv with resident dense weights (alcm_tconv.hip); actepi: const ActEpiDev* or nullptr
 bool tconv_supported(int prec, int C, int N, int ksize, int dil);
@@ -103,45 +105,20 @@ bool sgemm_planes_ok(int K, int N, int kpad);
 int sgemm_planes(const unsigned short* a, int64_t a_lo, int M, int K, const unsigned short* w, int64_t w_lo, int kpad,
                  int N, const float* bias, const float* res, int64_t ldr, float* out, int64_t ldo, float out_scale,
                  hipStream_t s);
-// single-plane 1x1 conv / linear (alcm_sgemm.hip, ALCM_LIN1); 1 when it launched, 0 when not eligible
-int lin_plane_try(const alcm_opconv_args& a, const unsigned short* wplane, double flops, double bytes, hipStream_t s);
 int split_planes(const float* x, int64_t rows, int C, int T, const float* scale, const float* shift,
                  unsigned short* y, hipStream_t s);
 
-// diagnostic / A-B switches, read from ALCM_* environment variables at library load (alcm_knobs.cpp)
-struct Knobs {
-  int wconv = 8;                 // ALCM_WCONV: > 0 = the wide-layer kernels (alcm_wconv.hip), 0 = opconv_kernel (A/B)
-  int wconv3 = -1;               // ALCM_WCONV3: persistent 8-wave 256 x 192 wide conv (alcm_wconv.hip): -1 by shape, 0 off, 1 on
-  int wconv3_grid = 0;           // ALCM_WCONV3_GRID: cap on wconv3's persistent workgroups (tests; 0 = one per CU)
-  int nconv = -1;                // ALCM_NCONV: 0 = opconv_kernel for the narrow tail, 2 = nconv for every width
-  int opconv_tile = 0;           // ALCM_OPCONV_TILE: narrow-layer tile variant
-  bool serial_resblocks = false; // ALCM_SERIAL_RESBLOCKS: default of alcm_model_set_resblock_streams
-  bool prof_shapes = false;      // ALCM_PROF_SHAPES: split profile rows per layer shape
-  int tconv_ablate = 0;          // ALCM_TCONV_ABLATE: timing-only ablation bits of the tail convs (1 no epilogue,
-                                 // 2 no MFMA, 4 no window DMA, 8 no plane stores, 16 no fp32 state stores); selects
-                                 // their diagnostics instantiation
-  bool tconv_trace = false;      // ALCM_TCONV_TRACE: per-phase shader-clock trace of the tail convs (alcm_debug_tconv_trace;
-                                 // diagnostics instantiation)
-  int lin1 = -1;                 // ALCM_LIN1: single-plane 1x1 convs on lin_plane_kernel (1: 32-deep 4-stage ring, 2: 64-deep
-                                 // double-buffered, -1: 64-deep for plane outputs), 0 = wconv2
-  int tconv = 1;                 // ALCM_TCONV: narrow conv for BigVGAN stages 3-5: 1 by shape, 2 streamed weights,
-                                 // 3 resident weights (alcm_tconv.hip), 0 = opconv / nconv
-  int act_defer = 1;             // ALCM_ACT_DEFER: act_mfma issues a tile's plane stores one tile late, before the next
-                                 // prefetch (0 = at the end of the tile)
-  int act_mfma = 1;              // ALCM_ACT_MFMA: Activation1d FIRs on MFMA for the wide stages (0 = VALU act_coop)
-  int conv1_h16 = 1;             // ALCM_CONV1_H16: wide-stage AMPBlock conv1 writes an fp16 plane for its Activation1d
-  int act_x3_mfma = 1;           // ALCM_ACT_X3_MFMA: the wide stages' three first Activation1d in one MFMA-FIR pass (0 = three)
-  int nct_cl = 1;                // ALCM_NCT_CL: NCT conv inputs (DiT proj_in, BigVGAN conv_pre) transposed to channels-last
-                                 // first (0 = strided gather in the conv)
-  int ups_t160 = 1;              // ALCM_UPS_T160: strided (upsampler phase) wconv2 launches may take 160-row tiles
-  int gemm_skinny = 1;           // ALCM_GEMM_SKINNY: M <= 64-row k = 1 GEMMs on gemm_skinny_kernel (0 = MFMA tiles)
-  int wconv_sum = 1;             // ALCM_WCONV_SUM: the wide stages' three chains' last conv2 + residual in one sum-form
-                                 // launch writing the next stage's upsampler planes (2 = fp32 output + to_planes,
-                                 // 0 = three accumulating launches)
-  int ksplit = 1;                // ALCM_KSPLIT: wconv3 K parts on under-filled grids where a workspace is given (0 = never)
-  int xp[4] = {0, 0, 0, 0};      // ALCM_XP0..3: scratch switches for an experiment in flight (no default path reads them)
-};
-const Knobs& knobs();
+// compute units of the current device, queried once (256 where the query fails or answers fewer than 8)
+inline int device_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    return (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8)
+               ? n
+               : 256;
+  }();
+  return ncu;
+}
 
 bool prof_enabled();
 void* prof_start(hipStream_t s);

@@ -2,7 +2,7 @@
 // again only on alcm_reload_knobs(): no launch path calls getenv.
 #include <cstdlib>
 
-#include "alcm_internal.h"
+#include "alcm_knobs.h"
 
 namespace alcm {
 

@@ -1607,7 +1607,9 @@ static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, i
         alcm_opconv_args pc[3] = {lastc[0], lastc[1], lastc[2]};
         pc[0].out = nullptr;
         pc[0].out_plane = w.ch[0].pl2;
-        if (wconv3_sum_ok(pc, 3)) {
+        ConvPlan pl[3];
+        int launches = 0;
+        if (conv_sum_plan(pc, 3, device_cus(), knobs(), pl, &launches) == 0 && pl[0].kernel == CK_WCONV3_SUM) {
           lastc[0] = pc[0];
           xpl = w.ch[0].pl2;
         }

@@ -44,7 +44,6 @@ struct NConvDev {
   int act_prefetch;  // ACT: residual prefetched into registers before the K loop
 };
 
-constexpr int NC_HALO = 64;  // max (k-1)*dil
 
 __device__ __forceinline__ void nc_glds4(const void* src, char* lds_base) {
   __builtin_amdgcn_global_load_lds((nc_gbl_void_t*)src, (nc_lds_void_t*)lds_base, 4, 0, 0);
@@ -255,43 +254,22 @@ __global__ __launch_bounds__(256) void nconv_kernel(const NConvDev P) {
   }
 }
 
-// Eligible: single-plane activations (F16 / F16W2 / BF16), N <= 96 with N % 4 == 0, Cp in {32, 64, 96},
-// (k-1)d <= 64, no output activation.  Returns 1 when it launched.
-int nconv_try(const alcm_opconv_args& a, const u16* wplane, const void* actepi, double flops, double bytes,
-              hipStream_t s) {
-  const int nck = knobs().nconv;  // diagnostics / A-B: ALCM_NCONV=0 uses opconv_kernel
-  if (nck == 0) return 0;
-  if (a.prec != PREC_F16 && a.prec != PREC_F16W2 && a.prec != PREC_BF16) return 0;
-  if (a.out_act || a.N > 96 || a.N % 4 || (a.ksize - 1) * a.dil > NC_HALO) return 0;
-  // measured (scripts/microbench.py tail): faster than opconv_kernel at C = 24 only (C = 48 / 96 pad or
-  // lose occupancy); ALCM_NCONV=2 forces it for every narrow shape
-  if (a.Cp != 32 && nck != 2) return 0;
-  if (a.Cp != 32 && a.Cp != 64 && a.Cp != 96) return 0;
-  auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  if (!(al16(a.bias) && al16(a.res) && al16(a.out))) return 0;
-  const bool act = actepi != nullptr;
+// the launch of a CK_NCONV plan (alcm_convplan.cpp)
+int nconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
+  const bool act = pl.act;
   NConvDev P{};
   P.a = (const u16*)a.a;
   P.T = a.T; P.Cp = a.Cp; P.ksize = a.ksize; P.dil = a.dil; P.pad = a.pad;
-  P.w = wplane; P.w_lo = a.w_lo_off; P.kpad = a.kpad; P.N = a.N;
+  P.w = conv_wplane(a); P.w_lo = a.w_lo_off; P.kpad = a.kpad; P.N = a.N;
   P.bias = a.bias; P.res = a.res; P.out = a.out; P.out_scale = a.out_scale; P.accumulate = a.accumulate;
-  if (act) P.act = *reinterpret_cast<const ActEpiDev*>(actepi);
+  if (act) P.act = act_epi_of(a);
   P.act_prefetch = 1;
-  // tile configurations (rows per tile, weight ring depth) sized for >= 2 workgroups per CU where the LDS
-  // allows: C = 24 -> 256 x 32, 4 buffers (36 KB, 4 workgroups per CU); C = 48 -> 256 x 64, 4 buffers (72 KB);
-  // C = 96 -> 128 x 96, 3 buffers (72 KB)
-  int BM, BN, NB;
-  if (a.N <= 32 && a.Cp == 32) BM = 256, BN = 32, NB = 4;
-  else if (a.N <= 64 && a.Cp == 64) BM = 256, BN = 64, NB = 4;
-  else if (a.N <= 96 && a.Cp == 96) BM = 128, BN = 96, NB = 3;
-  else return 0;
-  P.tstride = act ? BM - 2 * ACT_EPI_HALO : BM;
+  const int BN = pl.BN;
+  P.tstride = act ? pl.BM - 2 * ACT_EPI_HALO : pl.BM;
   P.tshift = act ? ACT_EPI_HALO : 0;
-  P.tiles_per_batch = (a.T + P.tstride - 1) / P.tstride;
-  const int64_t nwg = (int64_t)a.B * P.tiles_per_batch;
-  if (nwg >= (1ll << 31)) return 0;
+  P.tiles_per_batch = pl.tiles_per_batch;
   void* tok = prof_start(s);
-  const dim3 grid((unsigned)nwg), blk(256);
+  const dim3 grid((unsigned)pl.grid), blk(256);
   auto go = [&](auto bm_c, auto bn_c, auto nch_c, auto nbuf_c) {
     constexpr int BMv = decltype(bm_c)::value, BNv = decltype(bn_c)::value;
     constexpr int NCH = decltype(nch_c)::value, NBUF = decltype(nbuf_c)::value;
@@ -311,13 +289,8 @@ int nconv_try(const alcm_opconv_args& a, const u16* wplane, const void* actepi, 
     go(integral_constant<int, 256>{}, integral_constant<int, 32>{}, integral_constant<int, 1>{}, integral_constant<int, 4>{});
   else if (BN == 64) go(integral_constant<int, 256>{}, integral_constant<int, 64>{}, integral_constant<int, 2>{}, integral_constant<int, 4>{});
   else go(integral_constant<int, 128>{}, integral_constant<int, 96>{}, integral_constant<int, 3>{}, integral_constant<int, 3>{});
-  if (tok) {
-    char name[112];  // the demangled rocprofv3 name of the instantiation
-    std::snprintf(name, sizeof(name), "alcm::nconv_kernel<%d, %d, %d, %d, %d, %s>", BM, BN, a.Cp / 32, NB, a.prec,
-                  act ? "true" : "false");
-    prof_stop(tok, s, name, flops, bytes);
-  }
-  return 1;
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
+  return 0;
 }
 
 }  // namespace alcm

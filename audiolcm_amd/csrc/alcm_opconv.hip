@@ -148,7 +148,6 @@ struct OpConvDev {
 };
 
 constexpr int OC_AW = 48;       // window row stride (elements): conflict-free fragment reads from any start row
-constexpr int OC_HALO = 64;     // max (k-1)*dil
 
 __device__ __forceinline__ int oc_boff(int r, int kq) { return r * 32 + ((kq ^ ((r >> 2) & 2)) << 3); }
 
@@ -558,38 +557,12 @@ static void launch_opconv_v(const OpConvDev& Q, dim3 grid, int prec, hipStream_t
 }
 
 template <int BM, int BN, int WGM, int WGN, int TPS>
-static int launch_opconv(const OpConvDev& P, int B, int prec, bool act, double flops, double bytes, hipStream_t s) {
-  OpConvDev Q = P;
-  // ACT tiles overlap by 2 * ACT_EPI_HALO rows: each computes BM conv rows and emits BM - 2*HALO
-  Q.tstride = act ? BM - 2 * ACT_EPI_HALO : BM;
-  Q.tshift = act ? ACT_EPI_HALO : 0;
-  Q.tiles_per_batch = (P.T + Q.tstride - 1) / Q.tstride;
-  dim3 grid(B * Q.tiles_per_batch, (P.N + BN - 1) / BN);
-  // LDS-staged epilogue for narrow layers (one tile spans N); wide layers store straight from the
-  // accumulators (measured faster there: the LDS round trip costs more than the coalescing saves)
-  const bool vec = P.N % 4 == 0 && P.N <= BN;
-  if (act && !vec) return set_error(ALCM_E_INVALID, "opconv: fused activation needs N % 4 == 0 and one column tile");
-  void* tok = prof_start(s);
-  if (act) {
-    if constexpr (BN <= 96) launch_opconv_v<BM, BN, WGM, WGN, TPS, true, true>(Q, grid, prec, s);
-  } else if (vec) launch_opconv_v<BM, BN, WGM, WGN, TPS, true, false>(Q, grid, prec, s);
-  else launch_opconv_v<BM, BN, WGM, WGN, TPS, false, false>(Q, grid, prec, s);
-  if (tok) {
-    char name[128];
-    // the demangled rocprofv3 name of the instantiation (bench.py joins the two by name)
-    const int tps = (prec == PREC_SPLIT && BN >= 192) ? 1 : TPS;
-    const bool act3 = act && BM == 128 && prec == PREC_F16 && !P.res;
-    std::snprintf(name, sizeof(name), "alcm::opconv_kernel<%d, %d, %d, %d, %d, %d, %s, %s, %s>", BM, BN, WGM, WGN, prec,
-                  tps, (vec || act) ? "true" : "false", act ? "true" : "false", act3 ? "true" : "false");
-    prof_stop(tok, s, name, flops, bytes);
-  }
-  return 0;
-}
-
-// narrow-layer tile variant (diagnostics / A-B): ALCM_OPCONV_TILE=0 default, 1 = twice the rows per tile,
-// 2 = twice the rows and two taps per K step
-static int tile_variant(int prec) {
-  return prec != PREC_SPLIT ? knobs().opconv_tile : 0;  // the split operands need the default tiles' LDS
+static void launch_opconv(const ConvPlan& pl, const OpConvDev& P, int prec, hipStream_t s) {
+  const dim3 grid((unsigned)(pl.grid / pl.tiles_n), (unsigned)pl.tiles_n);
+  if (pl.act) {
+    if constexpr (BN <= 96) launch_opconv_v<BM, BN, WGM, WGN, TPS, true, true>(P, grid, prec, s);
+  } else if (pl.vec) launch_opconv_v<BM, BN, WGM, WGN, TPS, true, false>(P, grid, prec, s);
+  else launch_opconv_v<BM, BN, WGM, WGN, TPS, false, false>(P, grid, prec, s);
 }
 
 bool opconv_act_supported(int prec, int N, int Cp_in) {
@@ -599,52 +572,14 @@ bool opconv_act_supported(int prec, int N, int Cp_in) {
   return N <= 96;
 }
 
-int opconv(const alcm_opconv_args& a, hipStream_t s) {
-  const bool act = a.act_plane != nullptr;
-  if (!a.a || !a.w || (!a.out && !act && !a.geglu_plane && !a.out_plane) || a.B <= 0 || a.T <= 0 || a.N <= 0 || a.ksize <= 0 || a.dil <= 0)
-    return set_error(ALCM_E_INVALID, "opconv: bad arguments");
-  if (a.Cp <= 0 || a.Cp % 32) return set_error(ALCM_E_INVALID, "opconv: Cp must be a positive multiple of 32");
-  if ((a.ksize - 1) * a.dil > OC_HALO) return set_error(ALCM_E_INVALID, "opconv: receptive field too large");
+// the launch of a CK_OPCONV plan (alcm_convplan.cpp): opconv_kernel's tile ladder
+static int opconv_kernel_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
   const bool strided = a.out_stride > 0;
-  if (strided) {
-    if (a.pad < 0 || a.pad > (a.ksize - 1) * a.dil || a.out_offset < 0 || a.out_offset >= a.out_stride ||
-        (int64_t)(a.T - 1) * a.out_stride + a.out_offset >= a.out_rows || !a.out || a.res || a.accumulate ||
-        a.out_act || a.act_plane || a.geglu_plane)
-      return set_error(ALCM_E_INVALID, "opconv: bad strided-output arguments");
-  } else if (2 * a.pad != (a.ksize - 1) * a.dil) {
-    return set_error(ALCM_E_INVALID, "opconv: only same-length convs");
-  }
-  if (a.kpad < a.ksize * a.Cp || a.kpad % 32) return set_error(ALCM_E_INVALID, "opconv: kpad mismatch");
-  if (a.prec < PREC_BF16 || a.prec > PREC_F16W2) return set_error(ALCM_E_INVALID, "opconv: bad prec");
-  if ((((uintptr_t)a.a) & 15) || (((uintptr_t)a.w) & 15) || (a.a_lo_off % 8) || (a.w_lo_off % 8))
-    return set_error(ALCM_E_INVALID, "opconv: operands must be 16-byte aligned");
-  if (a.C <= 0 || a.C > a.Cp) return set_error(ALCM_E_INVALID, "opconv: C must be in (0, Cp]");
-  if (act) {
-    if (a.out_act || a.N % 2 || !a.act_alpha_exp || !a.act_inv_beta || !a.act_up_filter || !a.act_down_filter)
-      return set_error(ALCM_E_INVALID, "opconv: fused activation needs out_act == 0, even N and its parameters");
-    if (a.out && a.res && a.out == a.res) return set_error(ALCM_E_INVALID, "opconv: fused activation: out aliases res");
-    if ((((uintptr_t)a.act_plane) & 3) || (a.act_plane_lo_off % 2))
-      return set_error(ALCM_E_INVALID, "opconv: act_plane alignment");
-    if ((a.res && (((uintptr_t)a.res) & 15)) || (a.out && (((uintptr_t)a.out) & 15)) || a.N % 4)
-      return set_error(ALCM_E_INVALID, "opconv: fused activation needs 16-byte aligned res/out and N % 4 == 0");
-  }
   OpConvDev P{};
   P.a = (const u16*)a.a; P.a_lo = a.a_lo_off;
-  if (act) {
-    P.act.plane = (u16*)a.act_plane;
-    P.act.plane_lo = a.act_plane_lo_off;
-    P.act.Cp = round_up(a.N, 32);
-    P.act.aexp = a.act_alpha_exp;
-    P.act.ibeta = a.act_inv_beta;
-    for (int k = 0; k < 12; ++k) {
-      P.act.f.up[k] = 2.0f * a.act_up_filter[k];
-      P.act.f.dn[k] = a.act_down_filter[k];
-    }
-  }
+  if (pl.act) P.act = act_epi_of(a);
   P.T = a.T; P.Cp = a.Cp; P.ksize = a.ksize; P.dil = a.dil; P.pad = a.pad;
-  // planes of the packed weight: bf16 hi | bf16 lo | fp16 hi | fp16 lo, w_lo_off apart
-  const bool f16 = a.prec == PREC_F16 || a.prec == PREC_F16W2;
-  P.w = (const u16*)a.w + (f16 ? 2 * a.w_lo_off : 0);
+  P.w = conv_wplane(a);
   P.w_lo = a.w_lo_off; P.kpad = a.kpad; P.N = a.N;
   P.bias = a.bias; P.res = a.res; P.out = a.out; P.out_act = a.out_act; P.accumulate = a.accumulate;
   P.out_scale = a.out_scale;
@@ -652,98 +587,58 @@ int opconv(const alcm_opconv_args& a, hipStream_t s) {
   P.ostride = strided ? a.out_stride : 1;
   P.ooff = strided ? a.out_offset : 0;
   P.orows = strided ? a.out_rows : a.T;
-  const double M = (double)a.B * a.T;
-  const int npa = a.prec == PREC_SPLIT ? 2 : 1, npb = (a.prec == PREC_SPLIT || a.prec == PREC_F16W2) ? 2 : 1;
-  const double flops = 2.0 * M * a.N * (double)a.ksize * a.C;
-  const double bytes = M * a.Cp * 2.0 * npa + (double)a.N * a.kpad * 2.0 * npb +
-                       M * a.N * 4.0 * ((a.out ? 1 : 0) + (a.res ? 1 : 0) + (a.accumulate ? 1 : 0)) +
-                       (act ? M * round_up(a.N, 32) * 2.0 * npa : 0.0);
-  if (a.out_plane) {  // only the wide-layer kernel has the plane-output epilogue
-    if (a.res || a.accumulate || a.out_act || act || a.geglu_plane || strided || a.out ||
-        (a.prec != PREC_F16 && a.prec != PREC_BF16) || (((uintptr_t)a.out_plane) & 7) || !wconv_try(a, P.w, flops, bytes, s))
-      return set_error(ALCM_E_INVALID, "opconv: plane output needs F16/BF16, N % 4 == 0, Cp % 64 == 0, out == NULL "
-                                       "and no res/accumulate/act/GEGLU/strided output");
-    ALCM_HIP(hipGetLastError());
-    return 0;
+  // ACT tiles overlap by 2 * ACT_EPI_HALO rows: each computes BM conv rows and emits BM - 2*HALO
+  P.tstride = pl.act ? pl.BM - 2 * ACT_EPI_HALO : pl.BM;
+  P.tshift = pl.act ? ACT_EPI_HALO : 0;
+  P.tiles_per_batch = pl.tiles_per_batch;
+  void* tok = prof_start(s);
+  const int bm = pl.BM, bn = pl.BN, tps = pl.TPS;  //               BM   BN  WGM WGN TPS
+  if (bm == 128 && bn == 192) launch_opconv<128, 192, 2, 2, 1>(pl, P, a.prec, s);
+  else if (bm == 128 && bn == 128) launch_opconv<128, 128, 2, 2, 1>(pl, P, a.prec, s);
+  else if (bm == 128 && bn == 96) launch_opconv<128, 96, 2, 2, 1>(pl, P, a.prec, s);
+  else if (bm == 256 && bn == 96 && tps == 1) launch_opconv<256, 96, 4, 1, 1>(pl, P, a.prec, s);
+  else if (bm == 256 && bn == 96) launch_opconv<256, 96, 4, 1, 2>(pl, P, a.prec, s);
+  else if (bm == 256 && bn == 48) launch_opconv<256, 48, 4, 1, 1>(pl, P, a.prec, s);
+  else if (bm == 512 && bn == 48 && tps == 1) launch_opconv<512, 48, 4, 1, 1>(pl, P, a.prec, s);
+  else if (bm == 512 && bn == 48) launch_opconv<512, 48, 4, 1, 2>(pl, P, a.prec, s);
+  else if (bm == 256 && bn == 32) launch_opconv<256, 32, 4, 1, 1>(pl, P, a.prec, s);
+  else if (bm == 512 && bn == 32 && tps == 1) launch_opconv<512, 32, 4, 1, 1>(pl, P, a.prec, s);
+  else if (bm == 512 && bn == 32) launch_opconv<512, 32, 4, 1, 2>(pl, P, a.prec, s);
+  else launch_opconv<256, 16, 4, 1, 1>(pl, P, a.prec, s);
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
+  return 0;
+}
+
+static int conv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
+  switch (pl.kernel) {
+    case CK_LIN_PLANE: ALCM_TRY(lin_plane_launch(pl, a, s)); break;
+    case CK_WCONV3:
+    case CK_WCONV2: ALCM_TRY(wconv_launch(pl, a, s)); break;
+    case CK_NCONV: ALCM_TRY(nconv_launch(pl, a, s)); break;
+    default: ALCM_TRY(opconv_kernel_launch(pl, a, s)); break;
   }
-  if (a.geglu_plane) {  // only the wide-layer kernel has the GEGLU epilogue
-    if (!wconv_try(a, P.w, flops, bytes, s))
-      return set_error(ALCM_E_INVALID, "opconv: GEGLU plane epilogue needs F16/BF16, N % 128 == 0, Cp % 64 == 0, "
-                                       "no res/accumulate/act, 4-byte aligned plane");
-    ALCM_HIP(hipGetLastError());
-    return 0;
-  }
-  if (strided) {  // the two-workgroup wide-layer kernel, or opconv_kernel's LDS-staged epilogue (N <= 96)
-    if (wconv_try(a, P.w, flops, bytes, s)) {
-      ALCM_HIP(hipGetLastError());
-      return 0;
-    }
-    if (a.N % 4 || a.N > 96)
-      return set_error(ALCM_E_INVALID, "opconv: strided output needs the wide-layer kernel (F16/BF16, N % 192 == 0, "
-                                       "Cp % 64 == 0, (k-1)*dil <= 64) or N <= 96 with N % 4 == 0");
-  } else if ((!act && wconv_try(a, P.w, flops, bytes, s)) ||
-      nconv_try(a, P.w, act ? &P.act : nullptr, flops, bytes, s)) {
-    ALCM_HIP(hipGetLastError());
-    return 0;
-  }
-  const int N = a.N;
-  // one tap per K step (two taps per step measured slower: the larger weight buffers cost occupancy)
-  //                                                      BM   BN  WGM WGN TPS
-  // small problems whose 128 x 128 tiles would leave CUs idle (the text encoders' N = 1024 projections at
-  // M = 2464: 160 tiles for 256 CUs) take the 96-column tiles (220 tiles): text encode 13.5 -> 13.2 ms per B = 32
-  // (profiles/r3v); ALCM_OPCONV_TILE=-1 keeps the 128 x 128 tiles (A/B)
-  const int64_t tiles128 = (int64_t)a.B * ((a.T + 127) / 128) * ((N + 127) / 128);
-  const bool underfill = !act && N % 128 == 0 && N > 96 && tiles128 < 256 && knobs().opconv_tile != -1;
-  int rc;
-  if (act && N > 96) rc = set_error(ALCM_E_INVALID, "opconv: fused activation on N > 96 needs the wide kernel");
-  else if (N % 192 == 0 && N % 128 != 0) rc = launch_opconv<128, 192, 2, 2, 1>(P, a.B, a.prec, act, flops, bytes, s);
-  else if (N % 128 == 0 && !underfill) rc = launch_opconv<128, 128, 2, 2, 1>(P, a.B, a.prec, act, flops, bytes, s);
-  else if (N > 48) {
-    const int v = tile_variant(a.prec);
-    if (v == 1) rc = launch_opconv<256, 96, 4, 1, 1>(P, a.B, a.prec, act, flops, bytes, s);
-    else if (v == 2) rc = launch_opconv<256, 96, 4, 1, 2>(P, a.B, a.prec, act, flops, bytes, s);
-    else rc = launch_opconv<128, 96, 2, 2, 1>(P, a.B, a.prec, act, flops, bytes, s);
-  } else if (N > 32) {
-    const int v = tile_variant(a.prec);
-    if (v == 1) rc = launch_opconv<512, 48, 4, 1, 1>(P, a.B, a.prec, act, flops, bytes, s);
-    else if (v == 2) rc = launch_opconv<512, 48, 4, 1, 2>(P, a.B, a.prec, act, flops, bytes, s);
-    else rc = launch_opconv<256, 48, 4, 1, 1>(P, a.B, a.prec, act, flops, bytes, s);
-  } else if (N > 16) {
-    const int v = tile_variant(a.prec);
-    if (v == 1) rc = launch_opconv<512, 32, 4, 1, 1>(P, a.B, a.prec, act, flops, bytes, s);
-    else if (v == 2) rc = launch_opconv<512, 32, 4, 1, 2>(P, a.B, a.prec, act, flops, bytes, s);
-    else rc = launch_opconv<256, 32, 4, 1, 1>(P, a.B, a.prec, act, flops, bytes, s);
-  }
-  else rc = launch_opconv<256, 16, 4, 1, 1>(P, a.B, a.prec, act, flops, bytes, s);
-  if (rc) return rc;
   ALCM_HIP(hipGetLastError());
   return 0;
+}
+
+int opconv(const alcm_opconv_args& a, hipStream_t s) {
+  ConvPlan pl;
+  if (conv_plan(a, device_cus(), knobs(), &pl)) return set_error(ALCM_E_INVALID, pl.err);
+  return conv_launch(pl, a, s);
 }
 
 // out = (sum over i < n of conv_i + bias_i + res_i) * args[0].out_scale (+ out if args[0].accumulate): the fused
 // sum-form launch where it applies (three wide terms), else the terms in order, each accumulating into out
 int opconv_sum(const alcm_opconv_args* a, int n, hipStream_t s) {
-  if (!a || n < 1 || n > 3) return set_error(ALCM_E_INVALID, "opconv_sum: 1 <= n <= 3 terms");
-  if (!a[0].out && !a[0].out_plane) return set_error(ALCM_E_INVALID, "opconv_sum: args[0].out is required");
-  if (a[0].out_plane && !wconv3_sum_ok(a, n))
-    return set_error(ALCM_E_INVALID, "opconv_sum: a plane output needs the one-launch form (three F16 / BF16 terms, "
-                                     "dilation 1, Cp % 64 == 0, N % 192 == 0, full 256-row tiles) and no accumulate");
-  for (int i = 0; i < n; ++i)
-    if (a[i].B != a[0].B || a[i].T != a[0].T || a[i].N != a[0].N || a[i].act_plane || (i > 0 && a[i].out_plane) ||
-        a[i].geglu_plane || a[i].out_stride > 0 || a[i].out_act || (a[i].out && a[i].out != a[0].out))
-      return set_error(ALCM_E_INVALID, "opconv_sum: terms need equal B, T, N, same-length fp32 outputs into "
-                                       "args[0].out, no activation / plane / GEGLU / strided output");
-  if (wconv3_sum_try(a, n, s)) {
+  ConvPlan pl[3];
+  int launches = 0;
+  if (conv_sum_plan(a, n, device_cus(), knobs(), pl, &launches)) return set_error(ALCM_E_INVALID, pl[0].err);
+  if (pl[0].kernel == CK_WCONV3_SUM) {
+    ALCM_TRY(wconv3_sum_launch(pl[0], a, n, s));
     ALCM_HIP(hipGetLastError());
     return 0;
   }
-  for (int i = 0; i < n; ++i) {
-    alcm_opconv_args g = a[i];
-    g.out = a[0].out;
-    g.out_scale = a[0].out_scale;
-    g.accumulate = i > 0 ? 1 : a[0].accumulate;
-    ALCM_TRY(opconv(g, s));
-  }
+  for (int i = 0; i < launches; ++i) ALCM_TRY(conv_launch(pl[i], conv_sum_term(a, i), s));
   return 0;
 }
 
@@ -770,4 +665,32 @@ extern "C" int alcm_activation1d_op_f16in(const void* x16, void* y, int B, int T
 extern "C" int alcm_opconv(const alcm_opconv_args* args, alcm_stream_t stream) {
   if (!args) return alcm::set_error(ALCM_E_INVALID, "null args");
   return alcm::opconv(*args, (hipStream_t)stream);
+}
+
+extern "C" int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int as_sum, int ncu, alcm_conv_plan_info* out,
+                                    int* launches) {
+  if (!args || !out || !launches || n < 1 || (!as_sum && n != 1))
+    return alcm::set_error(ALCM_E_INVALID, "debug_conv_plan: bad arguments");
+  alcm::ConvPlan pl[3];
+  if (ncu <= 0) ncu = alcm::device_cus();
+  *launches = 0;
+  const int rc = as_sum ? alcm::conv_sum_plan(args, n, ncu, alcm::knobs(), pl, launches)
+                        : alcm::conv_plan(args[0], ncu, alcm::knobs(), &pl[0]);
+  if (rc) return alcm::set_error(rc, pl[0].err);
+  if (!as_sum) *launches = 1;
+  for (int i = 0; i < *launches; ++i) {
+    alcm_conv_plan_info& o = out[i];
+    std::snprintf(o.name, sizeof(o.name), "%s", pl[i].name);
+    o.kernel = pl[i].kernel;
+    o.bm = pl[i].BM; o.bn = pl[i].BN;
+    o.grid = pl[i].grid;
+    o.ksplit = pl[i].ksplit;
+    o.n_major = pl[i].n_major;
+    o.ncu = ncu;
+  }
+  return 0;
+}
+
+extern "C" int alcm_debug_ksplit_parts(int64_t tiles, int64_t slots, int chunks, double elems, double ws_floats) {
+  return alcm::ksplit_parts(tiles, slots, chunks, elems, ws_floats);
 }

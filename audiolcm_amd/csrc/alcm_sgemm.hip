@@ -39,7 +39,6 @@ struct SGemmDev {
   u16* oplane;       // single-plane kernel: acc + bias as a PREC operand plane [M][ldo] instead of out
 };
 
-constexpr int SG_BM = 128, SG_BN = 192;
 
 __device__ __forceinline__ void sg_glds16(const void* src, char* lds) {
   __builtin_amdgcn_global_load_lds((gbl_void_t*)src, (lds_void_t*)lds, 16, 0, 0);
@@ -267,64 +266,34 @@ int split_planes(const float* x, int64_t rows, int C, int T, const float* scale,
 
 bool sgemm_planes_ok(int K, int N, int kpad) { return K % 32 == 0 && N % SG_BN == 0 && kpad >= K; }
 
-// 1x1 conv / linear on one operand plane (ALCM_LIN1: 1 = 32-deep stages in a 4-deep ring, 2 = 64-deep stages double-
-// buffered, 0 = off: wconv2, -1 = by shape: the 64-deep build for plane outputs only).  Measured per step at B = 32
-// (gpurun_out/r4ag): DiT q,k,v (N = 1728, plane output) 1.04 ms on wconv2 -> 0.84 (ring) / 0.75 (64-deep); DiT
-// to_out (N = 576, fp32 output + residual, one round of 351 tiles, bound by its epilogue) 0.55 -> 0.62 / 0.60.
-// Eligible: f16 / bf16, k = 1 without padding, Cp % 32 == 0, N % 192 == 0, no GEGLU / strided / activated /
-// accumulated output.  Returns 1 when it launched.
-int lin_plane_try(const alcm_opconv_args& a, const u16* wplane, double flops, double bytes, hipStream_t s) {
-  int v = knobs().lin1;
-  if (v < 0) {
-    if (!a.out_plane) return 0;
-    v = 2;
-  }
-  if (v == 0 || (a.prec != PREC_F16 && a.prec != PREC_BF16)) return 0;
-  if (a.ksize != 1 || a.pad != 0 || a.out_stride > 0 || a.geglu_plane || a.out_act || a.accumulate || a.Cp % 32 ||
-      a.N % SG_BN || a.kpad < a.Cp || a.kpad % 8)
-    return 0;
-  if (a.out_plane ? (a.out || a.res) : !a.out) return 0;
-  auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  if (!al16(a.a) || !al16(wplane) || !al16(a.bias) || !al16(a.res) || !al16(a.out) || (((uintptr_t)a.out_plane) & 7))
-    return 0;
-  const int64_t M = (int64_t)a.B * a.T;
-  const int64_t nwg = (M + SG_BM - 1) / SG_BM * (a.N / SG_BN);
-  if (M >= (1ll << 31) || nwg >= (1ll << 30) || M * a.N >= (1ll << 40)) return 0;
+// 1x1 conv / linear on one operand plane: the launch of a CK_LIN_PLANE plan (alcm_convplan.cpp)
+int lin_plane_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
   SGemmDev P{};
-  P.a = (const u16*)a.a; P.w = wplane;
-  P.M = (int)M; P.N = a.N; P.K = a.Cp; P.kpad = a.kpad;
+  P.a = (const u16*)a.a; P.w = conv_wplane(a);
+  P.M = a.B * a.T; P.N = a.N; P.K = a.Cp; P.kpad = a.kpad;
   P.bias = a.bias; P.res = a.res; P.ldr = a.N; P.out = a.out; P.ldo = a.N; P.out_scale = a.out_scale;
   P.oplane = (u16*)a.out_plane;
-  P.tiles_n = a.N / SG_BN;
-  P.nwg = (int)nwg;
+  P.tiles_n = pl.tiles_n;
+  P.nwg = (int)pl.grid;
   void* tok = prof_start(s);
   const bool f16 = a.prec == PREC_F16;
-  const bool deep = v == 2 && a.Cp % 64 == 0;
-  if (deep) {
-    if (f16) hipLaunchKernelGGL((lin_plane_kernel<64, 2, PREC_F16>), dim3((unsigned)nwg), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((lin_plane_kernel<64, 2, PREC_BF16>), dim3((unsigned)nwg), dim3(256), 0, s, P);
+  const dim3 grid((unsigned)pl.grid), blk(256);
+  if (pl.kdeep == 64) {
+    if (f16) hipLaunchKernelGGL((lin_plane_kernel<64, 2, PREC_F16>), grid, blk, 0, s, P);
+    else hipLaunchKernelGGL((lin_plane_kernel<64, 2, PREC_BF16>), grid, blk, 0, s, P);
   } else {
-    if (f16) hipLaunchKernelGGL((lin_plane_kernel<32, 4, PREC_F16>), dim3((unsigned)nwg), dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((lin_plane_kernel<32, 4, PREC_BF16>), dim3((unsigned)nwg), dim3(256), 0, s, P);
+    if (f16) hipLaunchKernelGGL((lin_plane_kernel<32, 4, PREC_F16>), grid, blk, 0, s, P);
+    else hipLaunchKernelGGL((lin_plane_kernel<32, 4, PREC_BF16>), grid, blk, 0, s, P);
   }
-  if (tok) {
-    char name[96];
-    std::snprintf(name, sizeof(name), "alcm::lin_plane_kernel<%d, %d, %d>", deep ? 64 : 32, deep ? 2 : 4, a.prec);
-    if (knobs().prof_shapes)
-      std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " M%d N%d K%d", P.M, a.N, a.Cp);
-    prof_stop(tok, s, name, flops, bytes);
-  }
-  ALCM_HIP(hipGetLastError());
-  return 1;
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
+  return 0;
 }
-
 
 int sgemm_planes(const u16* a, int64_t a_lo, int M, int K, const u16* w, int64_t w_lo, int kpad, int N,
                  const float* bias, const float* res, int64_t ldr, float* out, int64_t ldo, float out_scale,
                  hipStream_t s) {
   if (!a || !w || !out || M <= 0 || !sgemm_planes_ok(K, N, kpad))
     return set_error(ALCM_E_INVALID, "sgemm_planes: needs K % 32 == 0, N % 192 == 0");
-  auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   if (!al16(a) || !al16(w) || (a_lo % 8) || (w_lo % 8) || (kpad % 8) || !al16(out) || ldo % 4 ||
       (res && (!al16(res) || ldr % 4)) || (bias && !al16(bias)))
     return set_error(ALCM_E_INVALID, "sgemm_planes: alignment");

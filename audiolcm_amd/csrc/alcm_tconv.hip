@@ -715,11 +715,7 @@ int tconv(const alcm_opconv_args& a, const u16* wd, int64_t wd_lo, int kd, const
     // box: k11 0.547 -> 0.491 ms, k3 0.300 -> 0.301, conv2 + residual 0.732 -> 0.695); C = 24 one workgroup per tile
     // (persistent measured +5..+17 %)
     int grid2 = (int)nt;
-    if (C == 96) {
-      int dev = 0, ncu = 256;
-      if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-      grid2 = (int)std::min<int64_t>(nt, (int64_t)ncu * 2);
-    }
+    if (C == 96) grid2 = (int)std::min<int64_t>(nt, (int64_t)device_cus() * 2);
     if (C == 96) rc = tc2_mode<96, 96, 1, 192, 11, 2, 2>(P, diag, grid2, act, a.res, outw, acc_mode, s);
     else if (C == 48) {
       if (npb == 2) rc = tc2_mode<48, 48, 2, 256, 24>(P, diag, grid2, act, a.res, outw, acc_mode, s);
@@ -735,10 +731,8 @@ int tconv(const alcm_opconv_args& a, const u16* wd, int64_t wd_lo, int kd, const
   } else {
     // persistent: a multiple of ncg workgroups so a workgroup's column group (blockIdx % ncg) is the same for every
     // tile it takes (tile % ncg == blockIdx % ncg); C = 24 fits two per CU
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     const int wgs = half48 ? occ48 : (C == 24 ? 2 : 1);
-    int grid = std::min<int64_t>(nt, (int64_t)ncu * wgs);
+    int grid = std::min<int64_t>(nt, (int64_t)device_cus() * wgs);
     grid = std::max(P.ncg, grid / P.ncg * P.ncg);
     if (C == 96) rc = tc_mode<96, 48, 1, 192, 11>(P, diag, grid, act, a.res, outw, acc_mode, s);
     else if (half48) {

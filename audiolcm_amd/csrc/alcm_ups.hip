@@ -212,15 +212,7 @@ int ups2(const float* x, float* out, int B, int T, int cin, int cout, const u16*
   const int64_t nt = (int64_t)B * P.tiles_per_batch;
   if (nt >= (1ll << 30)) return set_error(ALCM_E_INVALID, "ups2: problem too large");
   P.ntiles = (int)nt;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0, n = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-              ? n
-              : 256;
-  }
-  const int grid = (int)std::min<int64_t>(nt, (int64_t)ncu * (cin == 96 ? UpsGeo<96, 48>::OCC : UpsGeo<48, 32>::OCC));
+  const int grid = (int)std::min<int64_t>(nt, (int64_t)device_cus() * (cin == 96 ? UpsGeo<96, 48>::OCC : UpsGeo<48, 32>::OCC));
   void* tok = prof_start(s);
   if (cin == 96) hipLaunchKernelGGL((ups2_kernel<96, 48, 96>), dim3(grid), dim3(512), 0, s, P);
   else hipLaunchKernelGGL((ups2_kernel<48, 32, 48>), dim3(grid), dim3(512), 0, s, P);

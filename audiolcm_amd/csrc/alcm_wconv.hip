@@ -73,8 +73,6 @@ __device__ __forceinline__ void glds16(const void* src, char* lds_base) {
 // co-resident workgroups of a CU fetch ~32 B/cycle at full MFMA rate on the k = 7 / 11 / 9 shapes, the per-CU
 // L2 -> LDS rate measured in MI355X_MICROARCH.md ("Indexed rows"), which is what the DMA ablation shows; 256 x 96
 // halves the weight bytes (and doubles the window bytes, amortised over k taps).
-constexpr int W2_HALO = 64;  // max (k - 1) * dil
-
 // BM = 160 (waves 2 x 2 of 80 x 96, TM = 5): sequences of T = 312 rows as two tiles (320 rows) instead of three of 128
 // (384 rows, 768 tiles on the 512 workgroup slots of the chip: the VAE's k3 convs)
 template <int PREC, bool GEGLU, int BM = 128, int BN = 192>
@@ -361,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void wconv2_kernel(const WConvDev P) {
 //     where the two-workgroup 256 x 96 / 128 x 192 tiles need 20-41.
 // Persistent order: XCD x owns the tile range [x R, (x+1) R) (R = ceil(tiles / 8)), its workgroups take every
 // (grid / 8)-th tile of it, N-major (concurrent tiles share a weight slice in the XCD's L2) or M-major.
-constexpr int W3_BM = 256, W3_BN = 192, W3_WROWS = 320;
+constexpr int W3_WROWS = 320;  // (W3_BM x W3_BN tiles: alcm_convplan.h)
 constexpr int W3_WBUF = W3_WROWS * 128;  // 40 KB
 constexpr int W3_BBUF = W3_BN * 128;     // 24 KB
 constexpr int W3_WPW = W3_WROWS / 8 / 8;  // window DMA instructions per wave (5)
@@ -798,8 +796,6 @@ __global__ __launch_bounds__(512, 1) void wconv3_kernel(const WConvDev P) {
   }
 }
 
-static int g_ncu = 0;
-
 // K-split reduction of wconv3's partial slices: out = (sum over parts, in part order, + bias + res) * scale (+ out) —
 // the unsplit epilogue's expression with its accumulator replaced by the ordered part sum, so a launch is
 // deterministic (bit-stable run to run); float4 per lane over the B T N / 4 outputs (N % 4 == 0)
@@ -827,329 +823,99 @@ __global__ __launch_bounds__(256) void ksplit_reduce_kernel(const float4* __rest
 // the reduction launch of a K-split conv (same stream, right after the parts)
 static void ksplit_reduce(const alcm_opconv_args& a, int ks, hipStream_t s) {
   const int64_t n4 = (int64_t)a.B * a.T * a.N / 4;
-  const unsigned rg = (unsigned)std::min<int64_t>((n4 + 255) / 256, (int64_t)g_ncu * 8);
+  const unsigned rg = (unsigned)std::min<int64_t>((n4 + 255) / 256, (int64_t)device_cus() * 8);
   hipLaunchKernelGGL(ksplit_reduce_kernel, dim3(rg), dim3(256), 0, s, reinterpret_cast<const float4*>(a.ksplit_ws), ks,
                      n4, a.N / 4, reinterpret_cast<const float4*>(a.bias), reinterpret_cast<const float4*>(a.res),
                      reinterpret_cast<float4*>(a.out), a.out_scale, a.accumulate);
 }
 
-// K parts for wconv3 on a grid that does not fill the chip (items = tiles x parts): the smallest part count that
-// minimises rounds-of-items per part (e.g. the DiT FFN down-projection: 192 tiles of 256 x 192 on 256 CUs, 0.75 busy;
-// 4 parts = 768 items = 3 per CU, 0.75 of the time plus the reduction), within the caller's partial workspace; 1 =
-// no split
-static int wconv3_parts(const alcm_opconv_args& a, int64_t tiles, int ncu) {
-  if (!a.ksplit_ws || knobs().ksplit == 0 || a.out_plane || a.Cp % 64) return 1;
-  const int nc = a.Cp / 64;
-  int ks = 1;
-  double best = (double)((tiles + ncu - 1) / ncu);
-  for (int k = 2; k <= 8; ++k) {
-    if (nc % k || nc / k < 4 || (double)k * a.B * a.T * a.N > (double)a.ksplit_ws_floats) continue;
-    const double t = (double)((tiles * k + ncu - 1) / ncu) / k;
-    if (t < best * 0.95) {
-      best = t;
-      ks = k;
-    }
-  }
-  return ks;
-}
-
-// Eligible: fp16 / bf16 operands, Cp % 64 == 0, 3 <= k, (k-1) d <= 64, N % 192 == 0, plain fp32 epilogue (bias,
-// residual, scale, accumulate; no GEGLU / strided output).  Returns 1 when it launched.
-static int wconv3_try(const alcm_opconv_args& a, const u16* wplane, double flops, double bytes, hipStream_t s,
-                      int ks = 1) {
-  if (a.prec != PREC_F16 && a.prec != PREC_BF16) return 0;
-  if (a.out_act || a.out_stride > 0 || a.geglu_plane || a.Cp % 64 || a.ksize < 3 || (a.ksize - 1) * a.dil > 64 ||
-      a.N % W3_BN)
-    return 0;
-  if (a.out_plane ? (a.out || a.res || a.accumulate || (((uintptr_t)a.out_plane) & 3)) : !a.out) return 0;
-  if (!g_ncu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) ==
-                                                hipSuccess && n >= 8)
-      g_ncu = n;
-    else
-      g_ncu = 256;
-  }
+// what the plan fixes for both wide kernels
+static WConvDev wconv_dev(const ConvPlan& pl, const alcm_opconv_args& a) {
   WConvDev P{};
   P.a = (const u16*)a.a;
   P.T = a.T; P.Cp = a.Cp; P.ksize = a.ksize; P.dil = a.dil; P.pad = a.pad;
-  P.w = wplane; P.kpad = a.kpad; P.N = a.N;
+  P.w = conv_wplane(a); P.kpad = a.kpad; P.N = a.N;
   P.bias = a.bias; P.res = a.res; P.out = a.out; P.out_scale = a.out_scale; P.accumulate = a.accumulate;
   P.oplane = (u16*)a.out_plane;
-  P.tiles_per_batch = (P.T + W3_BM - 1) / W3_BM;
-  P.tiles_n = a.N / W3_BN;
-  const int64_t nt = (int64_t)a.B * P.tiles_per_batch * P.tiles_n;
-  if (nt >= (1ll << 30) || (int64_t)a.B * a.T * a.Cp >= (1ll << 40) || (int64_t)a.B * a.T * a.N >= (1ll << 40)) return 0;
-  if ((int64_t)W3_BN * a.kpad * 2 >= (1ll << 31)) return 0;  // per-lane 32-bit weight-row byte offsets
-  P.nwg = (int)nt;
-  P.n_major = 1;
-  if (ks > 1) {
-    if (a.out_plane || (a.Cp / 64) % ks || (int64_t)a.N % 4 || (((uintptr_t)a.ksplit_ws) & 15) ||
-        (a.bias && (((uintptr_t)a.bias) & 15)) || (a.res && (((uintptr_t)a.res) & 15)) || (((uintptr_t)a.out) & 15))
-      return 0;
-    P.ksplit = ks;
+  P.tiles_per_batch = pl.tiles_per_batch;
+  P.tiles_n = pl.tiles_n;
+  P.nwg = (int)pl.tiles;
+  P.n_major = pl.n_major;
+  if (pl.ksplit > 1) {
+    P.ksplit = pl.ksplit;
     P.part = a.ksplit_ws;
   }
-  const int R = (int)((nt * ks + 7) / 8);
-  int grid = 8 * std::min(g_ncu / 8, R);
-  if (knobs().wconv3_grid >= 8) grid = std::min(grid, knobs().wconv3_grid / 8 * 8);  // tests: several tiles per workgroup
+  return P;
+}
+
+// the launch of a CK_WCONV3 or CK_WCONV2 plan (alcm_convplan.cpp), with its K-split reduction
+int wconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
+  WConvDev P = wconv_dev(pl, a);
+  const int ks = pl.ksplit;
   void* tok = prof_start(s);
-  if (a.prec == PREC_F16) {
-    if (ks > 1) hipLaunchKernelGGL((wconv3_kernel<PREC_F16, 1, true>), dim3(grid), dim3(512), 0, s, P);
-    else hipLaunchKernelGGL((wconv3_kernel<PREC_F16, 1, false>), dim3(grid), dim3(512), 0, s, P);
+  if (pl.kernel == CK_WCONV3) {
+    const dim3 grid((unsigned)pl.grid), blk(512);
+    if (a.prec == PREC_F16) {
+      if (ks > 1) hipLaunchKernelGGL((wconv3_kernel<PREC_F16, 1, true>), grid, blk, 0, s, P);
+      else hipLaunchKernelGGL((wconv3_kernel<PREC_F16, 1, false>), grid, blk, 0, s, P);
+    } else {
+      if (ks > 1) hipLaunchKernelGGL((wconv3_kernel<PREC_BF16, 1, true>), grid, blk, 0, s, P);
+      else hipLaunchKernelGGL((wconv3_kernel<PREC_BF16, 1, false>), grid, blk, 0, s, P);
+    }
   } else {
-    if (ks > 1) hipLaunchKernelGGL((wconv3_kernel<PREC_BF16, 1, true>), dim3(grid), dim3(512), 0, s, P);
-    else hipLaunchKernelGGL((wconv3_kernel<PREC_BF16, 1, false>), dim3(grid), dim3(512), 0, s, P);
+    const bool strided = a.out_stride > 0;
+    P.gplane = (u16*)a.geglu_plane;
+    P.out_act = a.out_act;
+    P.ostride = strided ? a.out_stride : 1;
+    P.ooff = strided ? a.out_offset : 0;
+    P.orows = strided ? a.out_rows : a.T;
+    const dim3 grid((unsigned)pl.grid), blk(256);
+    auto go = [&](auto bm_c) {
+      constexpr int BM = decltype(bm_c)::value, BN = BM == 256 ? 96 : 192;
+      if (a.prec == PREC_F16) {
+        if (pl.geglu) hipLaunchKernelGGL((wconv2_kernel<PREC_F16, true, BM, BN>), grid, blk, 0, s, P);
+        else hipLaunchKernelGGL((wconv2_kernel<PREC_F16, false, BM, BN>), grid, blk, 0, s, P);
+      } else {
+        if (pl.geglu) hipLaunchKernelGGL((wconv2_kernel<PREC_BF16, true, BM, BN>), grid, blk, 0, s, P);
+        else hipLaunchKernelGGL((wconv2_kernel<PREC_BF16, false, BM, BN>), grid, blk, 0, s, P);
+      }
+    };
+    if (pl.BM == 256) {
+      go(std::integral_constant<int, 256>{});
+    } else if (pl.BM == 160) {
+      go(std::integral_constant<int, 160>{});
+    } else {
+      go(std::integral_constant<int, 128>{});
+    }
   }
   if (ks > 1) ksplit_reduce(a, ks, s);
-  if (tok) {
-    char name[96];
-    // (the rocprofv3 names of the instantiations, so bench.py finds their PMC traffic in profiles/*/kernels.json)
-    std::snprintf(name, sizeof(name),
-                  ks > 1 ? "alcm::wconv3_kernel<%d, 1, true> + ksplit_reduce" : "alcm::wconv3_kernel<%d, 1, false>",
-                  a.prec);
-    if (knobs().prof_shapes)
-      std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " T%d C%d N%d k%d", a.T, a.Cp, a.N,
-                    a.ksize);
-    prof_stop(tok, s, name, flops, bytes);
-  }
-  return 1;
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
+  return 0;
 }
 
-// Sum form (alcm_opconv_sum): three same-length terms with their own planes, weights, taps, biases and residuals
-// into one output, one pass of the persistent kernel and one epilogue (out = (sum of the terms' conv + bias +
-// residual) * scale (+ out)).  Eligible: the terms' shared B, T, Cp, N and precision (F16 / BF16), dilation 1,
-// 3 <= k <= 65, Cp % 64 == 0, N % 192 == 0, full 256-row tiles filling the chip (as wconv3 by shape).  Returns 1
-// when it launched.
-bool wconv3_sum_ok(const alcm_opconv_args* a, int n) {
-  if (n != 3 || knobs().wconv_sum == 0 || knobs().wconv <= 0 || knobs().wconv3 == 0) return false;
-  const alcm_opconv_args& a0 = a[0];
-  if ((a0.prec != PREC_F16 && a0.prec != PREC_BF16) || a0.Cp % 64 || a0.N % W3_BN) return false;
-  // output: fp32 out, or (no accumulate) the operand plane of the value the fp32 route would store
-  if (a0.out_plane ? (a0.out || a0.accumulate || (((uintptr_t)a0.out_plane) & 3)) : !a0.out) return false;
-  for (int i = 0; i < n; ++i) {
-    const alcm_opconv_args& t = a[i];
-    if (t.B != a0.B || t.T != a0.T || t.Cp != a0.Cp || t.N != a0.N || t.prec != a0.prec || t.dil != 1 ||
-        t.ksize < 3 || t.ksize - 1 > 64 || 2 * t.pad != t.ksize - 1 || t.out_act || t.out_stride > 0 ||
-        t.geglu_plane || (i > 0 && t.out_plane) || t.act_plane || (int64_t)W3_BN * t.kpad * 2 >= (1ll << 31))
-      return false;
-  }
-  if (!g_ncu) {
-    int dev = 0, nc = 0;
-    g_ncu = (hipGetDevice(&dev) == hipSuccess &&
-             hipDeviceGetAttribute(&nc, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && nc >= 8)
-                ? nc
-                : 256;
-  }
-  const int mt256 = (a0.T + W3_BM - 1) / W3_BM;
-  const int64_t nt = (int64_t)a0.B * mt256 * (a0.N / W3_BN);
-  const bool full = a0.T * 100 >= mt256 * W3_BM * 85;
-  if (!(knobs().wconv3 > 0 || (full && nt >= g_ncu))) return false;
-  return nt < (1ll << 30) && (int64_t)a0.B * a0.T * a0.Cp < (1ll << 40) && (int64_t)a0.B * a0.T * a0.N < (1ll << 40);
-}
-
-int wconv3_sum_try(const alcm_opconv_args* a, int n, hipStream_t s) {
-  if (!wconv3_sum_ok(a, n)) return 0;  // (sets g_ncu)
-  const alcm_opconv_args& a0 = a[0];
-  const int mt256 = (a0.T + W3_BM - 1) / W3_BM;
-  const int64_t nt = (int64_t)a0.B * mt256 * (a0.N / W3_BN);
-  WConvDev P{};
-  P.a = (const u16*)a0.a;
-  P.T = a0.T; P.Cp = a0.Cp; P.ksize = a0.ksize; P.dil = 1; P.pad = a0.pad;
-  P.N = a0.N;
-  P.out = a0.out; P.out_scale = a0.out_scale; P.accumulate = a0.accumulate;
-  P.oplane = (u16*)a0.out_plane;
-  P.tiles_per_batch = mt256;
-  P.tiles_n = a0.N / W3_BN;
-  P.nwg = (int)nt;
-  P.n_major = 1;
+// the launch of a CK_WCONV3_SUM plan (alcm_opconv_sum's one-launch form): three same-length terms with their own
+// planes, weights, taps, biases and residuals into one output, one pass of the persistent kernel and one epilogue
+// (out = (sum of the terms' conv + bias + residual) * scale (+ out))
+int wconv3_sum_launch(const ConvPlan& pl, const alcm_opconv_args* a, int n, hipStream_t s) {
+  WConvDev P = wconv_dev(pl, a[0]);
+  P.dil = 1;
+  P.bias = nullptr; P.res = nullptr;
   P.nseg = n;
-  double flops = 0, bytes = (double)a0.B * a0.T * a0.N * (a0.out_plane ? 2.0 : 4.0 * (a0.accumulate ? 2 : 1));
   for (int i = 0; i < n; ++i) {
-    const bool f16 = a[i].prec == PREC_F16;
     P.sa[i] = (const u16*)a[i].a;
-    P.sw[i] = (const u16*)a[i].w + (f16 ? 2 * a[i].w_lo_off : 0);
+    P.sw[i] = conv_wplane(a[i]);
     P.sk[i] = a[i].ksize;
     P.spad[i] = a[i].pad;
     P.skpad[i] = a[i].kpad;
     P.sbias[i] = a[i].bias;
     P.sres[i] = a[i].res;
-    flops += 2.0 * a0.B * a0.T * a0.N * (double)a[i].ksize * a[i].C;
-    bytes += (double)a0.B * a0.T * a0.Cp * 2.0 + (double)a0.N * a[i].kpad * 2.0 +
-             (a[i].res ? (double)a0.B * a0.T * a0.N * 4.0 : 0.0);
   }
-  P.w = P.sw[0]; P.kpad = P.skpad[0];
-  const int R = (int)((nt + 7) / 8);
-  int grid = 8 * std::min(g_ncu / 8, R);
-  if (knobs().wconv3_grid >= 8) grid = std::min(grid, knobs().wconv3_grid / 8 * 8);  // tests: several tiles per workgroup
   void* tok = prof_start(s);
-  if (a0.prec == PREC_F16) hipLaunchKernelGGL((wconv3_kernel<PREC_F16, 3, false>), dim3(grid), dim3(512), 0, s, P);
-  else hipLaunchKernelGGL((wconv3_kernel<PREC_BF16, 3, false>), dim3(grid), dim3(512), 0, s, P);
-  if (tok) {
-    char name[96];
-    std::snprintf(name, sizeof(name), "alcm::wconv3_kernel<%d, 3, false>", a0.prec);
-    if (knobs().prof_shapes)
-      std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " T%d C%d N%d k%d+%d+%d", a0.T, a0.Cp,
-                    a0.N, a[0].ksize, a[1].ksize, a[2].ksize);
-    prof_stop(tok, s, name, flops, bytes);
-  }
-  return 1;
-}
-
-// wconv2 tile by shape: 256 x 96 where the weight stream dominates the per-CU fetch (k >= 7:
-// the window is amortised over >= 7 taps) and there is at least one 256-row tile per CU; 128 x 192 elsewhere.
-// Measured per launch (B = 32, one box): s0 C768 k11 0.946 -> 0.860 ms, s1 C384 k11
-// 0.973 -> 0.934, s2 C192 k11 0.583 -> 0.559, DiT FFN-down 0.377 -> 0.358; k3 shapes equal or slower (VAE k3 +17 %)
-static bool wconv2_tile256(const alcm_opconv_args& a) {
-  const int64_t mt = (int64_t)a.B * ((a.T + 255) / 256);
-  return a.out_stride <= 0 && a.ksize >= 7 && mt * (a.N / 96) >= 256;
-}
-
-// Eligible: single-plane precisions, N a multiple of 192 (128 x 192 tiles) or 96 (256 x 96 tiles), Cp a multiple of
-// 64, (k-1)d <= 64, no output activation.  Returns 1 when it launched, 0 when the caller should use opconv_kernel
-// (ALCM_WCONV=0: always 0 for plain same-length convs, the A/B reference; the strided and GEGLU epilogues exist
-// only here).
-int wconv_try(const alcm_opconv_args& a, const u16* wplane, double flops, double bytes, hipStream_t s) {
-  const bool off = knobs().wconv <= 0;
-  const bool strided = a.out_stride > 0;
-  // persistent 8-wave kernel (ALCM_WCONV3: -1 by shape, 0 off, 1 wherever eligible): by shape where the 256-row
-  // M tiles are >= 85 % full (BigVGAN T = 2496 / 9984 / 19968, DiT L = 467; not the VAE's T = 312, measured +15 %,
-  // nor with the clips laid end to end as padded-flat rows: 2.85 vs 2.61 ms/step on wconv2)
-  // A persistent grid with fewer tiles than CUs leaves CUs idle where the two-workgroup kernel's half-size tiles share
-  // them: the DiT FFN down-projection (192 tiles of 256 x 192) measured 2.98 vs 2.82 ms/step (profiles/r4s)
-  const int w3 = knobs().wconv3;
-  const int mt256 = (a.T + W3_BM - 1) / W3_BM;
-  const bool full = a.T * 100 >= mt256 * W3_BM * 85;
-  if (!g_ncu) {
-    int dev = 0, n = 0;
-    g_ncu = (hipGetDevice(&dev) == hipSuccess &&
-             hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8)
-                ? n
-                : 256;
-  }
-  const int64_t tiles3 = (int64_t)a.B * mt256 * (a.N / W3_BN);
-  const bool fills = tiles3 >= g_ncu;
-  // a grid that does not fill the chip: K parts where the caller gave a partial workspace (ALCM_KSPLIT=0: never)
-  const int ks = (!off && w3 != 0 && full && !fills && !strided && !a.geglu_plane && a.N % W3_BN == 0)
-                     ? wconv3_parts(a, tiles3, g_ncu) : 1;
-  if (!off && (a.out_plane || (int64_t)a.B * a.T >= 1024) && lin_plane_try(a, wplane, flops, bytes, s)) return 1;
-  if (!off && w3 != 0 && !strided && !a.geglu_plane && (w3 > 0 || (full && (fills || ks > 1))) &&
-      wconv3_try(a, wplane, flops, bytes, s, ks))
-    return 1;
-  if (off && !a.geglu_plane && !strided && !a.out_plane) return 0;
-  if (a.prec != PREC_F16 && a.prec != PREC_BF16) return 0;
-  if ((a.out_act && (a.geglu_plane || strided)) || a.Cp % 64 || a.ksize < 1 || (a.ksize - 1) * a.dil > W2_HALO)
-    return 0;
-  // N % 96: whole tiles; else (N % 4, not strided / GEGLU) 128 x 192 tiles with a partial last one (the T5 wi, N = 5632)
-  const bool ragged = a.N % 96 != 0;
-  if (ragged && (a.N % 4 || strided || a.geglu_plane)) return 0;
-  // (only where the padded last tile wastes <= 25 % of the N tiles' columns: the text encoders' T5 wi / o, N = 5632 /
-  // 1024; small ragged N stay on opconv_kernel's narrower tiles)
-  if (ragged && 4 * (round_up(a.N, 192) - a.N) > round_up(a.N, 192)) return 0;
-  if (!a.geglu_plane && !strided && !a.out_plane && (int64_t)a.B * a.T < 1024) return 0;  // small problems: opconv_kernel's
-                                                                                     // 128-row tiles fill the chip better
-  auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  if (!(al16(a.bias) && al16(a.res) && al16(a.out))) return 0;
-  if (a.geglu_plane && (a.res || a.accumulate || (((uintptr_t)a.geglu_plane) & 3))) return 0;
-  // wconv2 tile: 256 x 96 halves the weight bytes every tile fetches (see the kernel comment)
-  const bool t256 = !ragged && wconv2_tile256(a);
-  // 160-row tiles where rounds x tile rows over the two-workgroup slots of the chip drop: the VAE's T = 312 k3 convs at
-  // N = 1536 (768 tiles of 128 rows = 1.5 rounds, 512 of 160 = one; 1.82 -> 1.43 ms/step); N = 768
-  // (384 tiles, one round either way) stays at 128
-  // (strided: the BigVGAN stage 0 / 1 upsampler phases, T = 624 / 2496 at N = 768 / 384: 1.25 / 2.5 rounds of
-  // 128-row tiles -> one / two of 160-row ones; ALCM_UPS_T160=0 keeps them at 128)
-  bool t160 = false;
-  if (!t256 && !a.geglu_plane && (!strided || knobs().ups_t160) && a.N % 192 == 0) {
-    const int64_t slots = 2 * (int64_t)g_ncu, tn = a.N / 192;
-    const int64_t r128 = ((int64_t)a.B * ((a.T + 127) / 128) * tn + slots - 1) / slots;
-    const int64_t r160 = ((int64_t)a.B * ((a.T + 159) / 160) * tn + slots - 1) / slots;
-    t160 = r160 * 160 < r128 * 128;
-  }
-  const int BM2 = t256 ? 256 : (t160 ? 160 : 128), BN2 = t256 ? 96 : 192;
-  // K parts where the grid fills less than one round of the chip's two-workgroup slots (the text towers' out-
-  // projections at 2464 rows: 80-120 tiles for 512 slots; the DiT to_out): plain fp32 epilogues only, the reduction
-  // applies bias / residual / scale / accumulate in part order
-  int ks2 = 1;
-  if (!off && a.ksplit_ws && knobs().ksplit != 0 && !a.geglu_plane && !strided && !a.out_plane && !a.out_act &&
-      a.N % 4 == 0) {
-    const int64_t tiles = (int64_t)a.B * ((a.T + BM2 - 1) / BM2) * ((a.N + BN2 - 1) / BN2);
-    const int64_t slots = 2 * (int64_t)g_ncu;
-    const int nc = a.Cp / 64;
-    double best = (double)((tiles + slots - 1) / slots);
-    for (int k = 2; k <= 8; ++k) {
-      // (>= 4 chunks of 64 channels per part: a part's window staging and its partial-slice epilogue are fixed costs)
-      if (nc % k || nc / k < 4 || (double)k * a.B * a.T * a.N > (double)a.ksplit_ws_floats) continue;
-      const double t = (double)((tiles * k + slots - 1) / slots) / k;
-      if (t < best * 0.95) {
-        best = t;
-        ks2 = k;
-      }
-    }
-    if (ks2 > 1 && ((((uintptr_t)a.ksplit_ws) & 15) || !a.out)) ks2 = 1;
-  }
-  if (a.N % BN2 == 0 || ragged) {
-    WConvDev P{};
-    P.a = (const u16*)a.a;
-    P.T = a.T; P.Cp = a.Cp; P.ksize = a.ksize; P.dil = a.dil; P.pad = a.pad;
-    P.w = wplane; P.kpad = a.kpad; P.N = a.N;
-    P.bias = a.bias; P.res = a.res; P.out = a.out; P.out_scale = a.out_scale; P.accumulate = a.accumulate;
-    P.gplane = (u16*)a.geglu_plane;
-    P.out_act = a.out_act;
-    P.oplane = (u16*)a.out_plane;
-    P.ostride = strided ? a.out_stride : 1;
-    P.ooff = strided ? a.out_offset : 0;
-    P.orows = strided ? a.out_rows : a.T;
-    // N-tile-major order where the weight matrix is long (Cp * k >= 4096) and there are enough M tiles to share
-    // an XCD's weight slice: that XCD's N tiles stay in its L2 (C768 k11 -17 %, DiT FFN -3..-10 %); M-major
-    // elsewhere (the N tiles of an M tile share its input window in L2)
-    const int tiles_m = a.B * ((a.T + BM2 - 1) / BM2);
-    // (the GEGLU up-projection, 64 M tiles x 48 N tiles of 1 MB weight slices: N-major -4 %, its M-major order
-    // re-reads the weights from the Infinity Cache once per M tile, 3 GB counted per launch)
-    P.n_major = (a.Cp * a.ksize >= 4096 && (tiles_m >= 128 || (a.geglu_plane && tiles_m >= 64)));
-    P.tiles_per_batch = (a.T + BM2 - 1) / BM2;
-    P.tiles_n = (a.N + BN2 - 1) / BN2;
-    const int64_t nwg2 = (int64_t)a.B * P.tiles_per_batch * P.tiles_n;
-    if (nwg2 * ks2 >= (1ll << 30) || (int64_t)a.B * a.T * a.Cp >= (1ll << 40)) return 0;
-    P.nwg = (int)nwg2;
-    if (ks2 > 1) {
-      P.ksplit = ks2;
-      P.part = a.ksplit_ws;
-    }
-    void* tok = prof_start(s);
-    const dim3 grid((unsigned)(nwg2 * ks2)), blk(256);
-    const bool gl = a.geglu_plane != nullptr;
-    auto go = [&](auto bm_c) {
-      constexpr int BM = decltype(bm_c)::value, BN = BM == 256 ? 96 : 192;
-      if (a.prec == PREC_F16) {
-        if (gl) hipLaunchKernelGGL((wconv2_kernel<PREC_F16, true, BM, BN>), grid, blk, 0, s, P);
-        else hipLaunchKernelGGL((wconv2_kernel<PREC_F16, false, BM, BN>), grid, blk, 0, s, P);
-      } else {
-        if (gl) hipLaunchKernelGGL((wconv2_kernel<PREC_BF16, true, BM, BN>), grid, blk, 0, s, P);
-        else hipLaunchKernelGGL((wconv2_kernel<PREC_BF16, false, BM, BN>), grid, blk, 0, s, P);
-      }
-    };
-    if (t256) {
-      go(std::integral_constant<int, 256>{});
-    } else if (t160) {
-      go(std::integral_constant<int, 160>{});
-    } else {
-      go(std::integral_constant<int, 128>{});
-    }
-    if (ks2 > 1) ksplit_reduce(a, ks2, s);
-    if (tok) {
-      char name[112];
-      // the demangled rocprofv3 name (template defaults included), so bench.py can join the PMC passes by name
-      std::snprintf(name, sizeof(name), ks2 > 1 ? "alcm::wconv2_kernel<%d, %s, %d, %d> + ksplit_reduce"
-                                                : "alcm::wconv2_kernel<%d, %s, %d, %d>", a.prec, gl ? "true" : "false",
-                    BM2, BN2);
-      if (knobs().prof_shapes)
-        std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " T%d C%d N%d k%d", a.T, a.Cp,
-                      a.N, a.ksize);
-      prof_stop(tok, s, name, flops, bytes);
-    }
-    return 1;
-  }
-  return 0;  // opconv_kernel
+  const dim3 grid((unsigned)pl.grid), blk(512);
+  if (a[0].prec == PREC_F16) hipLaunchKernelGGL((wconv3_kernel<PREC_F16, 3, false>), grid, blk, 0, s, P);
+  else hipLaunchKernelGGL((wconv3_kernel<PREC_BF16, 3, false>), grid, blk, 0, s, P);
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
+  return 0;
 }
 
 }  // namespace alcm

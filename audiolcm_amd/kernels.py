@@ -381,6 +381,16 @@ def activation1d_op_f16in(x16: torch.Tensor, alpha: torch.Tensor, beta: torch.Te
     return y
 
 
+def conv_plan(args, ncu: int = 0) -> list:
+    """Which kernel(s) an operand-plane conv call would launch: args is one _hip.OpConvArgs (alcm_opconv) or a
+    sequence of up to three (alcm_opconv_sum).  -> one dict per launch (name = its profile row, kernel, bm, bn, grid,
+    ksplit, n_major, ncu); needs no GPU when ncu is given."""
+    if isinstance(args, _hip.OpConvArgs):
+        return _hip.debug_conv_plan(args, 1, False, ncu)
+    arr = (_hip.OpConvArgs * len(args))(*args)
+    return _hip.debug_conv_plan(arr, len(args), True, ncu)
+
+
 def opconv_sum(terms, prec: int, out_scale: float = 1.0, accumulate_into: Optional[torch.Tensor] = None,
                out_plane: bool = False):
     """alcm_opconv_sum: out (B, T, N) = (sum over terms of conv_k(planes) + bias + residual) * out_scale (+ out) — the

@@ -232,7 +232,8 @@ int alcm_opconv(const alcm_opconv_args* args, alcm_stream_t stream);
  *   T and N, and only args[0]'s out / out_scale / accumulate are read (another term's out must be NULL or the same).
  *   Three F16 / BF16 terms of dilation 1 with Cp % 64 == 0 and N % 192 == 0 run as one launch summing all taps in one
  *   fp32 accumulator; otherwise the terms run in order, each accumulating into out (the same value up to fp32
- *   rounding order).  No activation / plane / GEGLU / strided outputs. */
+ *   rounding order).  No activation / plane / GEGLU / strided outputs.  Every term passes alcm_opconv's operand
+ *   checks before anything is launched, in either form (ALCM_E_INVALID otherwise). */
 int alcm_opconv_sum(const alcm_opconv_args* args, int n, alcm_stream_t stream);
 /* alcm_opconv_dense: the narrow AMPBlock conv of BigVGAN stages 3-5 (vocoder/bigvgan/models.py:72-81, C = N in
  * {24, 48} at F16 / F16W2, 96 at F16; ksize <= 11, (ksize-1)*dil <= 64) with the weights resident in LDS: same
@@ -317,6 +318,24 @@ int alcm_model_set_precision(alcm_model* m, int policy);
 int alcm_model_set_resblock_streams(alcm_model* m, int concurrent);
 /* re-read the ALCM_* diagnostic environment switches (they are read once at library load) */
 int alcm_reload_knobs(void);
+/* diagnostics: what alcm_opconv (as_sum == 0, n == 1) or alcm_opconv_sum (as_sum != 0, 1 <= n <= 3 terms) would
+ * launch for these arguments under the current ALCM_* switches on a device of ncu compute units (ncu <= 0: the
+ * current device's): one alcm_conv_plan_info per launch into out (room for 3) and the launch count, or the ALCM_E*
+ * code the call itself would return (message in alcm_last_error()).  Host only: pointers are tested for null-ness and
+ * alignment, never dereferenced, nothing is launched, and with ncu > 0 no device is needed.
+ * kernel: 0 lin_plane, 1 wconv3, 2 wconv3 sum form, 3 wconv2, 4 nconv, 5 opconv_kernel; name: the profile row. */
+typedef struct alcm_conv_plan_info {
+  char name[160];
+  int kernel, bm, bn;
+  int64_t grid; /* workgroups of the conv launch */
+  int ksplit;   /* K parts (1 = none; > 1 adds the reduction launch) */
+  int n_major;
+  int ncu;
+} alcm_conv_plan_info;
+int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int as_sum, int ncu, alcm_conv_plan_info* out,
+                         int* launches);
+/* diagnostics: the K-part count both K-split users take (alcm_convplan.h ksplit_parts) */
+int alcm_debug_ksplit_parts(int64_t tiles, int64_t slots, int chunks, double elems, double ws_floats);
 /* diagnostics: the BigVGAN tail-conv phase trace (ALCM_TCONV_TRACE=1, which selects the tail convs' diagnostics
  * instantiations): shader-clock cycles summed over waves and tiles for [window + first slices, K loop, post-loop
  * barrier, staging, residual + state, Activation1d, final barrier] and the wave-tile count, since the last reset;

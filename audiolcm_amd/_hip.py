@@ -57,7 +57,9 @@ class OpConvArgs(C.Structure):
 
 class ConvPlanInfo(C.Structure):
     _fields_ = [("name", C.c_char * 160), ("kernel", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("grid", i64),
-                ("ksplit", C.c_int), ("n_major", C.c_int), ("ncu", C.c_int)]
+                ("ksplit", C.c_int), ("n_major", C.c_int), ("ncu", C.c_int), ("inst", C.c_char * 96),
+                ("block", C.c_int), ("ncg", C.c_int), ("wslots", C.c_int), ("tiles_per_batch", C.c_int), ("tiles", i64),
+                ("flops", C.c_double), ("bytes", C.c_double)]
 
 
 class NamedTensor(C.Structure):
@@ -206,19 +208,24 @@ def debug_tconv_wg_times(n_wg: int) -> list:
     return [tuple(out[4 * i: 4 * i + 4]) for i in range(n)]
 
 
-CONV_KERNELS = ("lin_plane", "wconv3", "wconv3_sum", "wconv2", "nconv", "opconv_kernel")
+CONV_KERNELS = ("lin_plane", "wconv3", "wconv3_sum", "wconv2", "nconv", "opconv_kernel", "tconv", "tconv2")
+PLAN_OPCONV, PLAN_SUM, PLAN_DENSE = 0, 1, 2
 
 
-def debug_conv_plan(args, n: int = 1, as_sum: bool = False, ncu: int = 0) -> list:
-    """Diagnostics: the launches alcm_opconv (one OpConvArgs) or alcm_opconv_sum (as_sum: an array of n) would make under
-    the current ALCM_* switches on ncu compute units (0 = the current device's), one dict per launch; raises HipError
-    with the call's own error.  Host only: nothing is launched or dereferenced (alcm_debug_conv_plan)."""
+def debug_conv_plan(args, n: int = 1, form: int = PLAN_OPCONV, ncu: int = 0) -> list:
+    """Diagnostics: the launches alcm_opconv (form 0, one OpConvArgs), alcm_opconv_sum (form 1 / True: an array of n) or
+    alcm_opconv_dense (form 2, one OpConvArgs) would make under the current ALCM_* switches on ncu compute units (0 =
+    the current device's), one dict per launch; raises HipError with the call's own error.  Host only: nothing is
+    launched or dereferenced (alcm_debug_conv_plan).  inst, block, ncg and wslots are the tail convs' alone."""
     out = (ConvPlanInfo * 3)()
     nl = C.c_int(0)
-    a = args if as_sum else C.byref(args)
-    check(lib().alcm_debug_conv_plan(a, n, int(as_sum), ncu, out, C.byref(nl)), "alcm_debug_conv_plan")
+    a = args if int(form) == PLAN_SUM else C.byref(args)
+    check(lib().alcm_debug_conv_plan(a, n, int(form), ncu, out, C.byref(nl)), "alcm_debug_conv_plan")
     return [dict(name=out[i].name.decode(), kernel=CONV_KERNELS[out[i].kernel], bm=out[i].bm, bn=out[i].bn,
-                 grid=int(out[i].grid), ksplit=out[i].ksplit, n_major=out[i].n_major, ncu=out[i].ncu)
+                 grid=int(out[i].grid), ksplit=out[i].ksplit, n_major=out[i].n_major, ncu=out[i].ncu,
+                 inst=out[i].inst.decode(), block=out[i].block, ncg=out[i].ncg, wslots=out[i].wslots,
+                 tiles_per_batch=out[i].tiles_per_batch, tiles=int(out[i].tiles), flops=out[i].flops,
+                 bytes=out[i].bytes)
             for i in range(nl.value)]
 
 

@@ -1,6 +1,7 @@
 // The operand-plane conv planner (alcm_convplan.h): one validator and one kernel choice for alcm_opconv and
 // alcm_opconv_sum.  Order of preference of a single conv: lin_plane (k = 1), wconv3 (persistent, by shape), wconv2
-// (two workgroups per CU), nconv (C = 24 tail), opconv_kernel's tile ladder.
+// (two workgroups per CU), nconv (C = 24 tail), opconv_kernel's tile ladder.  alcm_opconv_dense (the BigVGAN tail
+// convs on dense weights) has its own validator and choice between tconv_kernel and tconv2_kernel, dense_conv_plan.
 #include "alcm_convplan.h"
 
 #include <algorithm>
@@ -440,6 +441,142 @@ int conv_sum_plan(const alcm_opconv_args* a, int n, int ncu, const Knobs& k, Con
   std::snprintf(q.name, sizeof(q.name), "alcm::wconv3_kernel<%d, 3, false>", a0.prec);
   shape_suffix(&q, k, " T%d C%d N%d k%d+%d+%d", a0.T, a0.Cp, a0.N, a[0].ksize, a[1].ksize, a[2].ksize);
   *launches = 1;
+  return 0;
+}
+
+bool opconv_act_supported(int prec, int N, int Cp_in) {
+  if (N % 4 || N <= 0) return false;
+  // opconv_kernel ACT tiles (BN <= 96): HBM-bound layers, the fusion saves ~15%.  Wide layers keep conv + standalone
+  // Activation1d: a fused epilogue in the two-workgroup wide conv measured -6 % end to end
+  return N <= 96;
+}
+
+// ------------------------------------------------------------------ the tail convs (alcm_opconv_dense)
+bool tconv_supported(const Knobs& k, int prec, int C, int N, int ksize, int dil) {
+  if (k.tconv == 0) return false;
+  if (prec != PREC_F16 && prec != PREC_F16W2) return false;
+  if (C != N || ksize > 11 || (ksize - 1) * dil > 64) return false;
+  if (C == 96) return prec == PREC_F16;
+  return C == 48 || C == 24;
+}
+
+namespace {
+
+// every operand check of alcm_opconv_dense: dense fp16 weights [N][kpad] (K = tap * C + c; lo plane w_lo_off elements
+// after hi for F16W2), out / res fp32 [B][T][N], Activation1d of the result into act_plane (or none)
+const char* validate_dense(const alcm_opconv_args& a, const Knobs& k) {
+  const bool act = a.act_plane != nullptr;
+  if (!a.a || !a.w || a.B <= 0 || a.T <= 0) return "opconv_dense: bad arguments";
+  if (act && (!a.act_alpha_exp || !a.act_inv_beta || !a.act_up_filter || !a.act_down_filter || a.N % 2))
+    return "opconv_dense: activation parameters";
+  if (!tconv_supported(k, a.prec, a.C, a.N, a.ksize, a.dil)) return "tconv: unsupported shape";
+  if (a.C <= 0 || a.Cp < a.C || a.ksize < 1 || a.dil < 1) return "tconv: bad geometry";
+  if (a.kpad != round_up(a.ksize * a.C, 32)) return "tconv: dense weight layout";
+  if (2 * a.pad != (a.ksize - 1) * a.dil || a.out_stride > 0 || a.out_act || a.geglu_plane)
+    return "tconv: same-length convs only";
+  // (the fp16 weight plane the kernels read lies 2 * w_lo_off elements behind w: aligned where w and w_lo_off are)
+  if ((addr(a.a) & 15) || (addr(a.w) & 15) || (a.w_lo_off % 8) || (a.Cp % 8) || (a.res && (addr(a.res) & 15)) ||
+      (a.out && (addr(a.out) & 15)))
+    return "tconv: alignment";
+  if (act && (a.accumulate || (a.out && !a.res))) return "tconv: epilogue combination";
+  // tiles recompute ACT_EPI_HALO rows on each side: a neighbour's state rows must still hold the residual
+  if (act && a.out && (const void*)a.out == (const void*)a.res) return "tconv: fused activation: out aliases res";
+  if (act && (addr(a.act_plane) & 3)) return "tconv: act_plane alignment";
+  if (a.out_plane) return "tconv: no plane output";
+  return nullptr;
+}
+
+}  // namespace
+
+int dense_conv_plan(const alcm_opconv_args& a, int ncu, const Knobs& k, ConvPlan* p) {
+  *p = ConvPlan{};
+  p->ksplit = 1;
+  if (const char* e = validate_dense(a, k)) return fail(p, e);
+  const bool act = a.act_plane != nullptr;
+  const int C = a.C, ks = a.ksize, npb = a.prec == PREC_F16W2 ? 2 : 1;
+  // ALCM_TCONV: 1 by shape, 2 streamed weights (two workgroups per CU) wherever the shape allows, 3 resident weights.
+  // Measured per launch (scripts/microbench.py tconv): streamed wins at C = 96 and C = 24, resident at C = 48
+  const int tk = k.tconv;
+  const bool streamed = tk == 2 || (tk != 3 && tk != 4 && C != 48);
+  // ALCM_TCONV=4 (C = 48): column halves (NS = 24, the B fragments of columns 24..31 read one zero row) on 128-row
+  // tiles, so the resident weights (k11: 54 KB) and the window leave room for two workgroups per CU
+  const bool half48 = !streamed && C == 48 && (tk == 4 || tk == 5);
+  const int occ48 = (tk == 5 && ks <= 3) ? 3 : 2;  // ALCM_TCONV=5: k = 3 at three workgroups per CU
+  // resident C = 48 at F16W2: the LDS weight region sized by the taps (k <= 7 leaves room for the window apart from
+  // the staged tile); every other instantiation reserves 11 taps
+  const int kmax48 = npb == 2 ? (ks <= 3 ? 3 : (ks <= 7 ? 7 : 11)) : 11;
+  int wgs = 0;  // persistent grids: workgroups per CU; 0 = one workgroup per tile
+  if (streamed) {
+    p->kernel = CK_TCONV2;
+    p->block = 256;
+    p->NS = C;
+    p->BM = C == 96 ? 192 : 256;
+    if (C == 96) {
+      // persistent, two workgroups per CU, the second half delayed by 2 sleeps (scripts/microbench.py tconv, one box:
+      // k11 0.547 -> 0.491 ms, k3 0.300 -> 0.301, conv2 + residual 0.732 -> 0.695)
+      p->R = 11; p->OCC = 2; p->STG = 2;
+      wgs = 2;
+    } else if (C == 48) {
+      p->R = 24; p->OCC = 2;
+    } else if (npb == 2) {
+      // C = 24 one workgroup per tile (persistent measured +5..+17 %), four workgroups per CU (6-row Activation1d runs
+      // and the residual loaded in the epilogue keep it at 128 VGPRs): conv2 + residual + Activation1d 0.61 -> 0.51 ms
+      // (k3), 0.70 -> 0.55 (k11), conv1 k3 0.39 -> 0.37, end to end -0.5 ms/step
+      p->R = 6; p->OCC = 4;
+    } else {
+      // (other policies; a W1 twin of the W2 instantiation's template arguments above made the compiler spill 84 B in
+      // the W2 kernel, 12 without)
+      p->R = 12; p->OCC = 2;
+    }
+  } else {
+    p->kernel = CK_TCONV;
+    if (C == 96) {  // two column halves: the 96 x 1056 weight matrix does not fit one CU's LDS
+      p->NS = 48; p->BM = 192; p->R = 11; p->KMAX = 11; p->OCC = 1;
+    } else if (half48) {
+      // (F16 has the one 11-tap, two-per-CU instantiation; at ALCM_TCONV=5, k = 3 its grid is still three per CU)
+      p->NS = 24; p->BM = 128; p->R = 7; p->KMAX = kmax48; p->OCC = npb == 2 ? occ48 : 2;
+    } else if (C == 48) {
+      p->NS = 48; p->BM = 256; p->R = 12; p->KMAX = kmax48; p->OCC = 1;
+    } else {
+      p->NS = 24; p->BM = 256; p->R = 6; p->KMAX = 11; p->OCC = 1;
+    }
+    p->block = p->BM * 2 + 64;
+    wgs = half48 ? occ48 : (C == 24 ? 2 : 1);  // C = 24 fits two per CU
+  }
+  p->C = C; p->NPB = npb; p->BN = p->NS;
+  p->act = act;
+  const int slots = a.kpad / 8;
+  p->wslots = slots % 2 ? slots : slots + 1;
+  p->ncg = p->tiles_n = a.N / p->NS;
+  // tiles overlap by 2 * ACT_EPI_HALO rows: each computes BM conv rows and emits BM - 2 * HALO
+  p->tiles_per_batch = (a.T + (p->BM - 2 * ACT_EPI_HALO) - 1) / (p->BM - 2 * ACT_EPI_HALO);
+  p->tiles = (int64_t)a.B * p->tiles_per_batch * p->ncg;
+  if (p->tiles >= (1ll << 30)) return fail(p, "tconv: problem too large");
+  p->grid = wgs ? std::min<int64_t>(p->tiles, (int64_t)ncu * wgs) : p->tiles;
+  // resident: a multiple of ncg workgroups so a workgroup's column group (blockIdx % ncg) is the same for every tile
+  // it takes (tile % ncg == blockIdx % ncg)
+  if (!streamed) p->grid = std::max<int64_t>(p->ncg, p->grid / p->ncg * p->ncg);
+  const bool res = a.res != nullptr, out = a.out != nullptr;
+  if (act && !res && !out) p->epi = TE_CONV1;
+  else if (act && res && out) p->epi = TE_CONV2;
+  else if (!act && res && out) p->epi = TE_LAST;
+  else return fail(p, "tconv: unsupported epilogue combination");
+  const double M = (double)a.B * a.T;
+  p->flops = 2.0 * M * a.N * (double)ks * C;
+  p->bytes = M * C * 2.0 + (double)a.N * a.kpad * 2.0 * npb +
+             M * a.N * 4.0 * ((out ? 1 : 0) + (res ? 1 : 0) + (a.accumulate ? 1 : 0)) + (act ? M * a.N * 2.0 : 0.0);
+  // the historical profile row (bench.py and the recorded profiles join by it); the template-id is p->inst
+  std::snprintf(p->name, sizeof(p->name), "alcm::tconv%s_kernel<C%d, W%d, BM%d, %s%s%s>", streamed ? "2" : "", C, npb,
+                p->BM, act ? "act" : "", res ? "+res" : "", p->epi == TE_LAST ? "+acc" : "");
+  shape_suffix(p, k, " T%d k%d", a.T, ks, 0);
+  static const char* const kEpi[] = {"true, false, false, false", "true, true, true, false",
+                                     "false, true, false, true"};  // ACT, RES, OUTW, ACC
+  if (streamed)
+    std::snprintf(p->inst, sizeof(p->inst), "tconv2_kernel<%d, %d, %d, %d, %d, %s, %d, %d>", C, p->NS, npb, p->BM, p->R,
+                  kEpi[p->epi], p->OCC, p->STG);
+  else
+    std::snprintf(p->inst, sizeof(p->inst), "tconv_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", C, p->NS, npb, p->BM, p->R,
+                  p->KMAX, p->OCC, kEpi[p->epi]);
   return 0;
 }
 

@@ -78,8 +78,6 @@ int opconv(const alcm_opconv_args& a, hipStream_t s);
 int flash_attention(const float* qkv, float* O, int B, int L, int H, int nh, int prec, hipStream_t s,
                     void* o_plane = nullptr, const float* bias = nullptr, int bld = 0, float scale = 0.f,
                     const void* qkv_plane = nullptr);
-// whether opconv can fuse Activation1d into its epilogue for N output channels at this precision
-bool opconv_act_supported(int prec, int N, int Cp_in);
 int opconv_sum(const alcm_opconv_args* a, int n, hipStream_t s);
 // the launches of a ConvPlan (alcm_convplan.h), one per kernel file: fill the kernel's argument struct, pick the
 // instantiation the plan names, launch, record the profile row
@@ -88,11 +86,9 @@ int wconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s); 
 int wconv3_sum_launch(const ConvPlan& pl, const alcm_opconv_args* a, int n, hipStream_t s);            // alcm_wconv.hip
 int nconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s);                        // alcm_nconv.hip
 
-// narrow AMPBlock conv with resident dense weights (alcm_tconv.hip); actepi: const ActEpiDev* or nullptr
-bool tconv_supported(int prec, int C, int N, int ksize, int dil);
-struct ActEpiDev;
-int tconv(const alcm_opconv_args& a, const unsigned short* wd, int64_t wd_lo, int kd, const ActEpiDev* act,
-          double flops, double bytes, hipStream_t s);
+// alcm_opconv_dense: the narrow AMPBlock conv on dense weights (a.w / w_lo_off / kpad as the C entry defines them),
+// planned by dense_conv_plan and launched by alcm_tconv.hip
+int opconv_dense(const alcm_opconv_args& a, hipStream_t s);
 
 struct Taps12O;
 

@@ -22,7 +22,8 @@ struct Knobs {
                                  // double-buffered, -1: 64-deep for plane outputs), 0 = wconv2
   int tconv = 1;                 // ALCM_TCONV: narrow conv for BigVGAN stages 3-5: 1 by shape, 2 streamed weights,
                                  // 3 resident weights, 4 resident with C = 48 as 24-column halves on 128-row tiles (two
-                                 // workgroups per CU), 5 = 4 with k = 3 at three per CU (alcm_tconv.hip), 0 = opconv / nconv
+                                 // workgroups per CU), 5 = 4 with k = 3 at three per CU (decided by dense_conv_plan,
+                                 // alcm_convplan.cpp; kernels in alcm_tconv.hip), 0 = opconv / nconv
   int act_defer = 1;             // ALCM_ACT_DEFER: act_mfma issues a tile's plane stores one tile late, before the next
                                  // prefetch (0 = at the end of the tile)
   int act_mfma = 1;              // ALCM_ACT_MFMA: Activation1d FIRs on MFMA for the wide stages (0 = VALU act_coop)

@@ -1370,19 +1370,22 @@ static bool stage_tconv(const StageW& S, int prec) {
   if (S.rb.empty() || !S.rb[0].c1[0].dw.p) return false;
   for (const AmpW& A : S.rb)
     for (size_t l = 0; l < A.dil.size(); ++l)
-      if (!tconv_supported(prec, S.cout, S.cout, A.k, A.dil[l])) return false;
+      if (!tconv_supported(knobs(), prec, S.cout, S.cout, A.k, A.dil[l])) return false;
   return true;
 }
 
-// the alcm_opconv arguments of a same-length conv of the planes `in` (default: the workspace planes)
+// the alcm_opconv arguments of a same-length conv of the planes `in` (default: the workspace planes); dense: the
+// alcm_opconv_dense arguments, which differ in the weight packing (cw.dw)
 static alcm_opconv_args plane_args(const ConvW& cw, const VocWs& w, int B, int T, int dil, const float* res, float* out,
-                                   float out_scale, int accumulate, int out_act, int prec, const u16* in) {
+                                   float out_scale, int accumulate, int out_act, int prec, const u16* in,
+                                   bool dense = false) {
+  const Packed& pk = dense ? cw.dw : cw.w;
   alcm_opconv_args g;
   std::memset(&g, 0, sizeof(g));
   g.a = in ? in : w.pl; g.a_lo_off = (int64_t)B * T * cw.w.cpad;
   g.B = B; g.T = T; g.C = cw.w.cin; g.Cp = cw.w.cpad;
   g.ksize = cw.w.taps; g.dil = dil; g.pad = (cw.w.taps - 1) * dil / 2;
-  g.w = cw.w.p; g.w_lo_off = cw.w.lo; g.kpad = cw.w.kpad; g.N = cw.w.rows;
+  g.w = pk.p; g.w_lo_off = pk.lo; g.kpad = pk.kpad; g.N = cw.w.rows;
   g.bias = cw.b; g.res = res; g.out = out; g.out_act = out_act; g.accumulate = accumulate;
   g.out_scale = out_scale; g.prec = prec;
   return g;
@@ -1392,34 +1395,7 @@ static int plane_conv(hipStream_t s, const ConvW& cw, const VocWs& w, int B, int
                       float* out, float out_scale, int accumulate, int out_act, int prec, const u16* in = nullptr,
                       const ActW* act = nullptr, u16* act_out = nullptr, bool dense = false,
                       void* out_plane = nullptr) {
-  alcm_opconv_args g;
-  std::memset(&g, 0, sizeof(g));
-  if (dense) {
-    g.a = in ? in : w.pl;
-    g.B = B; g.T = T; g.C = cw.w.cin; g.Cp = cw.w.cpad;
-    g.ksize = cw.w.taps; g.dil = dil; g.pad = (cw.w.taps - 1) * dil / 2;
-    g.N = cw.w.rows; g.bias = cw.b; g.res = res; g.out = out; g.out_scale = out_scale; g.accumulate = accumulate;
-    g.prec = prec;
-    ActEpiDev E{};
-    if (act) {
-      E.plane = act_out;
-      E.plane_lo = 0;
-      E.Cp = round_up(cw.w.rows, 32);
-      E.aexp = act->aexp;
-      E.ibeta = act->ibeta;
-      for (int k = 0; k < 12; ++k) {
-        E.f.up[k] = 2.0f * act->fup[k];
-        E.f.dn[k] = act->fdn[k];
-      }
-    }
-    const double M = (double)B * T;
-    const double flops = 2.0 * M * g.N * (double)g.ksize * g.C;
-    const double bytes = M * g.C * 2.0 + (double)g.N * cw.dw.kpad * 2.0 * (prec == PREC_F16W2 ? 2 : 1) +
-                         M * g.N * 4.0 * ((out ? 1 : 0) + (res ? 1 : 0) + (accumulate ? 1 : 0)) +
-                         (act ? M * g.N * 2.0 : 0.0);
-    return tconv(g, cw.dw.p + 2 * cw.dw.lo, cw.dw.lo, cw.dw.kpad, act ? &E : nullptr, flops, bytes, s);
-  }
-  g = plane_args(cw, w, B, T, dil, res, out, out_scale, accumulate, out_act, prec, in);
+  alcm_opconv_args g = plane_args(cw, w, B, T, dil, res, out, out_scale, accumulate, out_act, prec, in, dense);
   if (act) {
     g.act_plane = act_out;
     g.act_plane_lo_off = (int64_t)B * T * round_up(cw.w.rows, 32);
@@ -1429,7 +1405,7 @@ static int plane_conv(hipStream_t s, const ConvW& cw, const VocWs& w, int B, int
     g.act_down_filter = act->fdn;
   }
   g.out_plane = out_plane;
-  return opconv(g, s);
+  return dense ? opconv_dense(g, s) : opconv(g, s);
 }
 
 static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, int M, void* ws, size_t wsb,

@@ -565,13 +565,6 @@ static void launch_opconv(const ConvPlan& pl, const OpConvDev& P, int prec, hipS
   else launch_opconv_v<BM, BN, WGM, WGN, TPS, false, false>(P, grid, prec, s);
 }
 
-bool opconv_act_supported(int prec, int N, int Cp_in) {
-  if (N % 4 || N <= 0) return false;
-  // opconv_kernel ACT tiles (BN <= 96): HBM-bound layers, the fusion saves ~15%.  Wide layers keep conv + standalone
-  // Activation1d: a fused epilogue in the two-workgroup wide conv measured -6 % end to end
-  return N <= 96;
-}
-
 // the launch of a CK_OPCONV plan (alcm_convplan.cpp): opconv_kernel's tile ladder
 static int opconv_kernel_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
   const bool strided = a.out_stride > 0;
@@ -667,17 +660,18 @@ extern "C" int alcm_opconv(const alcm_opconv_args* args, alcm_stream_t stream) {
   return alcm::opconv(*args, (hipStream_t)stream);
 }
 
-extern "C" int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int as_sum, int ncu, alcm_conv_plan_info* out,
+extern "C" int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int form, int ncu, alcm_conv_plan_info* out,
                                     int* launches) {
-  if (!args || !out || !launches || n < 1 || (!as_sum && n != 1))
+  if (!args || !out || !launches || n < 1 || form < 0 || form > 2 || (form != 1 && n != 1))
     return alcm::set_error(ALCM_E_INVALID, "debug_conv_plan: bad arguments");
   alcm::ConvPlan pl[3];
   if (ncu <= 0) ncu = alcm::device_cus();
   *launches = 0;
-  const int rc = as_sum ? alcm::conv_sum_plan(args, n, ncu, alcm::knobs(), pl, launches)
-                        : alcm::conv_plan(args[0], ncu, alcm::knobs(), &pl[0]);
+  const int rc = form == 1   ? alcm::conv_sum_plan(args, n, ncu, alcm::knobs(), pl, launches)
+                 : form == 2 ? alcm::dense_conv_plan(args[0], ncu, alcm::knobs(), &pl[0])
+                             : alcm::conv_plan(args[0], ncu, alcm::knobs(), &pl[0]);
   if (rc) return alcm::set_error(rc, pl[0].err);
-  if (!as_sum) *launches = 1;
+  if (form != 1) *launches = 1;
   for (int i = 0; i < *launches; ++i) {
     alcm_conv_plan_info& o = out[i];
     std::snprintf(o.name, sizeof(o.name), "%s", pl[i].name);
@@ -687,6 +681,14 @@ extern "C" int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int as_
     o.ksplit = pl[i].ksplit;
     o.n_major = pl[i].n_major;
     o.ncu = ncu;
+    std::snprintf(o.inst, sizeof(o.inst), "%s", pl[i].inst);
+    o.block = pl[i].block;
+    o.ncg = pl[i].ncg;
+    o.tiles_per_batch = pl[i].tiles_per_batch;
+    o.wslots = pl[i].wslots;
+    o.tiles = pl[i].tiles;
+    o.flops = pl[i].flops;
+    o.bytes = pl[i].bytes;
   }
   return 0;
 }

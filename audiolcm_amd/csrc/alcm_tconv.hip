@@ -20,6 +20,11 @@
 //     them (act_epilogue_ct: compile-time channel pairs, one pass over the threads) into the next conv's planes;
 //   * C = 96 runs as two launches' worth of column halves (NS = 48 output channels per tile): its 96 x 1056
 //     weight matrix does not fit one CU's LDS.
+//
+// tconv2_kernel is the streamed-weight sibling (the weights go through an LDS ring, so several workgroups fit a CU).
+// Which of the two a call gets, with which tile configuration, grid and profile row, is decided on the host by
+// dense_conv_plan (alcm_convplan.cpp), which also holds every argument check; the host part of this file is the list
+// of built tile configurations, one launcher that takes the plan, and the alcm_opconv_dense entry.
 #include <cstdio>
 #include <cstring>
 
@@ -619,181 +624,106 @@ unsigned long long* g_tc_trace = nullptr;  // diagnostics trace buffer (64 x 8 s
                                            // allocated by the first
                                            // alcm_debug_tconv_trace call (never inside a launch path)
 
-struct TConvCfg {
-  int C, NS, NPB, BM;
-};
+using TcLaunch = void (*)(const TConvDev&, unsigned, hipStream_t);
 
-bool tconv_supported(int prec, int C, int N, int ksize, int dil) {
-  if (knobs().tconv == 0) return false;
-  if (prec != PREC_F16 && prec != PREC_F16W2) return false;
-  if (C != N || ksize > 11 || (ksize - 1) * dil > 64) return false;
-  if (C == 96) return prec == PREC_F16;
-  return C == 48 || C == 24;
+// one instantiation of either family (FAM: CK_TCONV takes KMAX, CK_TCONV2 takes STG)
+template <int FAM, int C, int NS, int NPB, int BM, int R, int KMAX, int OCC, int STG, bool ACT, bool RES, bool OUTW,
+          bool ACC, bool DG>
+static void tc_kernel(const TConvDev& P, unsigned grid, hipStream_t s) {
+  if constexpr (FAM == CK_TCONV)
+    hipLaunchKernelGGL((tconv_kernel<C, NS, NPB, BM, R, KMAX, OCC, ACT, RES, OUTW, ACC, DG>), dim3(grid),
+                       dim3(BM * 2 + 64), 0, s, P);
+  else
+    hipLaunchKernelGGL((tconv2_kernel<C, NS, NPB, BM, R, ACT, RES, OUTW, ACC, OCC, STG, DG>), dim3(grid), dim3(256), 0,
+                       s, P);
 }
 
-template <int C, int NS, int NPB, int BM, int R, int KMAX, int OCC, bool ACT, bool RES, bool OUTW, bool ACC>
-static void tc_launch(const TConvDev& P, bool diag, int grid, hipStream_t s) {
-  const dim3 g(grid), blk(BM * 2 + 64);
-  if (diag) hipLaunchKernelGGL((tconv_kernel<C, NS, NPB, BM, R, KMAX, OCC, ACT, RES, OUTW, ACC, true>), g, blk, 0, s, P);
-  else hipLaunchKernelGGL((tconv_kernel<C, NS, NPB, BM, R, KMAX, OCC, ACT, RES, OUTW, ACC, false>), g, blk, 0, s, P);
+// the epilogue forms a tile configuration is built with:  ACT    RES    OUTW   ACC
+template <int FAM, int C, int NS, int NPB, int BM, int R, int KMAX, int OCC, int STG, bool DG>
+static TcLaunch tc_epi(int epi) {
+  switch (epi) {
+    case TE_CONV1: return tc_kernel<FAM, C, NS, NPB, BM, R, KMAX, OCC, STG, true, false, false, false, DG>;
+    case TE_CONV2: return tc_kernel<FAM, C, NS, NPB, BM, R, KMAX, OCC, STG, true, true, true, false, DG>;
+    case TE_LAST: return tc_kernel<FAM, C, NS, NPB, BM, R, KMAX, OCC, STG, false, true, false, true, DG>;
+  }
+  return nullptr;
 }
 
-template <int C, int NS, int NPB, int BM, int R, int KMAX = 11, int OCC = 1>
-static int tc_mode(const TConvDev& P, bool diag, int grid, bool act, bool res, bool outw, bool acc, hipStream_t s) {
-  if (P.kd > (KMAX * C + 31) / 32 * 32) return set_error(ALCM_E_INVALID, "tconv: weights exceed the LDS reservation");
-  if (act && !res && !outw && !acc) tc_launch<C, NS, NPB, BM, R, KMAX, OCC, true, false, false, false>(P, diag, grid, s);
-  else if (act && res && outw && !acc) tc_launch<C, NS, NPB, BM, R, KMAX, OCC, true, true, true, false>(P, diag, grid, s);
-  else if (!act && res && acc) tc_launch<C, NS, NPB, BM, R, KMAX, OCC, false, true, false, true>(P, diag, grid, s);
-  else return set_error(ALCM_E_INVALID, "tconv: unsupported epilogue combination");
-  return 0;
+// the launch of this tile configuration if it is the plan's (diag: its diagnostics build), else null
+template <int FAM, int C, int NS, int NPB, int BM, int R, int KMAX, int OCC, int STG>
+static TcLaunch tc_match(const ConvPlan& pl, bool diag) {
+  if (pl.kernel != FAM || pl.C != C || pl.NS != NS || pl.NPB != NPB || pl.BM != BM || pl.R != R || pl.KMAX != KMAX ||
+      pl.OCC != OCC || pl.STG != STG || pl.block != (FAM == CK_TCONV ? BM * 2 + 64 : 256))
+    return nullptr;
+  return diag ? tc_epi<FAM, C, NS, NPB, BM, R, KMAX, OCC, STG, true>(pl.epi)
+              : tc_epi<FAM, C, NS, NPB, BM, R, KMAX, OCC, STG, false>(pl.epi);
 }
 
-template <int C, int NS, int NPB, int BM, int R, bool ACT, bool RES, bool OUTW, bool ACC, int OCC, int STG>
-static void tc2_launch(const TConvDev& P, bool diag, int grid, hipStream_t s) {
-  if (diag) hipLaunchKernelGGL((tconv2_kernel<C, NS, NPB, BM, R, ACT, RES, OUTW, ACC, OCC, STG, true>), dim3(grid), dim3(256), 0, s, P);
-  else hipLaunchKernelGGL((tconv2_kernel<C, NS, NPB, BM, R, ACT, RES, OUTW, ACC, OCC, STG, false>), dim3(grid), dim3(256), 0, s, P);
+// every tile configuration the library is built with (dense_conv_plan chooses among them, alcm_convplan.cpp)
+static TcLaunch tc_pick(const ConvPlan& pl, bool diag) {
+  static constexpr TcLaunch (*kBuilt[])(const ConvPlan&, bool) = {
+      //                  C  NS NPB  BM   R KMAX OCC STG
+      tc_match<CK_TCONV2, 96, 96, 1, 192, 11, 0, 2, 2>,
+      tc_match<CK_TCONV2, 48, 48, 2, 256, 24, 0, 2, 0>,
+      tc_match<CK_TCONV2, 48, 48, 1, 256, 24, 0, 2, 0>,
+      tc_match<CK_TCONV2, 24, 24, 2, 256, 6, 0, 4, 0>,
+      tc_match<CK_TCONV2, 24, 24, 1, 256, 12, 0, 2, 0>,
+      tc_match<CK_TCONV, 96, 48, 1, 192, 11, 11, 1, 0>,
+      tc_match<CK_TCONV, 48, 24, 2, 128, 7, 3, 3, 0>,
+      tc_match<CK_TCONV, 48, 24, 2, 128, 7, 3, 2, 0>,
+      tc_match<CK_TCONV, 48, 24, 2, 128, 7, 7, 2, 0>,
+      tc_match<CK_TCONV, 48, 24, 2, 128, 7, 11, 2, 0>,
+      tc_match<CK_TCONV, 48, 24, 1, 128, 7, 11, 2, 0>,
+      tc_match<CK_TCONV, 48, 48, 2, 256, 12, 3, 1, 0>,
+      tc_match<CK_TCONV, 48, 48, 2, 256, 12, 7, 1, 0>,
+      tc_match<CK_TCONV, 48, 48, 2, 256, 12, 11, 1, 0>,
+      tc_match<CK_TCONV, 48, 48, 1, 256, 12, 11, 1, 0>,
+      tc_match<CK_TCONV, 24, 24, 2, 256, 6, 11, 1, 0>,
+      tc_match<CK_TCONV, 24, 24, 1, 256, 6, 11, 1, 0>,
+  };
+  for (auto match : kBuilt)
+    if (TcLaunch f = match(pl, diag)) return f;
+  return nullptr;
 }
 
-template <int C, int NS, int NPB, int BM, int R, int OCC = 2, int STG = 0>
-static int tc2_mode(const TConvDev& P, bool diag, int grid, bool act, bool res, bool outw, bool acc, hipStream_t s) {
-  if (act && !res && !outw && !acc) tc2_launch<C, NS, NPB, BM, R, true, false, false, false, OCC, STG>(P, diag, grid, s);
-  else if (act && res && outw && !acc) tc2_launch<C, NS, NPB, BM, R, true, true, true, false, OCC, STG>(P, diag, grid, s);
-  else if (!act && res && acc) tc2_launch<C, NS, NPB, BM, R, false, true, false, true, OCC, STG>(P, diag, grid, s);
-  else return set_error(ALCM_E_INVALID, "tconv: unsupported epilogue combination");
-  return 0;
-}
-
-// conv on operand planes with dense fp16 weights `wd` ([N][kd], K = tap * C + c; lo plane wd_lo elements after
-// hi for F16W2): out / res fp32 [B][T][N], Activation1d of the result into act->plane (or none)
-int tconv(const alcm_opconv_args& a, const u16* wd, int64_t wd_lo, int kd, const ActEpiDev* act, double flops,
-          double bytes, hipStream_t s) {
-  if (!tconv_supported(a.prec, a.C, a.N, a.ksize, a.dil)) return set_error(ALCM_E_INVALID, "tconv: unsupported shape");
-  if (a.C <= 0 || a.Cp < a.C || a.ksize < 1 || a.dil < 1) return set_error(ALCM_E_INVALID, "tconv: bad geometry");
-  if (kd != (a.ksize * a.C + 31) / 32 * 32 || !wd) return set_error(ALCM_E_INVALID, "tconv: dense weight layout");
-  if (2 * a.pad != (a.ksize - 1) * a.dil || a.out_stride > 0 || a.out_act || a.geglu_plane)
-    return set_error(ALCM_E_INVALID, "tconv: same-length convs only");
-  if ((((uintptr_t)a.a) & 15) || (((uintptr_t)wd) & 15) || (wd_lo % 8) || (a.Cp % 8) ||
-      (a.res && (((uintptr_t)a.res) & 15)) || (a.out && (((uintptr_t)a.out) & 15)))
-    return set_error(ALCM_E_INVALID, "tconv: alignment");
-  const bool acc_mode = !act && a.res && a.out;
-  if (act && (a.accumulate || (a.out && !a.res))) return set_error(ALCM_E_INVALID, "tconv: epilogue combination");
+// the launch of a CK_TCONV / CK_TCONV2 plan (dense_conv_plan): fills the kernels' arguments, launches the
+// instantiation the plan names and records its profile row.  The diagnostics build of that instantiation only when a
+// diagnostic is asked for (the trace needs its buffer, allocated by the first alcm_debug_tconv_trace call)
+static int tconv_launch(const ConvPlan& pl, const alcm_opconv_args& a, hipStream_t s) {
   TConvDev P{};
   P.a = (const u16*)a.a;
   P.T = a.T; P.Cp = a.Cp; P.ksize = a.ksize; P.dil = a.dil; P.pad = a.pad;
-  P.w = wd; P.w_lo = wd_lo; P.kd = kd; P.N = a.N;
+  P.w = conv_wplane(a); P.w_lo = a.w_lo_off; P.kd = a.kpad; P.N = a.N;
   P.bias = a.bias; P.res = a.res; P.out = a.out; P.out_scale = a.out_scale; P.accumulate = a.accumulate;
-  if (act) P.act = *act;
-  // the diagnostics instantiation only when a diagnostic is asked for (the trace needs its buffer, allocated by the
-  // first alcm_debug_tconv_trace call)
+  if (pl.act) {
+    P.act = act_epi_of(a);
+    P.act.plane_lo = 0;  // single fp16 planes
+  }
+  P.tiles_per_batch = pl.tiles_per_batch; P.ntiles = (int)pl.tiles; P.ncg = pl.ncg;
+  P.wslots = pl.wslots;
   P.ablate = knobs().tconv_ablate;
   if (knobs().tconv_trace) P.trace = g_tc_trace;
-  const bool diag = P.ablate != 0 || P.trace != nullptr;
-  const int slots = kd / 8;
-  P.wslots = slots % 2 ? slots : slots + 1;
-  const int npb = a.prec == PREC_F16W2 ? 2 : 1;
-  const int C = a.C;
-  // streamed weights (two workgroups per CU) where the resident weights would take a CU's LDS: C >= 48
-  const int tk = knobs().tconv;
-  // measured per launch (scripts/microbench.py tconv): streamed wins at C = 96 and C = 24, resident at C = 48
-  const bool streamed = tk == 2 || (tk != 3 && tk != 4 && C != 48);
-  // ALCM_TCONV=4 (C = 48): column halves (NS = 24, the B fragments of columns 24..31 read one zero row) on 128-row
-  // tiles, so the resident weights (k11: 54 KB) and the window leave room for two workgroups per CU
-  const bool half48 = !streamed && C == 48 && (tk == 4 || tk == 5);
-  const int occ48 = (tk == 5 && a.ksize <= 3) ? 3 : 2;  // ALCM_TCONV=5: k = 3 at three workgroups per CU
-  const int BM = C == 96 ? 192 : (half48 ? 128 : 256);
-  const int NS = (!streamed && C == 96) ? 48 : (half48 ? 24 : C);
-  P.ncg = a.N / NS;
-  P.tiles_per_batch = (a.T + (BM - 2 * ACT_EPI_HALO) - 1) / (BM - 2 * ACT_EPI_HALO);
-  const int64_t nt = (int64_t)a.B * P.tiles_per_batch * P.ncg;
-  if (nt >= (1ll << 30)) return set_error(ALCM_E_INVALID, "tconv: problem too large");
-  P.ntiles = (int)nt;
-  const bool outw = a.out && !acc_mode;
+  const TcLaunch launch = tc_pick(pl, P.ablate != 0 || P.trace != nullptr);
+  if (!launch) return set_error(ALCM_E_INVALID, std::string("tconv: not built: ") + pl.inst);
   void* tok = prof_start(s);
-  int rc;
-  if (streamed) {
-    // C = 96: persistent, two workgroups per CU, the second half delayed by 2 sleeps (scripts/microbench.py tconv, one
-    // box: k11 0.547 -> 0.491 ms, k3 0.300 -> 0.301, conv2 + residual 0.732 -> 0.695); C = 24 one workgroup per tile
-    // (persistent measured +5..+17 %)
-    int grid2 = (int)nt;
-    if (C == 96) grid2 = (int)std::min<int64_t>(nt, (int64_t)device_cus() * 2);
-    if (C == 96) rc = tc2_mode<96, 96, 1, 192, 11, 2, 2>(P, diag, grid2, act, a.res, outw, acc_mode, s);
-    else if (C == 48) {
-      if (npb == 2) rc = tc2_mode<48, 48, 2, 256, 24>(P, diag, grid2, act, a.res, outw, acc_mode, s);
-      else rc = tc2_mode<48, 48, 1, 256, 24>(P, diag, grid2, act, a.res, outw, acc_mode, s);
-    } else {
-      // four workgroups per CU (6-row Activation1d runs and the residual loaded in the epilogue keep it at 128 VGPRs):
-      // conv2 + residual + Activation1d 0.61 -> 0.51 ms (k3), 0.70 -> 0.55 (k11), conv1 k3 0.39 -> 0.37, end to end
-      // -0.5 ms/step (gpurun_out/r5aa)
-      if (npb == 2) rc = tc2_mode<24, 24, 2, 256, 6, 4>(P, diag, grid2, act, a.res, outw, acc_mode, s);
-      else rc = tc2_mode<24, 24, 1, 256, 12>(P, diag, grid2, act, a.res, outw, acc_mode, s);  // (other policies; a W1 twin of
-      // the W2 instantiation's template arguments above made the compiler spill 84 B in the W2 kernel, 12 without)
-    }
-  } else {
-    // persistent: a multiple of ncg workgroups so a workgroup's column group (blockIdx % ncg) is the same for every
-    // tile it takes (tile % ncg == blockIdx % ncg); C = 24 fits two per CU
-    const int wgs = half48 ? occ48 : (C == 24 ? 2 : 1);
-    int grid = std::min<int64_t>(nt, (int64_t)device_cus() * wgs);
-    grid = std::max(P.ncg, grid / P.ncg * P.ncg);
-    if (C == 96) rc = tc_mode<96, 48, 1, 192, 11>(P, diag, grid, act, a.res, outw, acc_mode, s);
-    else if (half48) {
-      if (npb == 2 && a.ksize <= 3 && occ48 == 3)
-        rc = tc_mode<48, 24, 2, 128, 7, 3, 3>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else if (npb == 2 && a.ksize <= 3) rc = tc_mode<48, 24, 2, 128, 7, 3, 2>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else if (npb == 2 && a.ksize <= 7) rc = tc_mode<48, 24, 2, 128, 7, 7, 2>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else if (npb == 2) rc = tc_mode<48, 24, 2, 128, 7, 11, 2>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else rc = tc_mode<48, 24, 1, 128, 7, 11, 2>(P, diag, grid, act, a.res, outw, acc_mode, s);
-    } else if (C == 48) {
-      // LDS weight region sized by the taps: k <= 7 leaves room for the window apart from the staged tile
-      if (npb == 2 && a.ksize <= 3) rc = tc_mode<48, 48, 2, 256, 12, 3>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else if (npb == 2 && a.ksize <= 7) rc = tc_mode<48, 48, 2, 256, 12, 7>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else if (npb == 2) rc = tc_mode<48, 48, 2, 256, 12>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else rc = tc_mode<48, 48, 1, 256, 12>(P, diag, grid, act, a.res, outw, acc_mode, s);
-    } else {
-      if (npb == 2) rc = tc_mode<24, 24, 2, 256, 6>(P, diag, grid, act, a.res, outw, acc_mode, s);
-      else rc = tc_mode<24, 24, 1, 256, 6>(P, diag, grid, act, a.res, outw, acc_mode, s);
-    }
-  }
-  if (rc) return rc;
-  if (tok) {
-    char name[96];
-    std::snprintf(name, sizeof(name), "alcm::tconv%s_kernel<C%d, W%d, BM%d, %s%s%s>", streamed ? "2" : "", C, npb, BM, act ? "act" : "",
-                  a.res ? "+res" : "", acc_mode ? "+acc" : "");
-    if (knobs().prof_shapes)
-      std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " T%d k%d", a.T, a.ksize);
-    prof_stop(tok, s, name, flops, bytes);
-  }
+  launch(P, (unsigned)pl.grid, s);
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
   ALCM_HIP(hipGetLastError());
   return 0;
+}
+
+// alcm_opconv_dense, for the models too: validate and plan once, then launch
+int opconv_dense(const alcm_opconv_args& a, hipStream_t s) {
+  ConvPlan pl;
+  if (dense_conv_plan(a, device_cus(), knobs(), &pl)) return set_error(ALCM_E_INVALID, pl.err);
+  return tconv_launch(pl, a, s);
 }
 
 }  // namespace alcm
 
 extern "C" int alcm_opconv_dense(const alcm_opconv_args* args, alcm_stream_t stream) {
-  using namespace alcm;
-  if (!args || !args->a || !args->w || args->B <= 0 || args->T <= 0) return set_error(ALCM_E_INVALID, "opconv_dense: bad arguments");
-  const alcm_opconv_args& a = *args;
-  ActEpiDev E{};
-  const bool act = a.act_plane != nullptr;
-  if (act) {
-    if (!a.act_alpha_exp || !a.act_inv_beta || !a.act_up_filter || !a.act_down_filter || a.N % 2)
-      return set_error(ALCM_E_INVALID, "opconv_dense: activation parameters");
-    E.plane = (u16*)a.act_plane;
-    E.plane_lo = 0;
-    E.Cp = round_up(a.N, 32);
-    E.aexp = a.act_alpha_exp;
-    E.ibeta = a.act_inv_beta;
-    for (int k = 0; k < 12; ++k) {
-      E.f.up[k] = 2.0f * a.act_up_filter[k];
-      E.f.dn[k] = a.act_down_filter[k];
-    }
-  }
-  const double M = (double)a.B * a.T;
-  const double flops = 2.0 * M * a.N * (double)a.ksize * a.C;
-  const double bytes = M * a.C * 2.0 + (double)a.N * a.kpad * 2.0 * (a.prec == PREC_F16W2 ? 2 : 1) +
-                       M * a.N * 4.0 * ((a.out ? 1 : 0) + (a.res ? 1 : 0) + (a.accumulate ? 1 : 0)) +
-                       (act ? M * a.N * 2.0 : 0.0);
-  return tconv(a, (const u16*)a.w + 2 * a.w_lo_off, a.w_lo_off, a.kpad, act ? &E : nullptr, flops, bytes,
-               (hipStream_t)stream);
+  if (!args) return alcm::set_error(ALCM_E_INVALID, "opconv_dense: bad arguments");
+  return alcm::opconv_dense(*args, (hipStream_t)stream);
 }
 
 // diagnostics: the tconv phase trace (ALCM_TCONV_TRACE = 1) summed since the last reset; reset zeroes it.  The first

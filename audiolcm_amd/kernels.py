@@ -381,14 +381,15 @@ def activation1d_op_f16in(x16: torch.Tensor, alpha: torch.Tensor, beta: torch.Te
     return y
 
 
-def conv_plan(args, ncu: int = 0) -> list:
-    """Which kernel(s) an operand-plane conv call would launch: args is one _hip.OpConvArgs (alcm_opconv) or a
-    sequence of up to three (alcm_opconv_sum).  -> one dict per launch (name = its profile row, kernel, bm, bn, grid,
-    ksplit, n_major, ncu); needs no GPU when ncu is given."""
+def conv_plan(args, ncu: int = 0, dense: bool = False) -> list:
+    """Which kernel(s) an operand-plane conv call would launch: args is one _hip.OpConvArgs (alcm_opconv, or
+    alcm_opconv_dense with dense = True) or a sequence of up to three (alcm_opconv_sum).  -> one dict per launch (name =
+    its profile row, kernel, bm, bn, grid, ksplit, n_major, ncu, tiles_per_batch, tiles, flops, bytes; for the tail
+    convs also inst = the template-id, block, ncg, wslots); needs no GPU when ncu is given."""
     if isinstance(args, _hip.OpConvArgs):
-        return _hip.debug_conv_plan(args, 1, False, ncu)
+        return _hip.debug_conv_plan(args, 1, _hip.PLAN_DENSE if dense else _hip.PLAN_OPCONV, ncu)
     arr = (_hip.OpConvArgs * len(args))(*args)
-    return _hip.debug_conv_plan(arr, len(args), True, ncu)
+    return _hip.debug_conv_plan(arr, len(args), _hip.PLAN_SUM, ncu)
 
 
 def opconv_sum(terms, prec: int, out_scale: float = 1.0, accumulate_into: Optional[torch.Tensor] = None,

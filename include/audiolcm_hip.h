@@ -318,12 +318,14 @@ int alcm_model_set_precision(alcm_model* m, int policy);
 int alcm_model_set_resblock_streams(alcm_model* m, int concurrent);
 /* re-read the ALCM_* diagnostic environment switches (they are read once at library load) */
 int alcm_reload_knobs(void);
-/* diagnostics: what alcm_opconv (as_sum == 0, n == 1) or alcm_opconv_sum (as_sum != 0, 1 <= n <= 3 terms) would
- * launch for these arguments under the current ALCM_* switches on a device of ncu compute units (ncu <= 0: the
- * current device's): one alcm_conv_plan_info per launch into out (room for 3) and the launch count, or the ALCM_E*
- * code the call itself would return (message in alcm_last_error()).  Host only: pointers are tested for null-ness and
- * alignment, never dereferenced, nothing is launched, and with ncu > 0 no device is needed.
- * kernel: 0 lin_plane, 1 wconv3, 2 wconv3 sum form, 3 wconv2, 4 nconv, 5 opconv_kernel; name: the profile row. */
+/* diagnostics: what alcm_opconv (form == 0, n == 1), alcm_opconv_sum (form == 1, 1 <= n <= 3 terms) or
+ * alcm_opconv_dense (form == 2, n == 1) would launch for these arguments under the current ALCM_* switches on a
+ * device of ncu compute units (ncu <= 0: the current device's): one alcm_conv_plan_info per launch into out (room for
+ * 3) and the launch count, or the ALCM_E* code the call itself would return (message in alcm_last_error()).  Host
+ * only: pointers are tested for null-ness and alignment, never dereferenced, nothing is launched, and with ncu > 0 no
+ * device is needed.
+ * kernel: 0 lin_plane, 1 wconv3, 2 wconv3 sum form, 3 wconv2, 4 nconv, 5 opconv_kernel, 6 tconv_kernel (tail conv,
+ * resident weights), 7 tconv2_kernel (tail conv, streamed weights); name: the profile row. */
 typedef struct alcm_conv_plan_info {
   char name[160];
   int kernel, bm, bn;
@@ -331,8 +333,15 @@ typedef struct alcm_conv_plan_info {
   int ksplit;   /* K parts (1 = none; > 1 adds the reduction launch) */
   int n_major;
   int ncu;
+  /* the tail convs only (empty / 0 elsewhere): the template-id of the instantiation but for its diagnostics flag,
+   * which the profile row does not spell; threads per workgroup; column groups; 16-byte slots of an LDS weight row */
+  char inst[96];
+  int block, ncg, wslots;
+  int tiles_per_batch; /* row tiles of one clip */
+  int64_t tiles;       /* output tiles */
+  double flops, bytes; /* the cost the profile row is charged */
 } alcm_conv_plan_info;
-int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int as_sum, int ncu, alcm_conv_plan_info* out,
+int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int form, int ncu, alcm_conv_plan_info* out,
                          int* launches);
 /* diagnostics: the K-part count both K-split users take (alcm_convplan.h ksplit_parts) */
 int alcm_debug_ksplit_parts(int64_t tiles, int64_t slots, int chunks, double elems, double ws_floats);

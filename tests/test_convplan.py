@@ -1,15 +1,20 @@
 """The operand-plane conv planner (audiolcm_amd/csrc/alcm_convplan.cpp): which kernel, tile, K parts and profile name
-an alcm_opconv / alcm_opconv_sum call gets, and which calls it rejects.
+an alcm_opconv / alcm_opconv_sum / alcm_opconv_dense call gets, and which calls it rejects.
 
 The CPU tests ask the library's diagnostics entry (alcm_debug_conv_plan: nothing is launched, pointers are only
 tested for null-ness and alignment) and compare with tests/data/conv_plans.json, a table of (arguments, switches,
 profile names) recorded from the build before the planner existed while it ran the benchmark and the GPU op tests.
+tests/data/dense_plans.json is the same for alcm_opconv_dense (the BigVGAN tail convs): recorded from the build before
+dense_conv_plan existed, its dispatch function compiled for the host with the two launch sites replaced by a record of
+the instantiation and the launch geometry, over every ALCM_TCONV value, (C, precision), tap count, epilogue form and
+a set of (B, T) from one partial tile to the benchmark's stage 3-5 shapes.
 The GPU tests check that a real call of each kernel family records exactly the profile row the planner names.
 """
 import contextlib
 import ctypes as C
 import json
 import os
+import re
 
 import numpy as np
 import pytest
@@ -20,10 +25,11 @@ from audiolcm_amd import _hip
 from audiolcm_amd import kernels as K
 
 TABLE = os.path.join(REPO, "tests", "data", "conv_plans.json")
+DENSE_TABLE = os.path.join(REPO, "tests", "data", "dense_plans.json")
 KNOB_ENV = {"wconv": ("ALCM_WCONV", 8), "wconv3": ("ALCM_WCONV3", -1), "wconv3_grid": ("ALCM_WCONV3_GRID", 0),
             "nconv": ("ALCM_NCONV", -1), "opconv_tile": ("ALCM_OPCONV_TILE", 0), "lin1": ("ALCM_LIN1", -1),
             "ups_t160": ("ALCM_UPS_T160", 1), "wconv_sum": ("ALCM_WCONV_SUM", 1), "ksplit": ("ALCM_KSPLIT", 1),
-            "prof_shapes": ("ALCM_PROF_SHAPES", 0)}
+            "prof_shapes": ("ALCM_PROF_SHAPES", 0), "tconv": ("ALCM_TCONV", 1)}
 POINTERS = ("a", "w", "bias", "res", "out", "act_plane", "act_alpha_exp", "act_inv_beta", "act_up_filter",
             "act_down_filter", "geglu_plane", "out_plane", "ksplit_ws")
 E_INVALID = -1
@@ -70,10 +76,11 @@ def row_args(d, index=0, out0=None):
     return a
 
 
-def plan_rc(args, n, as_sum, ncu):
+def plan_rc(args, n, form, ncu):
     out = (_hip.ConvPlanInfo * 3)()
     nl = C.c_int(0)
-    rc = _hip.lib().alcm_debug_conv_plan(args if as_sum else C.byref(args), n, int(as_sum), ncu, out, C.byref(nl))
+    form = int(form)
+    rc = _hip.lib().alcm_debug_conv_plan(args if form == 1 else C.byref(args), n, form, ncu, out, C.byref(nl))
     return rc, _hip.lib().alcm_last_error().decode() if rc else ""
 
 
@@ -205,6 +212,136 @@ def test_ksplit_parts():
         assert p["grid"] == tiles * want
 
 
+# ------------------------------------------------------------------ the tail convs (alcm_opconv_dense)
+PLAN_KEYS = ("name", "inst", "block", "ncg", "tiles_per_batch", "tiles", "wslots", "flops", "bytes", "grid")
+
+
+def dense_call(B, T, Cc, prec, k, dil, epi):
+    """A dense_plans.json case as the row dict row_args takes: the models' arguments of an AMPBlock conv1 (epi 0:
+    Activation1d planes only), conv2 (1: + residual and fp32 state) or a resblock's last conv2 (2: residual into the
+    accumulated output, no activation)."""
+    kpad = (k * Cc + 31) // 32 * 32
+    d = dict(a=0, w=0, bias=0, B=B, T=T, C=Cc, Cp=(Cc + 31) // 32 * 32, N=Cc, ksize=k, dil=dil, pad=(k - 1) * dil // 2,
+             kpad=kpad, w_lo_off=Cc * kpad, prec=prec)
+    if epi < 2:
+        d.update(act_plane=0, act_alpha_exp=0, act_inv_beta=0, act_up_filter=0, act_down_filter=0,
+                 act_plane_lo_off=B * T * d["Cp"])
+    if epi > 0:
+        d.update(res=0, out=0)
+    if epi == 2:
+        d.update(accumulate=1)
+    return d
+
+
+def load_dense_table():
+    with open(DENSE_TABLE) as f:
+        return json.load(f)
+
+
+def dense_expected(t, case, tk, ncu, shapes=False):
+    """The recorded plan of a table case under ALCM_TCONV = tk on ncu compute units, keyed as PLAN_KEYS."""
+    B, T, Cc, prec, k, dil, epi, flops, nbytes, per_tk = case
+    name, inst, block, ncg, tpb, ntiles, wslots, *grids = per_tk[t["tks"].index(tk)]
+    return dict(name=t["names"][name] + (f" T{T} k{k}" if shapes else ""), inst=t["insts"][inst], block=block, ncg=ncg,
+                tiles_per_batch=tpb, tiles=ntiles, wslots=wslots, flops=float(flops), bytes=float(nbytes),
+                grid=grids[t["ncus"].index(ncu)])
+
+
+def built_tail_instantiations():
+    """The template-ids the launcher can emit: its list of built tile configurations (alcm_tconv.hip, tc_pick) times
+    the three epilogue forms, spelled as ConvPlan::inst spells them."""
+    with open(os.path.join(REPO, "audiolcm_amd", "csrc", "alcm_tconv.hip")) as f:
+        src = f.read()
+    cfgs = re.findall(r"^\s*tc_match<(CK_TCONV2?), ([0-9, ]+)>,$", src, re.M)
+    out = set()
+    for fam, nums in cfgs:
+        Cc, NS, NPB, BM, R, KMAX, OCC, STG = (int(x) for x in nums.split(","))
+        for epi in ("true, false, false, false", "true, true, true, false", "false, true, false, true"):
+            if fam == "CK_TCONV2":
+                out.add(f"tconv2_kernel<{Cc}, {NS}, {NPB}, {BM}, {R}, {epi}, {OCC}, {STG}>")
+            else:
+                out.add(f"tconv_kernel<{Cc}, {NS}, {NPB}, {BM}, {R}, {KMAX}, {OCC}, {epi}>")
+    assert len(out) == 3 * len(cfgs)
+    return out
+
+
+def test_dense_table_reaches_every_instantiation():
+    """The recorded calls reach every instantiation the launcher is built with, and name no other."""
+    t = load_dense_table()
+    built = built_tail_instantiations()
+    assert len(built) == 51
+    used = {t["insts"][r[1]] for c in t["cases"] for r in c[9]}
+    assert used == built == set(t["insts"])
+    grids = [(c[0] * r[4] * r[3], r[7]) for c in t["cases"] for r in c[9]]  # (tiles, grid at the first ncu)
+    assert any(g == n for n, g in grids) and any(g < n for n, g in grids), "one workgroup per tile, and tile walkers"
+
+
+def test_dense_planner_reproduces_recorded_choices():
+    """Every recorded alcm_opconv_dense call gets the instantiation, launch geometry, kernel arguments (ncg,
+    tiles_per_batch, ntiles, wslots), cost and profile name the dispatch had before the planner, under every ALCM_TCONV
+    value and CU count, and every recorded rejection keeps its code and message."""
+    t = load_dense_table()
+    assert len(t["cases"]) >= 375 and len(t["rejects"]) >= 80
+    bad, checked = [], 0
+    for tk in t["tks"]:
+        for shapes in (False, True):
+            with knobs(tconv=tk, prof_shapes=int(shapes)):
+                for c in t["cases"]:
+                    a = row_args(dense_call(*c[:7]))
+                    for ncu in t["ncus"]:
+                        p, = K.conv_plan(a, ncu, dense=True)
+                        want = dense_expected(t, c, tk, ncu, shapes)
+                        checked += 1
+                        if {k: p[k] for k in PLAN_KEYS} != want or p["kernel"] != want["inst"].split("_")[0]:
+                            bad.append((tk, ncu, c[:7], want, p))
+    with knobs(tconv=0):
+        for c in t["cases"]:
+            checked += 1
+            if plan_rc(row_args(dense_call(*c[:7])), 1, 2, 256) != (E_INVALID, t["off_error"]):
+                bad.append((0, c[:7]))
+    for r in t["rejects"]:
+        with knobs(**r["knobs"]):
+            checked += 1
+            got = plan_rc(row_args(r["args"]), 1, 2, r["ncu"])
+            if got != (r["rc"], r["error"]):
+                bad.append((r["what"], r["knobs"], got, r["error"]))
+    assert not bad, f"{len(bad)} of {checked} differ, first: {bad[0]}"
+    assert checked == len(t["cases"]) * (len(t["tks"]) * 2 * len(t["ncus"]) + 1) + len(t["rejects"])
+
+
+def _out_is_res(d):
+    d["out_is_res"] = 1
+
+
+DENSE_DEFECTS = {  # what the dispatch used to let through: (spoil the row dict, form it applies to, message)
+    "act, out == res": (_out_is_res, 1, "tconv: fused activation: out aliases res"),
+    "act_plane & 3": (lambda d: d.update(act_plane=2), 0, "tconv: act_plane alignment"),
+    "out_plane set": (lambda d: d.update(out_plane=0), 2, "tconv: no plane output"),
+    "B = 0": (lambda d: d.update(B=0), 1, "opconv_dense: bad arguments"),
+    "T < 0": (lambda d: d.update(T=-5), 0, "opconv_dense: bad arguments"),
+}
+
+
+@pytest.mark.parametrize("defect", sorted(DENSE_DEFECTS))
+def test_dense_plan_rejects_what_the_dispatch_let_through(defect):
+    """alcm_opconv_dense, from the C entry and from the models alike (one front door), refuses before any launch: a
+    fused-activation call whose out is its res (tiles recompute halo rows: alcm_opconv refuses it too), a misaligned
+    act_plane, an out_plane (there is no such epilogue; it used to be ignored), and B <= 0 / T <= 0 (the internal path
+    did not check).  The same arguments without the defect plan."""
+    spoil, epi, msg = DENSE_DEFECTS[defect]
+    for Cc, prec, k in ((96, 2, 3), (48, 3, 7), (24, 3, 11)):
+        d = dense_call(2, 300, Cc, prec, k, 1, epi)
+        p, = K.conv_plan(row_args(d), 256, dense=True)
+        assert p["kernel"] in ("tconv", "tconv2") and p["grid"] > 0 and p["block"] > 0
+        spoil(d)
+        assert plan_rc(row_args(d), 1, 2, 256) == (E_INVALID, msg), (defect, Cc)
+    # (only the fused activation is refused: without it the call plans as it always did)
+    if defect == "act, out == res":
+        d = dense_call(2, 300, 48, 3, 7, 1, 2)
+        _out_is_res(d)
+        assert K.conv_plan(row_args(d), 256, dense=True)[0]["inst"].endswith("false, true, false, true>")
+
+
 # ------------------------------------------------------------------ GPU: a real call records the planned row
 def _conv_args(B, T, Cc, N, k, dil, prec, seed, out_plane=False, ws=False):
     import torch
@@ -242,6 +379,11 @@ FAMILIES = {  # kernel family: (switches, [(B, T, C, N, k, dil, prec)], out_plan
     "nconv": ({}, [(2, 300, 24, 24, 3, 1, 2)], False, False),
     "opconv_kernel": ({}, [(2, 300, 48, 48, 7, 3, 1)], False, False),
 }
+TAIL_FAMILIES = {  # the tail convs through alcm_opconv_dense: (C, k, prec, epilogue form as dense_call) at B = 2, T = 300
+    "tconv2_c96_persistent": (96, 3, 2, 0),
+    "tconv_c48_resident": (48, 7, 3, 1),
+    "tconv2_c24_per_tile": (24, 11, 3, 2),
+}
 
 
 @pytest.mark.gpu
@@ -269,3 +411,50 @@ def test_profile_row_is_the_planned_one(family):
         torch.cuda.synchronize()
         rows = _hip.profile_end()
     assert [(r["name"], r["launches"]) for r in rows] == [(plans[0]["name"], 1)], (rows, plans)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family", sorted(TAIL_FAMILIES))
+def test_tail_profile_row_is_the_planned_one(family):
+    """One alcm_opconv_dense launch per tail family, on K.opconv(..., dense=True)'s packing: the recorded profile row is
+    the plan's, and the plan is the recorded table's for this device's CU count (the kernels' numerics are
+    test_gpu_ops.py's; what could go wrong here is the launcher taking another instantiation or grid than planned)."""
+    import torch
+    from audiolcm_amd.recipe import kaiser_sinc_filter1d
+    _hip.require_device(0)
+    Cc, k, prec, epi = TAIL_FAMILIES[family]
+    B, T = 2, 300
+    g = torch.Generator().manual_seed(400 + Cc)
+    planes = K.operand_planes((torch.randn((B, T, Cc), generator=g) * 0.5).cuda(), prec)
+    packed = K.pack_conv_weight((torch.randn((Cc, Cc, k), generator=g) / np.sqrt(Cc * k)).cuda())  # cpad = C: dense K
+    bias = (torch.randn((Cc,), generator=g) * 0.05).cuda()
+    res, out = torch.randn((B, T, Cc), generator=g).cuda(), torch.zeros((B, T, Cc), device="cuda")
+    ae, ib = K.snake_params((torch.randn((Cc,), generator=g) * 0.3).cuda(), (torch.randn((Cc,), generator=g) * 0.3).cuda())
+    ae, ib = ae.contiguous(), ib.contiguous()
+    f = kaiser_sinc_filter1d(0.25, 0.3, 12).reshape(-1).float().cpu().contiguous()
+    y = torch.zeros((1, B, T, (Cc + 31) // 32 * 32), dtype=torch.int16, device="cuda")
+    a = _hip.OpConvArgs()
+    a.a, a.B, a.T, a.C, a.Cp = _hip.ptr(planes), B, T, Cc, planes.shape[3]
+    a.ksize, a.dil, a.pad = k, 1, (k - 1) // 2
+    a.w, a.w_lo_off, a.kpad, a.N = _hip.ptr(packed.data), packed.lo_off, packed.kpad, Cc
+    a.bias, a.out_scale, a.prec = _hip.ptr(bias), 1.0, prec
+    if epi < 2:
+        a.act_plane, a.act_alpha_exp, a.act_inv_beta = _hip.ptr(y), _hip.ptr(ae), _hip.ptr(ib)
+        a.act_up_filter = a.act_down_filter = f.data_ptr()
+    if epi > 0:
+        a.res, a.out = _hip.ptr(res), _hip.ptr(out)
+    if epi == 2:
+        a.accumulate = 1
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    t = load_dense_table()
+    assert ncu in t["ncus"], f"the table holds no grids for {ncu} compute units"
+    case, = [c for c in t["cases"] if c[:7] == [B, T, Cc, prec, k, 1, epi]]
+    plan, = K.conv_plan(a, dense=True)
+    assert plan["ncu"] == ncu and family.startswith(plan["kernel"] + "_")
+    assert {key: plan[key] for key in PLAN_KEYS} == dense_expected(t, case, 1, ncu)
+    _hip.profile_begin()
+    _hip.check(_hip.lib().alcm_opconv_dense(C.byref(a), _hip.stream_handle()), "opconv_dense")
+    torch.cuda.synchronize()
+    rows = _hip.profile_end()
+    assert [(r["name"], r["launches"], r["flops"], r["bytes"]) for r in rows] == \
+        [(plan["name"], 1, plan["flops"], plan["bytes"])], (rows, plan)

@@ -98,6 +98,10 @@ _SIGS = [
     ("alcm_layer_norm_plane", C.c_int, [fp, C.c_int, C.c_int, i64, C.c_float, fp, fp, vp, C.c_int, vp]),
     ("alcm_lcm_step", C.c_int, [fp, fp, fp, C.POINTER(C.c_float), fp, fp, i64, vp]),
     ("alcm_lcm_step_cfg", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), fp, fp, i64, vp]),
+    ("alcm_lcm_step_edit", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), fp, fp, fp, fp, C.c_int, C.c_int,
+                                     C.c_int, vp]),
+    ("alcm_latent_init", C.c_int, [fp, fp, fp, C.c_float, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp,
+                                   C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_sincos_embedding", C.c_int, [fp, C.c_float, fp, C.c_int, C.c_int, C.c_int, fp, vp]),
     ("alcm_model_create", C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(NamedTensor), C.c_int, C.c_int,
                                     C.POINTER(vp)]),

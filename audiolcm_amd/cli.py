@@ -10,13 +10,17 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
     them (the reference passes the raw string to ``gen_test_sample``, which fails on ``prompt.items()``);
   * the unused unconditional embedding (``uc``, computed when ``--scale != 1`` and never passed to the LCM
     sampler, :90-92) is skipped;
-  * ``--plms`` (teacher sampler, out of the hot-path scope and broken for LCM_audio, plms.py:185) and
-    ``--inpaint`` raise;
+  * ``--plms`` (teacher sampler, out of the hot-path scope and broken for LCM_audio, plms.py:185) raises;
+  * ``--inpaint`` (parsed and never read by the reference) is text-guided inpainting of ``--init-audio PATH`` on the
+    spans of ``--mask-spans "2.0-4.5,7-8"`` (seconds); without both it raises.  ``--init-audio`` alone is a variation
+    of that clip at ``--strength F``; ``--duration SECONDS`` generates long-form clips by windowed continuation
+    (DESIGN.md §5);
   * ``--synthetic-seed N`` runs on the seeded recipe weights (no checkpoints offline).
 """
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 from typing import Dict, List, Optional, Sequence
@@ -25,7 +29,8 @@ import numpy as np
 import torch
 
 from .config import instantiate_from_config, load_config
-from .infer_api import load_model_from_config, struct_caption
+from .infer_api import (FRAME_SAMPLES, SAMPLE_RATE, load_init_audio, load_model_from_config, parse_spans,
+                        spans_to_mask, struct_caption)
 from .lcm import LCMSampler
 from .models import VocoderBigVGAN
 from .wavio import write_pcm16
@@ -56,6 +61,14 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--seed", type=int, default=0, help="per-clip RNG seeds: seed + (prompt * n_iter + iteration) * n_samples + sample")
     p.add_argument("--precision", choices=["split", "mixed", "bf16"], default="mixed",
                    help="MFMA precision policy (DESIGN.md §3)")
+    p.add_argument("--init-audio", type=str, default=None,
+                   help="16 kHz mono PCM16 WAV every prompt starts from: a variation, or with --inpaint an inpainting")
+    p.add_argument("--strength", type=float, default=0.5,
+                   help="with --init-audio: how far the clip is noised before sampling, in (0, 1]")
+    p.add_argument("--mask-spans", type=str, default=None,
+                   help='with --inpaint: the time spans to regenerate, in seconds, e.g. "2.0-4.5,7-8"')
+    p.add_argument("--duration", type=float, default=None,
+                   help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--test-dataset-tsv", type=str, default=None, help="override the config's test_dataset tsv_path")
     return p.parse_args(argv)
 
@@ -70,6 +83,37 @@ class GenSamples:
         self.save_mel, self.save_wav = save_mel, save_wav
         self.channel_dim = model.channels
         self.original_inference_steps = original_inference_steps
+        self.init_wav = None
+        if opt.init_audio:
+            self.init_wav = load_init_audio(opt.init_audio, model.unet.diffusion_model.cfg.max_latent_len)
+
+    def generate(self, c, seeds):
+        """Conditioning (B, ...) and per-clip seeds -> (mel, waveform (B, 1, L) or None)."""
+        B = c.shape[0]
+        kw = dict(guidance_scale=self.opt.scale, original_inference_steps=self.original_inference_steps)
+        if self.opt.duration is not None:
+            from .pipeline import AudioLCMPipeline
+            pipe = AudioLCMPipeline(self.model, self.vocoder.generator, steps=self.opt.ddim_steps,
+                                    latent_shape=(self.opt.H, self.opt.W), **kw)
+            out = pipe.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES))
+            return out["mel"], out["wav"].unsqueeze(1)
+        if self.init_wav is not None:
+            from .mel import MelNet
+            from .models import DiagonalGaussianDistribution
+            post = self.model.encode_first_stage(MelNet()(self.init_wav))
+            T = post.mean.shape[2]
+            mask = None
+            if self.opt.inpaint:
+                mask = torch.from_numpy(spans_to_mask(parse_spans(self.opt.mask_spans), T)).expand(B, T)
+            init = DiagonalGaussianDistribution(post.parameters.expand(B, -1, -1).contiguous())
+            z, _ = self.sampler.sample_edit(S=self.opt.ddim_steps, conditioning=c, init=init, mask=mask,
+                                            strength=self.opt.strength, seeds=seeds, **kw)
+        else:
+            shape = [self.channel_dim, self.opt.H, self.opt.W] if self.channel_dim > 0 else [self.opt.H, self.opt.W]
+            z, _ = self.sampler.sample(S=self.opt.ddim_steps, conditioning=c, batch_size=B, shape=shape,
+                                       verbose=False, seeds=seeds, **kw)
+        mel = self.model.decode_first_stage(z)
+        return mel, self.vocoder.vocode(mel) if self.save_wav else None
 
     def clip_seed(self, prompt_index: int, it: int, j: int) -> int:
         """RNG seed of sample j of iteration `it` of the prompt at global index `prompt_index` (batch-invariant)."""
@@ -86,12 +130,8 @@ class GenSamples:
             c = self.model.get_learned_conditioning(text)
             B = c.shape[0]
             seeds = [self.clip_seed(first_index + i, it, j) for i in range(len(prompts)) for j in range(n)]
-            shape = [self.channel_dim, self.opt.H, self.opt.W] if self.channel_dim > 0 else [self.opt.H, self.opt.W]
-            z, _ = self.sampler.sample(S=self.opt.ddim_steps, conditioning=c, batch_size=B, shape=shape,
-                                       verbose=False, guidance_scale=self.opt.scale,
-                                       original_inference_steps=self.original_inference_steps, seeds=seeds)
-            mel = self.model.decode_first_stage(z)
-            wav = self.vocoder.vocode(mel).squeeze(1).cpu().numpy() if self.save_wav else None
+            mel, wav = self.generate(c, seeds)
+            wav = wav.squeeze(1).cpu().numpy() if self.save_wav else None
             mel_np = mel.cpu().numpy()
             for i in range(len(prompts)):
                 for j in range(n):
@@ -114,12 +154,18 @@ def build(opt):
     if opt.plms:
         raise NotImplementedError("--plms: the teacher PLMS sampler is outside the LCM hot path (and calls the 3-arg "
                                   "apply_model, plms.py:185, which LCM_audio does not have)")
-    if opt.inpaint:
-        raise NotImplementedError("--inpaint is not part of the text-to-audio path")
+    if opt.inpaint and not (opt.init_audio and opt.mask_spans):
+        raise NotImplementedError("--inpaint needs --init-audio PATH and --mask-spans: the clip to inpaint and the "
+                                  "time spans to regenerate")
+    if opt.mask_spans and not opt.inpaint:
+        raise ValueError("--mask-spans is used with --inpaint")
+    if opt.init_audio and opt.duration is not None:
+        raise ValueError("--init-audio and --duration do not combine")
     config = load_config(opt.base)
     split = {"split": True, "bf16": "bf16", "mixed": "mixed"}[opt.precision]
     if opt.synthetic_seed is not None:
-        model = load_model_from_config(config, None, split=split, synthetic_seed=opt.synthetic_seed)
+        model = load_model_from_config(config, None, split=split, synthetic_seed=opt.synthetic_seed,
+                                       encoder=bool(opt.init_audio))
         from . import recipe
         vocoder = VocoderBigVGAN(state=recipe.bigvgan_state(opt.synthetic_seed), split=split)
     else:

@@ -46,6 +46,12 @@ int activation1d(const float* x, float* y, int B, int T, int C, int64_t sb, int6
                  const float* inv_beta, const float* up_filter, const float* down_filter, hipStream_t s);
 int lcm_step(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
              const float* coeffs, float* prev, float* den, int64_t n, hipStream_t s);
+int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                  const float* coeffs, const float* z0, const float* mask, float* prev, float* den, int B, int C, int T,
+                  hipStream_t s);
+int latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
+                const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
+                int C, int T, hipStream_t s);
 int fill_f32(float* p, int64_t n, float v, hipStream_t s);
 int nct_to_cl(const float* x, int B, int C, int T, int Cp, float* y, hipStream_t s);
 // fp32 rows [rows][C] -> operand planes [rows][Cp] in the format of `prec` (SPLIT: lo plane rows * Cp after hi)

@@ -417,20 +417,29 @@ int activation1d(const float* x, float* y, int B, int T, int C, int64_t sb, int6
 struct StepCoeffs {
   float sqrt_a, sqrt_b, c_out, c_skip, sqrt_a_prev, sqrt_b_prev;
 };
+// The per-element step, shared by lcm_step_kernel and lcm_step_edit_kernel: the denoised estimate of one element
+// (has_u: eu is the unconditional eps of the classifier-free guidance combine, plms.py:184-186: e_u + s * (e_c - e_u))
+// and the re-noised previous sample of a denoised value.  The roundings are spelled out (which products fuse into an
+// fma and which are rounded on their own), so that every kernel that inlines these computes the same bits and the
+// compiler's contraction choices in the surrounding code cannot change them.
+__device__ __forceinline__ float lcm_denoise(float xi, float e, bool has_u, float eu, float cfg, const StepCoeffs& k) {
+  if (has_u) e = fmaf(cfg, e - eu, eu);
+  const float x0 = fmaf(-k.sqrt_b, e, xi) / k.sqrt_a;
+  return fmaf(k.c_skip, xi, k.c_out * x0);
+}
+__device__ __forceinline__ float lcm_renoise(float d, float nz, const StepCoeffs& k) {
+#pragma clang fp contract(off)
+  const float a = k.sqrt_a_prev * d, b = k.sqrt_b_prev * nz;
+  return a + b;
+}
+
 __global__ void lcm_step_kernel(const float* __restrict__ x, const float* __restrict__ eps,
                                 const float* __restrict__ eps_u, float cfg, const float* __restrict__ noise,
                                 StepCoeffs k, float* prev, float* den, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float xi = x[i];
-    float e = eps[i];
-    if (eps_u) {  // classifier-free guidance combine, plms.py:184-186: e_u + s * (e_c - e_u)
-      const float eu = eps_u[i];
-      e = eu + cfg * (e - eu);
-    }
-    const float x0 = (xi - k.sqrt_b * e) / k.sqrt_a;
-    const float d = k.c_out * x0 + k.c_skip * xi;
+    const float d = lcm_denoise(x[i], eps[i], eps_u != nullptr, eps_u ? eps_u[i] : 0.f, cfg, k);
     if (den) den[i] = d;
-    if (prev) prev[i] = noise ? k.sqrt_a_prev * d + k.sqrt_b_prev * noise[i] : d;
+    if (prev) prev[i] = noise ? lcm_renoise(d, noise[i], k) : d;
   }
 }
 
@@ -440,7 +449,201 @@ int lcm_step(const float* x, const float* eps, const float* eps_u, float cfg, co
   if (n == 0) return 0;
   StepCoeffs k{c[0], c[1], c[2], c[3], c[4], c[5]};
   const int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  void* tok = prof_start(s);
   hipLaunchKernelGGL(lcm_step_kernel, dim3(blocks), dim3(256), 0, s, x, eps, eps_u, cfg, noise, k, prev, den, n);
+  // per element: x, eps (+ eps_u, + noise) in, prev and den out
+  prof_stop(tok, s, "alcm::lcm_step_kernel", 8.0 * n,
+            4.0 * n * (2 + (eps_u ? 1 : 0) + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0)));
+  ALCM_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------- LCM edit step and its starting point
+// Latents are (B, C, T) and the mask (B, T): one work item is V consecutive frames of one clip (V = 4 with 16-byte
+// accesses when T and the pointers allow, else 1) in kEditCh consecutive channel rows: the item reads the mask of its
+// frames once and reuses it for its channels, whose loads are all in flight together.  Items (frames fastest, then
+// channel groups, then clips) are spread over the grid with a grid-stride loop.
+constexpr int kEditCh = 4;
+constexpr int kEditBlock = 64;     // small blocks: the configured shapes have a few thousand items
+constexpr int kEditMaxBlocks = 1024;
+
+struct EditItem {
+  int64_t b;
+  int c0, t;
+};
+template <int V>
+__device__ __forceinline__ EditItem edit_item(int64_t it, int C, int T) {
+  const int TV = T / V, CG = (C + kEditCh - 1) / kEditCh;
+  const int64_t row = it / TV;  // (b, channel group)
+  const int64_t b = row / CG;
+  return EditItem{b, (int)(row - b * CG) * kEditCh, (int)(it - row * TV) * V};
+}
+
+template <int V>
+struct FVec;
+template <>
+struct FVec<1> {
+  float v[1];
+  __device__ static FVec ld(const float* p) { return FVec{{*p}}; }
+  __device__ void st(float* p) const { *p = v[0]; }
+};
+template <>
+struct FVec<4> {
+  float v[4];
+  __device__ static FVec ld(const float* p) {
+    const float4 f = *reinterpret_cast<const float4*>(p);
+    return FVec{{f.x, f.y, f.z, f.w}};
+  }
+  __device__ void st(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+};
+
+// m = 1 keeps the step's own value and m = 0 the known one, both bit for bit; in between the blend.
+__device__ __forceinline__ float mask_blend(float m, float regen, float keep) {
+  return m == 1.f ? regen : m == 0.f ? keep : m * regen + (1.f - m) * keep;
+}
+
+template <int V>
+__global__ __launch_bounds__(kEditBlock) void lcm_step_edit_kernel(
+    const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg,
+    const float* __restrict__ noise, StepCoeffs k, const float* __restrict__ z0, const float* __restrict__ mask,
+    float* __restrict__ prev, float* __restrict__ den, int C, int T, int64_t items) {
+  for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+    const EditItem w = edit_item<V>(it, C, T);
+    const FVec<V> m = FVec<V>::ld(mask + w.b * T + w.t);
+    const int64_t o0 = (w.b * C + w.c0) * T + w.t;
+#pragma unroll
+    for (int j = 0; j < kEditCh; ++j) {
+      if (w.c0 + j >= C) break;
+      const int64_t o = o0 + (int64_t)j * T;
+      const FVec<V> xv = FVec<V>::ld(x + o), ev = FVec<V>::ld(eps + o), zv = FVec<V>::ld(z0 + o);
+      FVec<V> uv = xv, nv = xv, dv, pv;
+      if (eps_u) uv = FVec<V>::ld(eps_u + o);
+      if (noise) nv = FVec<V>::ld(noise + o);
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const float d = lcm_denoise(xv.v[i], ev.v[i], eps_u != nullptr, uv.v[i], cfg, k);
+        dv.v[i] = mask_blend(m.v[i], d, zv.v[i]);
+        pv.v[i] = noise ? lcm_renoise(dv.v[i], nv.v[i], k) : dv.v[i];
+      }
+      if (den) dv.st(den + o);
+      if (prev) pv.st(prev + o);
+    }
+  }
+}
+
+static bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if ((uintptr_t)p & 15) return false;  // NULL counts as aligned
+  return true;
+}
+static int64_t edit_items(int B, int C, int T, bool vec) {
+  return (int64_t)B * ((C + kEditCh - 1) / kEditCh) * (vec ? T / 4 : T);
+}
+static int edit_blocks(int64_t items) {
+  return (int)std::min<int64_t>((items + kEditBlock - 1) / kEditBlock, kEditMaxBlocks);
+}
+
+int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
+                  const float* z0, const float* mask, float* prev, float* den, int B, int C, int T, hipStream_t s) {
+  if (!x || !eps || !c || !z0 || !mask || (!prev && !den))
+    return set_error(ALCM_E_INVALID, "lcm_step_edit: null x, eps, coeffs, z0 or mask, or no output");
+  if (B < 0 || C < 0 || T < 0) return set_error(ALCM_E_INVALID, "lcm_step_edit: negative B, C or T");
+  if (B == 0 || C == 0 || T == 0) return 0;
+  StepCoeffs k{c[0], c[1], c[2], c[3], c[4], c[5]};
+  const bool vec = T % 4 == 0 && aligned16({x, eps, eps_u, noise, z0, mask, prev, den});
+  const int64_t items = edit_items(B, C, T, vec);
+  void* tok = prof_start(s);
+  if (vec)
+    hipLaunchKernelGGL(lcm_step_edit_kernel<4>, dim3(edit_blocks(items)), dim3(kEditBlock), 0, s, x, eps, eps_u, cfg,
+                       noise, k, z0, mask, prev, den, C, T, items);
+  else
+    hipLaunchKernelGGL(lcm_step_edit_kernel<1>, dim3(edit_blocks(items)), dim3(kEditBlock), 0, s, x, eps, eps_u, cfg,
+                       noise, k, z0, mask, prev, den, C, T, items);
+  // per element: x, eps, z0 (+ eps_u, + noise) in, prev and den out; the mask once per frame and channel group
+  const double n = (double)B * C * T;
+  prof_stop(tok, s, vec ? "alcm::lcm_step_edit_kernel<4>" : "alcm::lcm_step_edit_kernel<1>", 12.0 * n,
+            4.0 * n * (3 + (eps_u ? 1 : 0) + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0)) +
+                4.0 * B * T * ((C + kEditCh - 1) / kEditCh));
+  ALCM_HIP(hipGetLastError());
+  return 0;
+}
+
+// z0 = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0) from the encoder's (B, 2C, T) moments (the posterior mode
+// scale * mean without e0; lcm_audio.py:197-204, distributions.py:24-44), or a given z0; x = the sampler's start
+// sa * z0 + sb * n0 on kept frames (m = 0), sa_r * z0 + sb_r * n0 on regenerated ones (m = 1).
+template <int V>
+__global__ __launch_bounds__(kEditBlock) void latent_init_kernel(
+    const float* __restrict__ moments, const float* __restrict__ z0_in, const float* __restrict__ e0, float scale,
+    const float* __restrict__ noise, const float* __restrict__ mask, float sa, float sb, float sa_r, float sb_r,
+    float* __restrict__ z0_out, float* __restrict__ x_out, int C, int T, int64_t items) {
+  for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+    const EditItem w = edit_item<V>(it, C, T);
+    FVec<V> m = {};
+    if (mask) m = FVec<V>::ld(mask + w.b * T + w.t);
+    const int64_t o0 = (w.b * C + w.c0) * T + w.t;        // latent element (b, c0, t)
+    const int64_t om0 = (2 * w.b * C + w.c0) * T + w.t;   // its mean; the logvar is C rows further
+#pragma unroll
+    for (int j = 0; j < kEditCh; ++j) {
+      if (w.c0 + j >= C) break;
+      const int64_t o = o0 + (int64_t)j * T, om = om0 + (int64_t)j * T;
+      FVec<V> z;
+      if (z0_in) {
+        z = FVec<V>::ld(z0_in + o);
+      } else {
+        z = FVec<V>::ld(moments + om);
+        if (e0) {
+          const FVec<V> lv = FVec<V>::ld(moments + om + (int64_t)C * T), ev = FVec<V>::ld(e0 + o);
+#pragma unroll
+          for (int i = 0; i < V; ++i)
+            z.v[i] = scale * (z.v[i] + expf(0.5f * fminf(fmaxf(lv.v[i], -30.f), 20.f)) * ev.v[i]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < V; ++i) z.v[i] = scale * z.v[i];
+        }
+      }
+      if (z0_out) z.st(z0_out + o);
+      if (x_out) {
+        const FVec<V> nv = FVec<V>::ld(noise + o);
+        FVec<V> xv;
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          const float keep = sa * z.v[i] + sb * nv.v[i];
+          if (mask) {
+            const float regen = sa_r * z.v[i] + sb_r * nv.v[i];
+            xv.v[i] = m.v[i] * regen + (1.f - m.v[i]) * keep;
+          } else {
+            xv.v[i] = keep;
+          }
+        }
+        xv.st(x_out + o);
+      }
+    }
+  }
+}
+
+int latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
+                const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
+                int C, int T, hipStream_t s) {
+  if ((moments != nullptr) == (z0_in != nullptr))
+    return set_error(ALCM_E_INVALID, "latent_init: pass exactly one of moments and z0_in");
+  if (!z0_out && !x_out) return set_error(ALCM_E_INVALID, "latent_init: no output");
+  if (x_out && !noise) return set_error(ALCM_E_INVALID, "latent_init: x_out needs noise");
+  if (B < 0 || C < 0 || T < 0) return set_error(ALCM_E_INVALID, "latent_init: negative B, C or T");
+  if (B == 0 || C == 0 || T == 0) return 0;
+  if (z0_in) e0 = nullptr;
+  const bool vec = T % 4 == 0 && aligned16({moments, z0_in, e0, noise, mask, z0_out, x_out});
+  const int64_t items = edit_items(B, C, T, vec);
+  void* tok = prof_start(s);
+  if (vec)
+    hipLaunchKernelGGL(latent_init_kernel<4>, dim3(edit_blocks(items)), dim3(kEditBlock), 0, s, moments, z0_in, e0,
+                       scale, noise, mask, sa, sb, sa_r, sb_r, z0_out, x_out, C, T, items);
+  else
+    hipLaunchKernelGGL(latent_init_kernel<1>, dim3(edit_blocks(items)), dim3(kEditBlock), 0, s, moments, z0_in, e0,
+                       scale, noise, mask, sa, sb, sa_r, sb_r, z0_out, x_out, C, T, items);
+  const double n = (double)B * C * T;
+  prof_stop(tok, s, vec ? "alcm::latent_init_kernel<4>" : "alcm::latent_init_kernel<1>", 10.0 * n,
+            4.0 * n * (1 + (e0 ? 2 : 0) + (x_out ? 2 : 0) + (z0_out ? 1 : 0)) +
+                (mask ? 4.0 * B * T * ((C + kEditCh - 1) / kEditCh) : 0.0));
   ALCM_HIP(hipGetLastError());
   return 0;
 }
@@ -558,6 +761,18 @@ extern "C" int alcm_lcm_step_cfg(const float* x, const float* eps_cond, const fl
   if (!eps_uncond) return alcm::set_error(ALCM_E_INVALID, "lcm_step_cfg: null eps_uncond");
   return alcm::lcm_step(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, prev_out, denoised_out, n,
                         (hipStream_t)stream);
+}
+extern "C" int alcm_lcm_step_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                                  const float* noise, const float* coeffs, const float* z0, const float* mask,
+                                  float* prev_out, float* denoised_out, int B, int C, int T, alcm_stream_t stream) {
+  return alcm::lcm_step_edit(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, z0, mask, prev_out, denoised_out, B, C,
+                             T, (hipStream_t)stream);
+}
+extern "C" int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, float scale,
+                                const float* noise, const float* mask, float sa, float sb, float sa_r, float sb_r,
+                                float* z0_out, float* x_out, int B, int C, int T, alcm_stream_t stream) {
+  return alcm::latent_init(moments, z0_in, e0, scale, noise, mask, sa, sb, sa_r, sb_r, z0_out, x_out, B, C, T,
+                           (hipStream_t)stream);
 }
 extern "C" int alcm_sincos_embedding(const float* v, float vscale, const float* freqs, int B, int half,
                                      int cos_first, float* out, alcm_stream_t stream) {

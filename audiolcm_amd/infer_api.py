@@ -10,7 +10,8 @@ placeholders for a Lightning checkpoint's non-tensor objects; yaml.safe_load).
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -20,18 +21,19 @@ from .ckpt import load_checkpoint, state_dict_of
 from .config import instantiate_from_config, load_config
 from .lcm import LCM_audio, LCMSampler
 from .models import BigVGAN, VocoderBigVGAN
-from .wavio import write_pcm16
+from .wavio import read_wav, write_pcm16
 
 
 def load_model_from_config(config, ckpt: Optional[str] = None, verbose: bool = True, split: bool = True,
-                           synthetic_seed: Optional[int] = None) -> LCM_audio:
-    """InferAPI.py:26-45: instantiate LCM_audio and load the Lightning ``state_dict``."""
+                           synthetic_seed: Optional[int] = None, encoder: bool = False) -> LCM_audio:
+    """InferAPI.py:26-45: instantiate LCM_audio and load the Lightning ``state_dict`` (``encoder``: the synthetic
+    weights include the VAE encoder; a checkpoint's ``first_stage_model.encoder.*`` is always loaded)."""
     model = instantiate_from_config(config.model, split=split)
     if ckpt:
         print(f"Loading model from {ckpt}")
         model.load_state_dict(state_dict_of(load_checkpoint(ckpt)), strict=False)
     elif synthetic_seed is not None:
-        model.load_recipe(synthetic_seed)
+        model.load_recipe(synthetic_seed, encoder=encoder)
     else:
         print("Note chat no ckpt is loaded !!!")
     return model
@@ -88,7 +90,7 @@ class GenSamples:
         return self.gen_batch([prompt], [name])
 
 
-def _build(config_path, model_path, vocoder_path, synthetic_seed, split, synthetic_tokenizer=False):
+def _build(config_path, model_path, vocoder_path, synthetic_seed, split, synthetic_tokenizer=False, encoder=False):
     config = load_config(config_path)
     if synthetic_seed is None:
         if not model_path or not os.path.exists(model_path):
@@ -101,7 +103,7 @@ def _build(config_path, model_path, vocoder_path, synthetic_seed, split, synthet
             model.cond_stage_model.use_synthetic_tokenizer()
         vocoder = VocoderBigVGAN(vocoder_path, split=split)
     else:
-        model = load_model_from_config(config, None, split=split, synthetic_seed=synthetic_seed)
+        model = load_model_from_config(config, None, split=split, synthetic_seed=synthetic_seed, encoder=encoder)
         vocoder = VocoderBigVGAN(state=recipe.bigvgan_state(synthetic_seed), h=None, split=split)
     sampler = LCMSampler(model)
     steps_cfg = config.model.params.get("num_ddim_timesteps", 50)
@@ -139,3 +141,105 @@ def AudioLCMInfer(ori_prompt: str, config_path: str = "configs/audiolcm.yaml",
     """InferAPI.py:103-133."""
     return AudioLCMBatchInfer([ori_prompt], config_path, model_path, vocoder_path, 1, synthetic_seed, split, outpath,
                               seed)
+
+
+# ---------------------------------------------------------------------------- audio-conditioned generation
+SAMPLE_RATE = 16000
+FRAME_SAMPLES = 512  # one latent frame = 2 mel frames x hop 256
+
+
+def parse_spans(text: str) -> List[Tuple[float, float]]:
+    """``"2.0-4.5,7-8"`` -> [(2.0, 4.5), (7.0, 8.0)] (seconds)."""
+    spans = []
+    for part in text.split(","):
+        if not part.strip():
+            continue
+        try:
+            a, b = part.split("-")
+            spans.append((float(a), float(b)))
+        except ValueError:
+            raise ValueError(f"bad span {part!r}: expected START-END in seconds") from None
+    return spans
+
+
+def spans_to_mask(spans: Optional[Sequence[Tuple[float, float]]], n_frames: int, sample_rate: int = SAMPLE_RATE,
+                  frame_samples: int = FRAME_SAMPLES) -> np.ndarray:
+    """(n_frames,) float32 regenerate-mask of the time spans [t0, t1) in seconds: span -> latent frames
+    floor(sample_rate * t0 / frame_samples) up to (not including) ceil(sample_rate * t1 / frame_samples), so a span
+    ending mid-frame takes that frame too; clipped to the clip."""
+    mask = np.zeros((n_frames,), dtype=np.float32)
+    for t0, t1 in spans or ():
+        if t1 <= t0:
+            continue
+        lo = max(0, math.floor(sample_rate * t0 / frame_samples))
+        hi = min(n_frames, math.ceil(sample_rate * t1 / frame_samples))
+        mask[lo:hi] = 1.0
+    return mask
+
+
+def load_init_audio(path: str, max_frames: Optional[int] = None) -> np.ndarray:
+    """16 kHz mono PCM16 WAV -> float32 samples, zero-padded up to a whole number of latent frames (512 samples) and
+    cropped to ``max_frames`` of them (the DiT's length limit) when given.  Another sample rate raises ValueError."""
+    x, sr = read_wav(path)
+    if sr != SAMPLE_RATE:
+        raise ValueError(f"{path}: sample rate {sr}, need {SAMPLE_RATE} (resampling is not done here)")
+    if x.size == 0:
+        raise ValueError(f"{path}: no samples")
+    if max_frames is not None:
+        x = x[:max_frames * FRAME_SAMPLES]
+    return np.pad(x, (0, -x.size % FRAME_SAMPLES))
+
+
+def _seed_list(seed: Optional[int], n: int):
+    return None if seed is None else list(range(seed, seed + n))
+
+
+def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
+                      mask_spans: Optional[Sequence[Tuple[float, float]]] = None,
+                      config_path: str = "configs/audiolcm.yaml", model_path: str = "./model/000184.ckpt",
+                      vocoder_path: str = "./model/vocoder", synthetic_seed: Optional[int] = None, split: bool = True,
+                      outpath: str = "results/test", seed: Optional[int] = None) -> str:
+    """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength``, or, with ``mask_spans``
+    ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
+    clip is synthesised again from the latent.  Returns the WAV path (``<prompt-with-dashes>_0.wav``)."""
+    from .mel import MelNet
+    wav_in = load_init_audio(init_audio)  # a bad input fails before the models are built
+    model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
+                                                 encoder=True)
+    wav_in = wav_in[:model.unet.diffusion_model.cfg.max_latent_len * FRAME_SAMPLES]
+    os.makedirs(outpath, exist_ok=True)
+    with torch.no_grad():
+        c = model.get_learned_conditioning({"ori_caption": [ori_prompt], "struct_caption": [struct_caption(ori_prompt)]})
+        post = model.encode_first_stage(MelNet()(wav_in))
+        T = post.mean.shape[2]
+        mask = torch.from_numpy(spans_to_mask(mask_spans, T))[None] if mask_spans is not None else None
+        z, _ = sampler.sample_edit(S=2, conditioning=c, init=post, mask=mask, strength=strength,
+                                   seeds=_seed_list(seed, 1), original_inference_steps=orig_steps)
+        wav = vocoder.vocode(model.decode_first_stage(z)).squeeze(1).cpu().numpy()
+    path = os.path.join(outpath, wav_name_for(ori_prompt) + "_0.wav")
+    write_pcm16(path, wav[0], SAMPLE_RATE)
+    return path
+
+
+def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: str = "configs/audiolcm.yaml",
+                      model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
+                      synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
+                      seed: Optional[int] = None) -> str:
+    """A clip of ceil(duration_s * 16000 / 512) latent frames by long-form continuation
+    (``AudioLCMPipeline.generate_long``).  ``seed`` None draws the clip's base seed from the global RNG.  Returns the
+    WAV path."""
+    from .pipeline import AudioLCMPipeline
+    model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split)
+    latent_len = math.ceil(duration_s * SAMPLE_RATE / FRAME_SAMPLES)
+    if latent_len < 1:
+        raise ValueError("duration_s must be positive")
+    base = int(torch.randint(0, 2 ** 31 - 1, (1,))) if seed is None else seed
+    pipe = AudioLCMPipeline(model, vocoder.generator, steps=2, original_inference_steps=orig_steps,
+                            latent_shape=(model.mel_dim, model.mel_length))
+    os.makedirs(outpath, exist_ok=True)
+    with torch.no_grad():
+        c = model.get_learned_conditioning({"ori_caption": [ori_prompt], "struct_caption": [struct_caption(ori_prompt)]})
+        wav = pipe.generate_long(c, [base], latent_len)["wav"].cpu().numpy()
+    path = os.path.join(outpath, wav_name_for(ori_prompt) + "_0.wav")
+    write_pcm16(path, wav[0], SAMPLE_RATE)
+    return path

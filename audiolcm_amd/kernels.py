@@ -324,6 +324,39 @@ def lcm_step(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tensor], 
     return prev, den
 
 
+def lcm_step_edit(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tensor], coeffs, z0: torch.Tensor,
+                  mask: torch.Tensor, eps_uncond: Optional[torch.Tensor] = None,
+                  cfg_scale: float = 1.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``lcm_step`` (with the guidance combine when ``eps_uncond`` is given) on (B, C, T) latents, blended per frame with
+    the known latent ``z0``: mask (B, T) in [0, 1], 1 = take the step's value, 0 = keep z0.  Returns (prev, denoised)."""
+    B, Cc, T = x.shape
+    assert eps.shape == x.shape and z0.shape == x.shape and tuple(mask.shape) == (B, T)
+    prev = torch.empty_like(x)
+    den = torch.empty_like(x)
+    arr = (C.c_float * 6)(*[float(c) for c in coeffs])
+    check(lib().alcm_lcm_step_edit(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, ptr(z0),
+                                   ptr(mask), ptr(prev), ptr(den), B, Cc, T, stream_handle()), "lcm_step_edit")
+    return prev, den
+
+
+def latent_init(noise: Optional[torch.Tensor], keep=(1.0, 0.0), regen=(0.0, 1.0), moments: Optional[torch.Tensor] = None,
+                z0: Optional[torch.Tensor] = None, e0: Optional[torch.Tensor] = None, scale: float = 1.0,
+                mask: Optional[torch.Tensor] = None, want_z0: bool = True,
+                want_x: bool = True) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """Encoder moments (B, 2C, T) (with posterior noise ``e0``, None = the mode) or a given latent ``z0`` (B, C, T) ->
+    (z0, x): z0 = scale * posterior sample, x = the sampler's start sa * z0 + sb * noise with (sa, sb) = ``keep`` on
+    frames of mask 0 and ``regen`` on frames of mask 1 (mask None: ``keep`` everywhere).  One launch."""
+    src = moments if moments is not None else z0
+    B, T = src.shape[0], src.shape[2]
+    Cc = src.shape[1] // 2 if moments is not None else src.shape[1]
+    z0_out = torch.empty((B, Cc, T), device=src.device, dtype=torch.float32) if want_z0 else None
+    x_out = torch.empty((B, Cc, T), device=src.device, dtype=torch.float32) if want_x else None
+    check(lib().alcm_latent_init(ptr(moments), ptr(z0), ptr(e0), float(scale), ptr(noise), ptr(mask), float(keep[0]),
+                                 float(keep[1]), float(regen[0]), float(regen[1]), ptr(z0_out), ptr(x_out), B, Cc, T,
+                                 stream_handle()), "latent_init")
+    return z0_out, x_out
+
+
 def sincos_embedding(v: torch.Tensor, freqs: torch.Tensor, scale: float, cos_first: bool) -> torch.Tensor:
     B = v.shape[0]
     half = freqs.numel()

@@ -23,7 +23,7 @@ import torch
 from . import _hip, recipe, schedule
 from ._hip import check, lib, ptr, stream_handle
 from .config import instantiate_from_config
-from .models import AutoencoderKL, ConcatDiT2MLP
+from .models import AutoencoderKL, ConcatDiT2MLP, DiagonalGaussianDistribution
 
 
 class DiffusionWrapper:
@@ -78,9 +78,13 @@ class LCM_audio:
             self.scale_factor = float(sd["scale_factor"])
         return self
 
-    def load_recipe(self, seed: int = 0):
+    def load_recipe(self, seed: int = 0, encoder: bool = False):
+        """``encoder``: also load the VAE encoder (``recipe.vae_encoder_state``), which the audio-in paths need."""
         self.unet.diffusion_model.load_state_dict(recipe.dit_state(seed))
-        self.first_stage_model.load_state_dict(recipe.vae_state(seed))
+        vae = dict(recipe.vae_state(seed))
+        if encoder:
+            vae.update(recipe.vae_encoder_state(seed))
+        self.first_stage_model.load_state_dict(vae)
         if self.cond_stage_model is not None and hasattr(self.cond_stage_model, "load_state_dict"):
             self.cond_stage_model.load_state_dict(recipe.text_state(seed))
             if hasattr(self.cond_stage_model, "use_synthetic_tokenizer"):  # recipe weights: hash ids are as good
@@ -112,7 +116,6 @@ class LCM_audio:
 
     def get_first_stage_encoding(self, encoder_posterior, generator=None):
         """lcm_audio.py:197-204: scale_factor * posterior.sample() (a tensor passes through)."""
-        from .models import DiagonalGaussianDistribution
         if isinstance(encoder_posterior, DiagonalGaussianDistribution):
             z = encoder_posterior.sample(generator)
         elif isinstance(encoder_posterior, torch.Tensor):
@@ -229,6 +232,14 @@ class LCMSampler:
         if noise is None:
             noise = torch.randn((n_noise, batch_size, Cc, T), device=dev) if n_noise else None
         noise = noise.to(dev).float().contiguous() if noise is not None else None
+        return self._run(plan, img, noise, cond, batch_size, guidance_scale, unconditional_conditioning,
+                         unconditional_guidance_scale)
+
+    def _run(self, plan, img, noise, cond, batch_size, guidance_scale, unconditional_conditioning,
+             unconditional_guidance_scale, z0=None, mask=None):
+        """The step loop of ``sample`` and ``sample_edit``: img (B, C, T) at plan[0]'s noise level, noise[i] the noise of
+        step i.  With z0 / mask every step blends the denoised estimate with the known latent (alcm_lcm_step_edit)."""
+        dev = img.device
         dit: ConcatDiT2MLP = self.model.unet.diffusion_model
         cfg = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
         c = cond.to(dev).float()
@@ -248,8 +259,12 @@ class LCMSampler:
             eps = dit.forward_cached(xin, ts, cemb, w_emb)
             coeffs = (C.c_float * 6)(*p["coeffs"])
             nz = ptr(noise[i]) if p["add_noise"] else None
-            if cfg:
-                eu, ec = eps[:batch_size], eps[batch_size:]
+            eu, ec = (eps[:batch_size], eps[batch_size:]) if cfg else (None, eps)
+            if mask is not None:
+                check(lib().alcm_lcm_step_edit(ptr(img), ptr(ec), ptr(eu), float(unconditional_guidance_scale), nz,
+                                               coeffs, ptr(z0), ptr(mask), ptr(prev), ptr(denoised), *img.shape,
+                                               stream_handle()), "lcm_step_edit")
+            elif cfg:
                 check(lib().alcm_lcm_step_cfg(ptr(img), ptr(ec), ptr(eu), float(unconditional_guidance_scale), nz,
                                               coeffs, ptr(prev), ptr(denoised), n, stream_handle()), "lcm_step_cfg")
             else:
@@ -257,3 +272,84 @@ class LCMSampler:
                                           stream_handle()), "lcm_step")
             img, prev = prev, img
         return denoised, img
+
+    @torch.no_grad()
+    def sample_edit(self, S, conditioning, init, mask=None, strength: float = 1.0,
+                    seeds: Optional[Sequence[int]] = None, noise: Optional[torch.Tensor] = None,
+                    init_noise: Optional[torch.Tensor] = None, posterior_noise: Optional[torch.Tensor] = None,
+                    sample_posterior: bool = True, guidance_scale=5., original_inference_steps=50,
+                    unconditional_conditioning: Optional[torch.Tensor] = None,
+                    unconditional_guidance_scale: float = 1.0, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Audio-conditioned sampling: S LCM steps from a known latent instead of pure noise.
+
+        ``init``: the encoder's ``DiagonalGaussianDistribution`` (z0 = scale_factor * its sample with the noise e0, or
+        its mode with ``sample_posterior=False``) or a (B, C, T) latent z0 already scaled.  ``mask`` (B, T) in [0, 1]
+        or None (= 1 everywhere): frames of mask 1 are regenerated, frames of mask 0 keep z0 exactly (every step
+        blends its denoised estimate with z0 per frame).  ``strength`` in (0, 1] places the first timestep t0
+        (``schedule.sample_plan``).  Kept frames start from sqrt(ac[t0]) z0 + sqrt(1 - ac[t0]) n0; regenerated frames
+        too when strength < 1 (the input is a hint), and from pure n0 at strength 1 (the reference's x_T).
+
+        RNG: with ``seeds``, per prompt n0, the step noise and e0 from ``recipe.edit_noise``; ``init_noise``, ``noise``
+        and ``posterior_noise`` replace the respective draw; without seeds the global device RNG.
+        Returns (denoised, last sample) like ``sample``."""
+        self.make_schedule(verbose=False)
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"`strength` must be in (0, 1], got {strength}")
+        dev = torch.device("cuda")
+        post = init if isinstance(init, DiagonalGaussianDistribution) else None
+        if post is not None:
+            moments = post.parameters.to(dev).float().contiguous()
+            B, Cc, T = moments.shape[0], moments.shape[1] // 2, moments.shape[2]
+            z_in = None
+        else:
+            z_in = init.to(dev).float().contiguous()
+            if z_in.dim() != 3:
+                raise ValueError("audio latents are (B, C, T)")
+            B, Cc, T = z_in.shape
+            moments = None
+        dit: ConcatDiT2MLP = self.model.unet.diffusion_model
+        if T > dit.cfg.max_latent_len:
+            raise ValueError(f"latent length {T} exceeds the DiT's {dit.cfg.max_latent_len} frames")
+        if mask is not None:
+            mask = torch.as_tensor(mask, dtype=torch.float32)
+            if mask.dim() == 0:
+                mask = mask.expand(B, T)
+            if tuple(mask.shape) != (B, T):
+                raise ValueError(f"mask must be (B, T) = {(B, T)}, got {tuple(mask.shape)}")
+            mask = mask.to(dev).contiguous()
+        cond = conditioning
+        if isinstance(cond, dict):
+            cond = cond[list(cond.keys())[0]]
+            while isinstance(cond, list):
+                cond = cond[0]
+        plan = schedule.sample_plan(S, original_inference_steps, strength=strength)
+        self.num_inference_steps = len(plan)
+        self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
+        n_noise = sum(1 for p in plan if p["add_noise"])
+        e0 = posterior_noise if post is not None and sample_posterior else None
+        draw_e0 = post is not None and sample_posterior and posterior_noise is None
+        if seeds is not None:
+            n0_h, noise_h, e0_h = recipe.edit_noise(seeds, len(plan), Cc, T)
+            n0 = _h2d(n0_h, dev) if init_noise is None else init_noise
+            noise = _h2d(noise_h, dev) if noise is None else noise
+            if draw_e0:
+                e0 = _h2d(e0_h, dev)
+        else:
+            n0 = torch.randn((B, Cc, T), device=dev) if init_noise is None else init_noise
+            if noise is None and n_noise:
+                noise = torch.randn((n_noise, B, Cc, T), device=dev)
+            if draw_e0:
+                e0 = torch.randn((B, Cc, T), device=dev)
+        n0 = n0.to(dev).float().contiguous()
+        noise = noise.to(dev).float().contiguous() if noise is not None else None
+        e0 = e0.to(dev).float().contiguous() if e0 is not None else None
+        keep = tuple(plan[0]["coeffs"][:2])  # sqrt(ac[t0]), sqrt(1 - ac[t0])
+        regen = keep if strength < 1.0 else (0.0, 1.0)
+        z0 = torch.empty((B, Cc, T), device=dev, dtype=torch.float32)
+        img = torch.empty_like(z0)
+        sk = regen if mask is None else keep  # no mask: every frame is regenerated
+        check(lib().alcm_latent_init(ptr(moments), ptr(z_in), ptr(e0), float(self.model.scale_factor), ptr(n0),
+                                     ptr(mask), sk[0], sk[1], regen[0], regen[1], ptr(z0), ptr(img), B, Cc, T,
+                                     stream_handle()), "latent_init")
+        return self._run(plan, img, noise, cond, B, guidance_scale, unconditional_conditioning,
+                         unconditional_guidance_scale, z0=z0 if mask is not None else None, mask=mask)

@@ -457,3 +457,29 @@ def prompt_noise(seeds, steps: int, channels: int = 20, length: int = 312):
     x_T = torch.stack(xs, 0)
     noise = torch.stack(ns, 1) if steps > 1 else torch.zeros((0, len(xs), channels, length))
     return x_T, noise
+
+
+def edit_noise(seeds, steps: int, channels: int = 20, length: int = 312):
+    """``prompt_noise`` plus the posterior noise of an audio-conditioned call: per prompt, from the same
+    ``torch.Generator(seed)``, the starting noise n0, one noise tensor per non-final step, then e0 (the noise of
+    ``DiagonalGaussianDistribution.sample``) drawn last, so the first two results equal ``prompt_noise(...)`` bit for
+    bit.  Returns ``n0`` (B,C,T), ``noise`` (max(S-1,0),B,C,T) and ``e0`` (B,C,T)."""
+    xs, ns, es = [], [], []
+    for s in seeds:
+        g = torch.Generator().manual_seed(int(s))
+        xs.append(torch.randn((channels, length), generator=g))
+        ns.append(torch.stack([torch.randn((channels, length), generator=g) for _ in range(max(steps - 1, 0))], 0)
+                  if steps > 1 else torch.zeros((0, channels, length)))
+        es.append(torch.randn((channels, length), generator=g))
+    noise = torch.stack(ns, 1) if steps > 1 else torch.zeros((0, len(xs), channels, length))
+    return torch.stack(xs, 0), noise, torch.stack(es, 0)
+
+
+WINDOW_SEED_STRIDE = 0x9E3779B1  # odd 32-bit golden-ratio constant: windows of neighbouring prompt seeds do not collide
+
+
+def window_seed(seed: int, k: int) -> int:
+    """RNG seed of window k of a long-form clip whose prompt seed is ``seed``: window 0 is the prompt's own seed, window
+    k >= 1 is (seed + k * WINDOW_SEED_STRIDE) mod 2^63.  A function of (seed, k) alone, so a clip does not depend on
+    the batch it is generated in."""
+    return (int(seed) + int(k) * WINDOW_SEED_STRIDE) % (1 << 63)

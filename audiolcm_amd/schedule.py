@@ -91,10 +91,13 @@ def timestep_freqs(dim: int = 256, max_period: int = 10000) -> torch.Tensor:
     return _cr_exp(-math.log(max_period) * torch.arange(start=0, end=half, dtype=torch.float32) / half)
 
 
-def sample_plan(S: int, original_inference_steps: int = 50, timesteps: Optional[Sequence[int]] = None
-                ) -> List[Dict]:
-    """Per-step (t, prev_t, coeffs, add_noise) for LCMSampler.lcm_sampling (scheduling_lcm.py:344-382)."""
-    ts = lcm_timesteps(None if timesteps is not None else S, original_inference_steps, timesteps=timesteps)
+def sample_plan(S: int, original_inference_steps: int = 50, timesteps: Optional[Sequence[int]] = None,
+                strength: float = 1.0) -> List[Dict]:
+    """Per-step (t, prev_t, coeffs, add_noise) for LCMSampler.lcm_sampling (scheduling_lcm.py:344-382).  ``strength``
+    < 1 starts the schedule at the noise level int(original_inference_steps * strength) steps up (set_timesteps,
+    scheduling_lcm.py:171), for sampling from a partly noised input."""
+    ts = lcm_timesteps(None if timesteps is not None else S, original_inference_steps, timesteps=timesteps,
+                       strength=strength)
     ac = alphas_cumprod()
     plan = []
     for i, t in enumerate(ts):

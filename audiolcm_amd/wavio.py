@@ -32,3 +32,30 @@ def read_pcm16(path: str):
     sr = struct.unpack("<I", raw[24:28])[0]
     n = struct.unpack("<I", raw[40:44])[0]
     return np.frombuffer(raw[44:44 + n], dtype="<i2"), sr
+
+
+def read_wav(path: str):
+    """Mono PCM16 WAV -> (float32 samples in [-1, 1] (x / 32768), sample rate).  Walks the RIFF chunks (a file may
+    carry LIST or other chunks before ``data``); anything but mono 16-bit PCM raises ValueError."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    fmt = data = None
+    pos = 12
+    while pos + 8 <= len(raw):
+        cid, size = raw[pos:pos + 4], struct.unpack("<I", raw[pos + 4:pos + 8])[0]
+        body = raw[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            fmt = body
+        elif cid == b"data":
+            data = body
+            break
+        pos += 8 + size + (size & 1)  # chunks are word aligned
+    if fmt is None or len(fmt) < 16 or data is None:
+        raise ValueError(f"{path}: missing fmt or data chunk")
+    tag, channels, sr, _, _, bits = struct.unpack("<HHIIHH", fmt[:16])
+    if tag != 1 or channels != 1 or bits != 16:
+        raise ValueError(f"{path}: only mono PCM16 is read (format {tag}, {channels} channels, {bits} bits)")
+    x = np.frombuffer(data[:len(data) // 2 * 2], dtype="<i2").astype(np.float32) / np.float32(32768.0)
+    return x, sr

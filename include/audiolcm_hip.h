@@ -279,6 +279,26 @@ int alcm_lcm_step(const float* x, const float* eps, const float* noise, const fl
 int alcm_lcm_step_cfg(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
                       const float* noise, const float* coeffs, float* prev_out, float* denoised_out, int64_t n,
                       alcm_stream_t stream);
+/* alcm_lcm_step_edit: the step above (eps_uncond may be NULL: no guidance combine) on (B, C, T) latents with a known
+ * latent z0 (B, C, T) blended in per frame by mask (B, T) in [0, 1], 1 = regenerate:
+ *   d' = m * d + (1 - m) * z0   (d: the step's denoised value; m = 1 gives d and m = 0 gives z0, bit for bit)
+ *   denoised_out = d',  prev_out = noise ? sqrt_a_prev * d' + sqrt_b_prev * noise : d'.
+ * 16-byte accesses along T when T % 4 == 0 and every pointer is 16-byte aligned, element accesses otherwise.
+ * ALCM_E_INVALID for a null x, eps_cond, coeffs, z0 or mask, both outputs null, or a negative B, C or T. */
+int alcm_lcm_step_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                       const float* noise, const float* coeffs, const float* z0, const float* mask, float* prev_out,
+                       float* denoised_out, int B, int C, int T, alcm_stream_t stream);
+/* alcm_latent_init: the encoder output (or a given latent) -> the edit sampler's starting point, one launch.
+ *   exactly one of moments (B, 2C, T: mean | logvar, AutoencoderKL.encode) and z0_in (B, C, T);
+ *   z0 = z0_in, or scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0); e0 (B, C, T) NULL: the posterior mode
+ *        scale * mean (e0 is ignored with z0_in);
+ *   x  = m * (sa_r * z0 + sb_r * noise) + (1 - m) * (sa * z0 + sb * noise), m = mask[b][t] (B, T);
+ *        mask NULL: x = sa * z0 + sb * noise.
+ * z0_out / x_out (B, C, T): either may be NULL, not both; noise (B, C, T) is needed for x_out.  ALCM_E_INVALID
+ * otherwise, or for a negative B, C or T. */
+int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
+                     const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
+                     int C, int T, alcm_stream_t stream);
 /* out[b] = [f(v[b]*vscale*freqs[i]) ...]: cos_first ? [cos | sin] (TimestepEmbedder, concatDiT.py:49-67)
  *                                                   : [sin | cos] (get_guidance_scale_embedding, w*1000).
  * freqs: the reference's fp32 frequency table (half entries, device pointer) */

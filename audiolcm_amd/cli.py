@@ -14,7 +14,10 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
   * ``--inpaint`` (parsed and never read by the reference) is text-guided inpainting of ``--init-audio PATH`` on the
     spans of ``--mask-spans "2.0-4.5,7-8"`` (seconds); without both it raises.  ``--init-audio`` alone is a variation
     of that clip at ``--strength F``; ``--duration SECONDS`` generates long-form clips by windowed continuation
-    (DESIGN.md §5);
+    (DESIGN.md §5).  ``--keep-original`` (with ``--inpaint``) takes a recording of any length, regenerates only the
+    whole latent frames inside the spans window by window and fades them into the input over ``--fade-ms F`` (default
+    32) either side: every sample further than F ms from a span is written back as it was read, and each output has
+    the input's sample count.  Without it the clip is cropped to the DiT's 845 frames and synthesised again as a whole;
   * ``--synthetic-seed N`` runs on the seeded recipe weights (no checkpoints offline).
 """
 from __future__ import annotations
@@ -29,8 +32,8 @@ import numpy as np
 import torch
 
 from .config import instantiate_from_config, load_config
-from .infer_api import (FRAME_SAMPLES, SAMPLE_RATE, load_init_audio, load_model_from_config, parse_spans,
-                        spans_to_mask, struct_caption)
+from .infer_api import (FRAME_SAMPLES, SAMPLE_RATE, fade_samples_of, keep_original_mask, load_init_audio,
+                        load_init_audio_whole, load_model_from_config, parse_spans, spans_to_mask, struct_caption)
 from .lcm import LCMSampler
 from .models import VocoderBigVGAN
 from .wavio import write_pcm16
@@ -67,6 +70,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                    help="with --init-audio: how far the clip is noised before sampling, in (0, 1]")
     p.add_argument("--mask-spans", type=str, default=None,
                    help='with --inpaint: the time spans to regenerate, in seconds, e.g. "2.0-4.5,7-8"')
+    p.add_argument("--keep-original", action="store_true",
+                   help="with --inpaint: any clip length; keep the input waveform outside the spans bit for bit")
+    p.add_argument("--fade-ms", type=float, default=32.0,
+                   help="with --keep-original: the fade between the input and the regenerated audio, either side")
     p.add_argument("--duration", type=float, default=None,
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--test-dataset-tsv", type=str, default=None, help="override the config's test_dataset tsv_path")
@@ -83,8 +90,11 @@ class GenSamples:
         self.save_mel, self.save_wav = save_mel, save_wav
         self.channel_dim = model.channels
         self.original_inference_steps = original_inference_steps
-        self.init_wav = None
-        if opt.init_audio:
+        self.init_wav, self.init_samples = None, None
+        if opt.init_audio and opt.keep_original:
+            self.init_wav, self.init_samples = load_init_audio_whole(opt.init_audio)
+            self.keep_mask = keep_original_mask(parse_spans(opt.mask_spans), self.init_wav.size // FRAME_SAMPLES)
+        elif opt.init_audio:
             self.init_wav = load_init_audio(opt.init_audio, model.unet.diffusion_model.cfg.max_latent_len)
 
     def generate(self, c, seeds):
@@ -97,6 +107,15 @@ class GenSamples:
                                     latent_shape=(self.opt.H, self.opt.W), **kw)
             out = pipe.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES))
             return out["mel"], out["wav"].unsqueeze(1)
+        if self.opt.keep_original:
+            from .pipeline import AudioLCMPipeline
+            pipe = AudioLCMPipeline(self.model, self.vocoder.generator, steps=self.opt.ddim_steps,
+                                    latent_shape=(self.opt.H, self.opt.W), **kw)
+            out = pipe.edit_long(c, seeds, wav=np.broadcast_to(self.init_wav, (B, self.init_wav.size)).copy(),
+                                 mask=np.broadcast_to(self.keep_mask, (B, self.keep_mask.size)).copy(),
+                                 strength=self.opt.strength, keep_original=True,
+                                 fade_samples=fade_samples_of(self.opt.fade_ms))
+            return None, out["wav"][:, :self.init_samples].unsqueeze(1)
         if self.init_wav is not None:
             from .mel import MelNet
             from .models import DiagonalGaussianDistribution
@@ -132,19 +151,20 @@ class GenSamples:
             seeds = [self.clip_seed(first_index + i, it, j) for i in range(len(prompts)) for j in range(n)]
             mel, wav = self.generate(c, seeds)
             wav = wav.squeeze(1).cpu().numpy() if self.save_wav else None
-            mel_np = mel.cpu().numpy()
+            mel_np = mel.cpu().numpy() if mel is not None else None
             for i in range(len(prompts)):
                 for j in range(n):
                     idx = it * n + j  # the reference restarts idx per iteration (overwriting files); keep them apart
                     k = i * n + j
                     rec = {"caption": prompts[i]["ori_caption"]}
-                    if self.save_mel:
+                    if self.save_mel and mel_np is not None:  # --keep-original decodes no whole-clip mel
                         mp = os.path.join(self.outpath, f"{names[i]}_{idx}.npy")
                         np.save(mp, mel_np[k])
                         rec["mel_path"] = mp
                     if self.save_wav:
                         wp = os.path.join(self.outpath, f"{names[i]}_{idx}.wav")
-                        write_pcm16(wp, wav[k], self.opt.sample_rate)
+                        write_pcm16(wp, wav[k], self.opt.sample_rate,
+                                    scale=32768.0 if self.opt.keep_original else 32767.0)
                         rec["audio_path"] = wp
                     records[i].append(rec)
         return [r for rs in records for r in rs]
@@ -157,6 +177,8 @@ def build(opt):
     if opt.inpaint and not (opt.init_audio and opt.mask_spans):
         raise NotImplementedError("--inpaint needs --init-audio PATH and --mask-spans: the clip to inpaint and the "
                                   "time spans to regenerate")
+    if opt.keep_original and not opt.inpaint:
+        raise ValueError("--keep-original is used with --inpaint")
     if opt.mask_spans and not opt.inpaint:
         raise ValueError("--mask-spans is used with --inpaint")
     if opt.init_audio and opt.duration is not None:

@@ -52,6 +52,8 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
 int latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
                 const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
                 int C, int T, hipStream_t s);
+int wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
+               int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s);
 int fill_f32(float* p, int64_t n, float v, hipStream_t s);
 int nct_to_cl(const float* x, int B, int C, int T, int Cp, float* y, hipStream_t s);
 // fp32 rows [rows][C] -> operand planes [rows][Cp] in the format of `prec` (SPLIT: lo plane rows * Cp after hi)

@@ -1,6 +1,9 @@
 // Bandwidth-bound kernels of the AudioLCM hot path (gfx950): norm statistics, softmax,
 // the fused anti-aliased SnakeBeta activation (Activation1d), the LCM step and the
 // sinusoidal embeddings.  All tensors are fp32; activations are channels-last (b, t, c).
+#include <algorithm>
+#include <vector>
+
 #include "alcm_common.h"
 #include "alcm_internal.h"
 
@@ -648,6 +651,144 @@ int latent_init(const float* moments, const float* z0_in, const float* e0, float
   return 0;
 }
 
+// ---------------------------------------------------------------- waveform paste
+// out = orig with a decoded region gen (samples gen_start .. gen_start + Ng of each clip) blended in around the
+// regenerated latent frames of mask (B, T): with d the distance in samples to the nearest sample of a regenerated frame
+// of the same clip, g = 1 at d = 0, ramp[d] for 0 < d < R and 0 from R on or outside gen; out is orig at g = 0 and gen at
+// g = 1, both bit for bit, and orig + g * (gen - orig) in between.  One workgroup takes kPasteTile frames of one clip:
+// it reads the mask of those frames and of H = ceil(R / frame_samples) frames either side into LDS, derives per frame
+// the distance in frames to the nearest regenerated frame on the left and on the right, and moves V samples per thread
+// and pass (V = 4 with 16-byte accesses when the sizes and pointers allow, else 1).  In place (out == orig) a sample of
+// g = 0 is neither read nor written and a tile without any g > 0 ends after the mask.
+constexpr int kPasteTile = 8;
+constexpr int kPasteHalo = 16;  // frames the ramp may reach past a regenerated frame: R <= kPasteHalo * frame_samples
+constexpr int kPasteBlock = 256;
+
+template <int V>
+__global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
+    const float* orig, const float* __restrict__ gen, const float* __restrict__ mask, const float* __restrict__ ramp,
+    float* out, int64_t N, int64_t Ng, int64_t gen_start, int T, int fs, int R, int H, int f_first, int tiles,
+    FastDiv fsdiv) {
+  __shared__ int s_reg[kPasteTile + 2 * kPasteHalo];
+  __shared__ int s_kl[kPasteTile], s_kr[kPasteTile];
+  const int b = blockIdx.x / tiles;
+  const int f0 = f_first + (int)(blockIdx.x - (unsigned)b * tiles) * kPasteTile;
+  const bool inplace = out == orig;
+  for (int i = threadIdx.x; i < kPasteTile + 2 * H; i += kPasteBlock) {
+    const int f = f0 - H + i;
+    s_reg[i] = (f >= 0 && f < T) ? (mask[(int64_t)b * T + f] > 0.f) : 0;
+  }
+  __syncthreads();
+  int live = 0;
+  if (threadIdx.x < kPasteTile) {
+    // frames to the nearest regenerated frame: 0 = this one, H + 1 = none within the ramp's reach
+    const int c = H + threadIdx.x;
+    int kl = 0, kr = 0;
+    while (kl <= H && !s_reg[c - kl]) ++kl;
+    while (kr <= H && !s_reg[c + kr]) ++kr;
+    s_kl[threadIdx.x] = kl;
+    s_kr[threadIdx.x] = kr;
+    live = kl == 0 || (int64_t)(kl - 1) * fs + 1 < R || (int64_t)(kr - 1) * fs + 1 < R;
+  }
+  if (!__syncthreads_or(live) && inplace) return;
+
+  const int64_t n0 = (int64_t)f0 * fs, row = (int64_t)b * N, grow = (int64_t)b * Ng - gen_start;
+  const uint32_t chunks = (uint32_t)kPasteTile * fs / V;
+  for (uint32_t c = threadIdx.x; c < chunks; c += kPasteBlock) {
+    const int64_t n = n0 + (int64_t)c * V;
+    if (n >= N) break;
+    uint32_t j, off;
+    fsdiv.divmod(c * V, j, off);
+    const int kl = s_kl[j], kr = s_kr[j];
+    // kept frame: element i is dl + i samples past the last regenerated sample on the left, dr - i before the first on
+    // the right (V = 4 only with frame_samples % 4 == 0: the elements of one access share their frame)
+    const int64_t dl = off + (int64_t)(kl - 1) * fs + 1, dr = (int64_t)kr * fs - off;
+    const bool in_gen = n >= gen_start && n + V <= gen_start + Ng;
+    FVec<V> g;
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      const int64_t d = kl == 0 ? 0 : dl + i < dr - i ? dl + i : dr - i;
+      g.v[i] = !in_gen ? 0.f : d == 0 ? 1.f : d < R ? ramp[d] : 0.f;
+      any |= g.v[i] != 0.f;
+    }
+    if (!any) {
+      if (!inplace) FVec<V>::ld(orig + row + n).st(out + row + n);
+      continue;
+    }
+    const FVec<V> ov = FVec<V>::ld(orig + row + n), gv = FVec<V>::ld(gen + grow + n);
+    FVec<V> r;
+#pragma unroll
+    for (int i = 0; i < V; ++i)
+      r.v[i] = g.v[i] == 1.f ? gv.v[i] : g.v[i] == 0.f ? ov.v[i] : fmaf(g.v[i], gv.v[i] - ov.v[i], ov.v[i]);
+    r.st(out + row + n);
+  }
+}
+
+// The samples of g > 0 of one launch, from a host copy of the mask (taken only while profiling).
+static double wave_paste_blended(const std::vector<float>& m, int B, int64_t N, int64_t gen_start, int64_t Ng, int T,
+                                 int fs, int R, int H) {
+  double blended = 0;
+  const int f_lo = (int)(gen_start / fs), f_hi = (int)((gen_start + Ng + fs - 1) / fs);
+  for (int b = 0; b < B; ++b)
+    for (int f = f_lo; f < f_hi; ++f) {
+      int kl = 0, kr = 0;
+      while (kl <= H && !(f - kl >= 0 && m[(size_t)b * T + f - kl] > 0.f)) ++kl;
+      while (kr <= H && !(f + kr < T && m[(size_t)b * T + f + kr] > 0.f)) ++kr;
+      const int64_t lo = std::max<int64_t>((int64_t)f * fs, gen_start);
+      const int64_t hi = std::min<int64_t>({(int64_t)(f + 1) * fs, gen_start + Ng, N});
+      // samples of the frame within R of the left neighbour, and of the right one
+      const int64_t nl = std::clamp<int64_t>(R - 1 - (int64_t)(kl - 1) * fs, 0, fs);
+      const int64_t nr = std::clamp<int64_t>(R - 1 - (int64_t)(kr - 1) * fs, 0, fs);
+      blended += (double)std::min<int64_t>(kl == 0 ? fs : nl + nr, std::max<int64_t>(hi - lo, 0));
+    }
+  return blended;
+}
+
+int wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
+               int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
+  if (!orig || !out || !mask) return set_error(ALCM_E_INVALID, "wave_paste: null orig, out or mask");
+  if (B < 0 || N < 0 || Ng < 0 || gen_start < 0 || T < 0 || R < 0)
+    return set_error(ALCM_E_INVALID, "wave_paste: negative B, N, Ng, gen_start, T or R");
+  if (fs <= 0 || fs > (1 << 20)) return set_error(ALCM_E_INVALID, "wave_paste: frame_samples outside 1 .. 2^20");
+  if ((int64_t)T * fs < N) return set_error(ALCM_E_INVALID, "wave_paste: the mask's T * frame_samples is shorter than N");
+  if (gen_start + Ng > N) return set_error(ALCM_E_INVALID, "wave_paste: gen reaches past the clip");
+  if (R > (int64_t)kPasteHalo * fs) return set_error(ALCM_E_INVALID, "wave_paste: R exceeds 16 frames");
+  if ((Ng > 0 && !gen) || (R > 0 && !ramp)) return set_error(ALCM_E_INVALID, "wave_paste: null gen or ramp");
+  if (B == 0 || N == 0) return 0;
+  const bool inplace = out == orig;
+  if (Ng == 0) {  // nothing to blend: no launch
+    if (!inplace) ALCM_HIP(hipMemcpyAsync(out, orig, sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  // in place only the frames gen covers can change; out of place every frame is at least copied
+  const int64_t fa = inplace ? gen_start / fs : 0;
+  const int64_t fb = inplace ? (gen_start + Ng + fs - 1) / fs : (N + fs - 1) / fs;
+  const int64_t tiles = (fb - fa + kPasteTile - 1) / kPasteTile;
+  if (tiles * B >= (1ll << 31)) return set_error(ALCM_E_INVALID, "wave_paste: problem too large");
+  const int H = (R + fs - 1) / fs;
+  const bool vec = fs % 4 == 0 && N % 4 == 0 && Ng % 4 == 0 && gen_start % 4 == 0 && aligned16({orig, gen, out});
+  double blended = 0;
+  if (prof_enabled()) {
+    std::vector<float> m((size_t)B * T);
+    ALCM_HIP(hipMemcpyAsync(m.data(), mask, sizeof(float) * m.size(), hipMemcpyDeviceToHost, s));
+    ALCM_HIP(hipStreamSynchronize(s));
+    blended = wave_paste_blended(m, B, N, gen_start, Ng, T, fs, R, H);
+  }
+  void* tok = prof_start(s);
+  if (vec)
+    hipLaunchKernelGGL(wave_paste_kernel<4>, dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen, mask, ramp,
+                       out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)tiles, FastDiv((uint32_t)fs));
+  else
+    hipLaunchKernelGGL(wave_paste_kernel<1>, dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen, mask, ramp,
+                       out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)tiles, FastDiv((uint32_t)fs));
+  // per sample of g > 0: orig and gen in, out out; of g = 0: a copy out of place, nothing in place; the mask per frame
+  prof_stop(tok, s, vec ? "alcm::wave_paste_kernel<4>" : "alcm::wave_paste_kernel<1>", 3.0 * blended,
+            4.0 * (3.0 * blended + (inplace ? 0.0 : 2.0 * ((double)B * N - blended)) + (double)tiles * B * kPasteTile));
+  ALCM_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- sinusoidal embeddings
 // freqs[] is the reference's own fp32 frequency table (computed on the host exactly as
 // scheduling_lcm.py:103-105 / concatDiT.py:60-62 do), so the only device math is t*f and sin/cos.
@@ -773,6 +914,11 @@ extern "C" int alcm_latent_init(const float* moments, const float* z0_in, const 
                                 float* z0_out, float* x_out, int B, int C, int T, alcm_stream_t stream) {
   return alcm::latent_init(moments, z0_in, e0, scale, noise, mask, sa, sb, sa_r, sb_r, z0_out, x_out, B, C, T,
                            (hipStream_t)stream);
+}
+extern "C" int alcm_wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out,
+                               int B, int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R,
+                               alcm_stream_t stream) {
+  return alcm::wave_paste(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, frame_samples, R, (hipStream_t)stream);
 }
 extern "C" int alcm_sincos_embedding(const float* v, float vscale, const float* freqs, int B, int half,
                                      int cos_first, float* out, alcm_stream_t stream) {

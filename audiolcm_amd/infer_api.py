@@ -163,31 +163,62 @@ def parse_spans(text: str) -> List[Tuple[float, float]]:
 
 
 def spans_to_mask(spans: Optional[Sequence[Tuple[float, float]]], n_frames: int, sample_rate: int = SAMPLE_RATE,
-                  frame_samples: int = FRAME_SAMPLES) -> np.ndarray:
+                  frame_samples: int = FRAME_SAMPLES, inward: bool = False) -> np.ndarray:
     """(n_frames,) float32 regenerate-mask of the time spans [t0, t1) in seconds: span -> latent frames
     floor(sample_rate * t0 / frame_samples) up to (not including) ceil(sample_rate * t1 / frame_samples), so a span
-    ending mid-frame takes that frame too; clipped to the clip."""
+    ending mid-frame takes that frame too; clipped to the clip.  ``inward``: only the frames that lie wholly inside a
+    span (ceil at the start, floor at the end), so that nothing outside the span is regenerated."""
     mask = np.zeros((n_frames,), dtype=np.float32)
+    first, last = (math.ceil, math.floor) if inward else (math.floor, math.ceil)
     for t0, t1 in spans or ():
         if t1 <= t0:
             continue
-        lo = max(0, math.floor(sample_rate * t0 / frame_samples))
-        hi = min(n_frames, math.ceil(sample_rate * t1 / frame_samples))
+        lo = max(0, first(sample_rate * t0 / frame_samples))
+        hi = min(n_frames, last(sample_rate * t1 / frame_samples))
         mask[lo:hi] = 1.0
     return mask
+
+
+def keep_original_mask(spans: Sequence[Tuple[float, float]], n_frames: int) -> np.ndarray:
+    """The mask of a keep-original inpainting: the whole frames inside the spans, so that with a fade of F samples no
+    sample further than F from a span changes.  ValueError when no span holds a whole frame."""
+    mask = spans_to_mask(spans, n_frames, inward=True)
+    if not mask.any():
+        raise ValueError(f"no whole latent frame ({1000 * FRAME_SAMPLES // SAMPLE_RATE} ms) lies inside the spans "
+                         f"{list(spans)}")
+    return mask
+
+
+def fade_samples_of(fade_ms: float) -> int:
+    return int(round(fade_ms * SAMPLE_RATE / 1000.0))
 
 
 def load_init_audio(path: str, max_frames: Optional[int] = None) -> np.ndarray:
     """16 kHz mono PCM16 WAV -> float32 samples, zero-padded up to a whole number of latent frames (512 samples) and
     cropped to ``max_frames`` of them (the DiT's length limit) when given.  Another sample rate raises ValueError."""
+    x = _read_init_audio(path)
+    if max_frames is not None:
+        x = x[:max_frames * FRAME_SAMPLES]
+    return _pad_to_frames(x)
+
+
+def _read_init_audio(path: str) -> np.ndarray:
     x, sr = read_wav(path)
     if sr != SAMPLE_RATE:
         raise ValueError(f"{path}: sample rate {sr}, need {SAMPLE_RATE} (resampling is not done here)")
     if x.size == 0:
         raise ValueError(f"{path}: no samples")
-    if max_frames is not None:
-        x = x[:max_frames * FRAME_SAMPLES]
+    return x
+
+
+def _pad_to_frames(x: np.ndarray) -> np.ndarray:
     return np.pad(x, (0, -x.size % FRAME_SAMPLES))
+
+
+def load_init_audio_whole(path: str) -> Tuple[np.ndarray, int]:
+    """``load_init_audio`` without a crop, and the file's own sample count (a keep-original edit writes that many)."""
+    x = _read_init_audio(path)
+    return _pad_to_frames(x), x.size
 
 
 def _seed_list(seed: Optional[int], n: int):
@@ -198,14 +229,36 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
                       mask_spans: Optional[Sequence[Tuple[float, float]]] = None,
                       config_path: str = "configs/audiolcm.yaml", model_path: str = "./model/000184.ckpt",
                       vocoder_path: str = "./model/vocoder", synthetic_seed: Optional[int] = None, split: bool = True,
-                      outpath: str = "results/test", seed: Optional[int] = None) -> str:
+                      outpath: str = "results/test", seed: Optional[int] = None, keep_original: bool = False,
+                      fade_ms: float = 32.0) -> str:
     """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength``, or, with ``mask_spans``
     ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
-    clip is synthesised again from the latent.  Returns the WAV path (``<prompt-with-dashes>_0.wav``)."""
+    clip is synthesised again from the latent, cropped to the DiT's 845 frames.  ``keep_original`` (needs
+    ``mask_spans``): the clip is not cropped, only the whole frames inside the spans are regenerated
+    (``AudioLCMPipeline.edit_long``) and faded into the input over ``fade_ms`` either side; every sample further than
+    ``fade_ms`` from a span is written back as it was read, and the file has the input's sample count.  Returns the
+    WAV path (``<prompt-with-dashes>_0.wav``)."""
     from .mel import MelNet
-    wav_in = load_init_audio(init_audio)  # a bad input fails before the models are built
+    if keep_original and not mask_spans:
+        raise ValueError("keep_original needs mask_spans: the time spans to regenerate")
+    wav_in, n_samples = load_init_audio_whole(init_audio)  # a bad input fails before the models are built
+    if keep_original:
+        mask = keep_original_mask(mask_spans, wav_in.size // FRAME_SAMPLES)
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  encoder=True)
+    path = os.path.join(outpath, wav_name_for(ori_prompt) + "_0.wav")
+    if keep_original:
+        from .pipeline import AudioLCMPipeline
+        pipe = AudioLCMPipeline(model, vocoder.generator, steps=2, original_inference_steps=orig_steps,
+                                latent_shape=(model.mel_dim, model.mel_length))
+        os.makedirs(outpath, exist_ok=True)
+        with torch.no_grad():
+            c = model.get_learned_conditioning({"ori_caption": [ori_prompt],
+                                                "struct_caption": [struct_caption(ori_prompt)]})
+            out = pipe.edit_long(c, _seed_list(seed, 1), wav=wav_in[None], mask=mask[None], strength=strength,
+                                 keep_original=True, fade_samples=fade_samples_of(fade_ms))
+        write_pcm16(path, out["wav"][0, :n_samples].cpu().numpy(), SAMPLE_RATE, scale=32768.0)
+        return path
     wav_in = wav_in[:model.unet.diffusion_model.cfg.max_latent_len * FRAME_SAMPLES]
     os.makedirs(outpath, exist_ok=True)
     with torch.no_grad():
@@ -216,7 +269,6 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
         z, _ = sampler.sample_edit(S=2, conditioning=c, init=post, mask=mask, strength=strength,
                                    seeds=_seed_list(seed, 1), original_inference_steps=orig_steps)
         wav = vocoder.vocode(model.decode_first_stage(z)).squeeze(1).cpu().numpy()
-    path = os.path.join(outpath, wav_name_for(ori_prompt) + "_0.wav")
     write_pcm16(path, wav[0], SAMPLE_RATE)
     return path
 

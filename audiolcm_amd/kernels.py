@@ -357,6 +357,45 @@ def latent_init(noise: Optional[torch.Tensor], keep=(1.0, 0.0), regen=(0.0, 1.0)
     return z0_out, x_out
 
 
+PASTE_MAX_FADE_FRAMES = 16  # alcm_wave_paste: the ramp reaches at most 16 frames past a regenerated frame
+_ramps = {}
+
+
+def paste_ramp_host(R: int) -> torch.Tensor:
+    """The fade weights of ``wave_paste``: ramp[d] = 0.5 * (1 + cos(pi * d / R)) for d = 0 .. R - 1, evaluated in
+    float64 and rounded to fp32 (ramp[0] = 1, strictly decreasing, never 0).  R = 0: an empty table."""
+    d = torch.arange(R, dtype=torch.float64)
+    return (0.5 * (1.0 + torch.cos(math.pi * d / max(R, 1)))).float()
+
+
+def paste_ramp(R: int, device) -> torch.Tensor:
+    """``paste_ramp_host(R)`` on ``device``, built once per (R, device)."""
+    key = (int(R), torch.device(device))
+    if key not in _ramps:
+        _ramps[key] = paste_ramp_host(R).to(device)
+    return _ramps[key]
+
+
+def wave_paste(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_start: int = 0, fade_samples: int = 512,
+               frame_samples: int = 512, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Blend the decoded region ``gen`` (B, Ng), samples gen_start .. gen_start + Ng of each clip, into ``orig`` (B, N)
+    around the regenerated frames of ``mask`` (B, T; > 0 = regenerated, ``frame_samples`` samples per frame): gen
+    inside a regenerated frame, a raised-cosine fade over the ``fade_samples`` samples either side of one, orig bit for
+    bit further away and outside gen (alcm_wave_paste).  ``out`` None: a new tensor; ``out=orig`` pastes in place and
+    touches only what changes.  One launch."""
+    B, N = orig.shape
+    assert orig.is_contiguous() and gen.is_contiguous() and mask.is_contiguous()
+    assert gen.shape[0] == B and mask.shape[0] == B and gen.dim() == 2 and mask.dim() == 2
+    if out is None:
+        out = torch.empty_like(orig)
+    assert out.shape == orig.shape and out.is_contiguous()
+    ramp = paste_ramp(fade_samples, orig.device) if 0 < fade_samples <= PASTE_MAX_FADE_FRAMES * frame_samples else None
+    check(lib().alcm_wave_paste(ptr(orig), ptr(gen), ptr(mask), ptr(ramp), ptr(out), B, N, int(gen_start),
+                                gen.shape[1], mask.shape[1], int(frame_samples), int(fade_samples), stream_handle()),
+          "wave_paste")
+    return out
+
+
 def sincos_embedding(v: torch.Tensor, freqs: torch.Tensor, scale: float, cos_first: bool) -> torch.Tensor:
     B = v.shape[0]
     half = freqs.numel()

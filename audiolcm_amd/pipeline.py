@@ -17,6 +17,51 @@ from .lcm import LCM_audio, LCMSampler
 from .models import AutoencoderKL, BigVGAN, ConcatDiT2MLP
 
 
+FRAME_SAMPLES = 512  # one latent frame = 2 mel frames x hop 256
+
+
+def edit_windows(union, window: int, overlap: Optional[int] = None):
+    """(window starts, window length W) of ``edit_long`` for a clip of L = len(union) latent frames: ``union[t]`` is
+    true where any clip of the batch regenerates frame t.  W = min(window, L); ``overlap`` defaults to W // 2.  Each
+    window starts ``overlap`` frames before the first frame still to do (clamped to the clip) and clears its W frames; a
+    span longer than a window is continued by the next one, which sees the frames already produced as known context."""
+    todo = [bool(v) for v in union]
+    L = len(todo)
+    W = min(window, L)
+    overlap = W // 2 if overlap is None else overlap
+    if not 0 < overlap < W:
+        raise ValueError("need 0 < overlap < window")
+    starts = []
+    while any(todo):
+        s = min(max(todo.index(True) - overlap, 0), L - W)
+        starts.append(s)
+        todo[s:s + W] = [False] * W
+    return starts, W
+
+
+def paste_regions(union, halo: int):
+    """The latent-frame ranges [a, b) ``edit_long(keep_original=True)`` decodes: every maximal run [lo, hi) of
+    regenerated frames widened by ``halo`` frames either side, clamped to the clip; overlapping or touching ranges are
+    merged."""
+    todo = [bool(v) for v in union]
+    L = len(todo)
+    regions, t = [], 0
+    while t < L:
+        if not todo[t]:
+            t += 1
+            continue
+        hi = t
+        while hi < L and todo[hi]:
+            hi += 1
+        a, b = max(t - halo, 0), min(hi + halo, L)
+        if regions and a <= regions[-1][1]:
+            regions[-1] = (regions[-1][0], b)
+        else:
+            regions.append((a, b))
+        t = hi
+    return regions
+
+
 class AudioLCMPipeline:
     def __init__(self, model: LCM_audio, vocoder: BigVGAN, steps: int = 2, guidance_scale: float = 5.0,
                  original_inference_steps: int = 50, latent_shape=(20, 312)):
@@ -66,23 +111,120 @@ class AudioLCMPipeline:
         multiple of 512 (log-mel -> ``encode_first_stage``; needs the encoder weights) and ``latent`` (B, C, T) already
         scaled.  ``mask`` None: a variation of the whole clip at ``strength``; ``mask`` (B, T), 1 = regenerate: text-guided
         inpainting, the frames of mask 0 keep the input latent exactly.  The whole clip is decoded and vocoded again."""
+        z = self._edit_latent(cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
+                              cfg_scale)
+        out = self.decode(z)
+        return dict(latent=z, **out)
+
+    def _encode(self, wav):
+        if self._mel_net is None:
+            from .mel import MelNet
+            self._mel_net = MelNet()
+        return self.model.encode_first_stage(self._mel_net(wav))
+
+    def _edit_latent(self, cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
+                     cfg_scale):
+        """The latent of ``edit``: one ``sample_edit`` call on the whole clip."""
         if (wav is None) == (latent is None):
             raise ValueError("pass exactly one of `wav` and `latent`")
-        if wav is not None:
-            if self._mel_net is None:
-                from .mel import MelNet
-                self._mel_net = MelNet()
-            init = self.model.encode_first_stage(self._mel_net(wav))
-        else:
-            init = latent
+        init = self._encode(wav) if wav is not None else latent
         z, _ = self.sampler.sample_edit(S=steps or self.steps, conditioning=cond, init=init, mask=mask,
                                         strength=strength, seeds=seeds, sample_posterior=sample_posterior,
                                         guidance_scale=self.guidance_scale,
                                         original_inference_steps=self.original_inference_steps,
                                         unconditional_conditioning=unconditional,
                                         unconditional_guidance_scale=cfg_scale)
-        out = self.decode(z)
-        return dict(latent=z, **out)
+        return z
+
+    @torch.no_grad()
+    def edit_long(self, cond: torch.Tensor, seeds: Sequence[int], wav=None, latent: Optional[torch.Tensor] = None,
+                  mask=None, strength: float = 0.5, window: Optional[int] = None, overlap: Optional[int] = None,
+                  sample_posterior: bool = True, steps: Optional[int] = None,
+                  unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, keep_original: bool = False,
+                  fade_samples: int = 512, halo_frames: int = 32) -> Dict[str, torch.Tensor]:
+        """``edit`` for a clip of any length, optionally keeping the input waveform outside the regenerated frames.
+
+        The input is exactly one of ``wav`` (B, N), N a multiple of 512, encoded once as a whole (z = the scaled
+        posterior sample with e0 = ``recipe.edit_noise(seeds, S, C, L)[2]``, or the mode without ``sample_posterior``),
+        and ``latent`` (B, C, L).  ``mask`` (B, L), 1 = regenerate; None = all ones.  A clip of L <= W frames (W =
+        ``window`` or latent_shape[1]) takes ``edit``'s own path.  A longer one is edited window by window
+        (``edit_windows`` on the batch's union mask, ``overlap`` = W // 2 by default): window k is one ``sample_edit``
+        call on its W frames with the mask still to do and the seeds ``recipe.window_seed(seed, k)``; what it
+        produces is known context to the next window.  Frames of mask 0 keep the input latent exactly; an empty mask
+        runs no DiT call.
+
+        ``keep_original=False``: the whole clip is decoded; returns latent, mel, wav.  ``keep_original=True`` (needs
+        ``wav``): only ``paste_regions(union, halo_frames)`` are decoded, each blended into a copy of ``wav`` by one
+        ``kernels.wave_paste`` with a raised-cosine fade of ``fade_samples`` either side of the regenerated frames;
+        samples further away keep the input's bits.  Returns latent, wav (B, N) and regions.  ``halo_frames`` * 512 >=
+        ``fade_samples`` is required unless every region is cut by the clip's ends, so that a fade never reaches the
+        edge of a decoded region.  The default halo of 32 frames (1 s) also keeps the fade away from the zero-padded
+        edges of the region's decode; it is a choice, not a measurement (no trained weights here to listen to)."""
+        from . import kernels
+        if (wav is None) == (latent is None):
+            raise ValueError("pass exactly one of `wav` and `latent`")
+        if keep_original and wav is None:
+            raise ValueError("keep_original needs the input waveform `wav`")
+        dev = torch.device("cuda")
+        S = steps or self.steps
+        if wav is not None:
+            wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
+            if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES:
+                raise ValueError("`wav` is (B, N) with N a multiple of 512")
+            B, L = wav.shape[0], wav.shape[1] // FRAME_SAMPLES
+        else:
+            B, L = latent.shape[0], latent.shape[2]
+        W = min(window or self.latent_shape[1], L)
+        if mask is None:
+            union = [True] * L
+        else:
+            mask = torch.as_tensor(mask, dtype=torch.float32)
+            if tuple(mask.shape) != (B, L):
+                raise ValueError(f"mask must be (B, L) = {(B, L)}, got {tuple(mask.shape)}")
+            union = (mask > 0).any(0).tolist()
+        regions = paste_regions(union, halo_frames) if keep_original else None
+        if keep_original:
+            if not 0 <= fade_samples <= kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES:
+                raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES}")
+            if halo_frames * FRAME_SAMPLES < fade_samples and any(a > 0 or b < L for a, b in regions):
+                raise ValueError("halo_frames * 512 must be at least fade_samples: the fade has to end inside the "
+                                 "decoded region")
+        if any(union) and L <= W:
+            z = self._edit_latent(cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
+                                  cfg_scale)
+        else:
+            if wav is not None:
+                post = self._encode(wav)
+                e0 = None
+                if sample_posterior:
+                    Cc = post.parameters.shape[1] // 2
+                    e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(dev) if seeds is not None
+                          else torch.randn((B, Cc, L), device=dev))
+                z = kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
+                                        scale=float(self.model.scale_factor), want_x=False)[0]
+            else:
+                z = latent.to(dev).float().clone()
+            if any(union):
+                m = torch.ones((B, L)) if mask is None else mask.cpu().clone()
+                for k, s in enumerate(edit_windows(union, W, overlap)[0]):
+                    wseeds = None if seeds is None else [recipe.window_seed(sd, k) for sd in seeds]
+                    zk, _ = self.sampler.sample_edit(S=S, conditioning=cond, init=z[:, :, s:s + W].contiguous(),
+                                                     mask=m[:, s:s + W], strength=strength, seeds=wseeds,
+                                                     guidance_scale=self.guidance_scale,
+                                                     original_inference_steps=self.original_inference_steps,
+                                                     unconditional_conditioning=unconditional,
+                                                     unconditional_guidance_scale=cfg_scale)
+                    z[:, :, s:s + W] = zk
+                    m[:, s:s + W] = 0.0
+        if not keep_original:
+            return dict(latent=z, **self.decode(z))
+        out = wav.clone()
+        pm = torch.ones((B, L), device=dev) if mask is None else mask.to(dev).contiguous()
+        for a, b in regions:
+            gen = self.decode(z[:, :, a:b].contiguous())["wav"].contiguous()
+            kernels.wave_paste(out, gen, pm, gen_start=a * FRAME_SAMPLES, fade_samples=fade_samples,
+                               frame_samples=FRAME_SAMPLES, out=out)
+        return dict(latent=z, wav=out, regions=regions)
 
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
         """([(start, known)], window length) of ``generate_long``: window k covers frames start .. start + window, of

@@ -12,13 +12,15 @@ import struct
 import numpy as np
 
 
-def pcm16(wav) -> np.ndarray:
-    x = np.asarray(wav, dtype=np.float32).reshape(-1) * np.float32(32767.0)
+def pcm16(wav, scale: float = 32767.0) -> np.ndarray:
+    x = np.asarray(wav, dtype=np.float32).reshape(-1) * np.float32(scale)
     return np.clip(np.rint(x), -32768, 32767).astype("<i2")
 
 
-def write_pcm16(path: str, wav, sample_rate: int = 16000) -> None:
-    data = pcm16(wav).tobytes()
+def write_pcm16(path: str, wav, sample_rate: int = 16000, scale: float = 32767.0) -> None:
+    """``scale`` 32768.0 inverts ``read_wav`` (x / 32768) exactly, so samples read from a file and written back keep
+    their bits (with 32767 an untouched sample of |x| >= 0.5 comes back one step off); the default is libsndfile's."""
+    data = pcm16(wav, scale).tobytes()
     with open(path, "wb") as f:
         f.write(b"RIFF" + struct.pack("<I", 36 + len(data)) + b"WAVE")
         f.write(b"fmt " + struct.pack("<IHHIIHH", 16, 1, 1, sample_rate, sample_rate * 2, 2, 16))

@@ -299,6 +299,22 @@ int alcm_lcm_step_edit(const float* x, const float* eps_cond, const float* eps_u
 int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
                      const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
                      int C, int T, alcm_stream_t stream);
+/* alcm_wave_paste: blend a decoded region into the original waveform of a batch around the regenerated latent frames,
+ * one launch (no reference counterpart: the reference has no edit path).
+ *   orig, out (B, N); gen (B, Ng) holds samples gen_start .. gen_start + Ng of each clip; mask (B, T) per latent frame
+ *   of frame_samples samples, a frame of mask > 0 is regenerated; ramp (R entries, device): the fade weights.
+ *   d = distance in samples from sample n to the nearest sample of a regenerated frame of its clip (0 inside one, 1 on
+ *   the first kept sample next to one); g = 1 at d = 0, ramp[d] for 0 < d < R, 0 from R on and outside gen;
+ *   out = orig where g = 0 and gen where g = 1, both bit for bit, else orig + g * (gen - orig).
+ * R = 0 (ramp may be NULL) is a hard switch at the frame edges.  out may be orig itself: then samples of g = 0 are
+ * neither read nor written; any other overlap is not allowed.  The caller keeps ramp's reach inside gen (or accepts
+ * the cut at gen's edges).  16-byte accesses when frame_samples, N, Ng and gen_start are multiples of 4 and orig, gen
+ * and out are 16-byte aligned, element accesses otherwise.
+ * ALCM_E_INVALID for a null orig, out or mask (gen with Ng > 0, ramp with R > 0), a negative size, frame_samples
+ * outside 1 .. 2^20, T * frame_samples < N, gen_start + Ng > N, or R > 16 * frame_samples.  B, N or Ng of 0: no
+ * launch (Ng = 0 out of place copies orig). */
+int alcm_wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
+                    int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R, alcm_stream_t stream);
 /* out[b] = [f(v[b]*vscale*freqs[i]) ...]: cos_first ? [cos | sin] (TimestepEmbedder, concatDiT.py:49-67)
  *                                                   : [sin | cos] (get_guidance_scale_embedding, w*1000).
  * freqs: the reference's fp32 frequency table (half entries, device pointer) */

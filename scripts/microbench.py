@@ -5,6 +5,8 @@ Used to A/B kernel variants in one process and as the target of 
     python scripts/microbench.py op         # Activation1d -> operand planes + plane conv per BigVGAN stage
     python scripts/microbench.py conv       # window conv, BigVGAN stage 0-2 / VAE / DiT FFN shapes
     python scripts/microbench.py act        # standalone Activation1d
+    python scripts/microbench.py paste      # alcm_wave_paste in place / out of place
+    python scripts/microbench.py editlong   # 30 s keep-original edit: region decode + paste vs whole-clip decode
 """
 import os
 import sys
@@ -505,9 +507,73 @@ def bench_op1(B=32):
         torch.cuda.synchronize()
 
 
+def _span_mask(B, T, t0=4.0, t1=6.0):
+    from audiolcm_amd.infer_api import spans_to_mask
+    return torch.from_numpy(spans_to_mask([(t0, t1)], T)).expand(B, T).contiguous().cuda()
+
+
+def bench_paste(B=32, N=159744, R=512):
+    """alcm_wave_paste at the bench clip shape with one 2 s span: out of place (every sample copied), in place with gen
+    covering the whole clip, and in place with gen covering the span plus a 32-frame halo as edit_long calls it;
+    alternating, best of 3 x 200 launches, by the library's per-launch events and back to back; bytes from the launch's
+    own profile row (the bytes it touches)"""
+    T = N // 512
+    mask = _span_mask(B, T)
+    frames = mask[0].nonzero().flatten()
+    a, b = max(int(frames[0]) - 32, 0), min(int(frames[-1]) + 1 + 32, T)
+    orig, gen = torch.rand((B, N), device="cuda") * 2 - 1, torch.rand((B, N), device="cuda") * 2 - 1
+    part = gen[:, a * 512:b * 512].contiguous()
+    out, work = torch.empty_like(orig), orig.clone()
+    forms = {"out of place": lambda: K.wave_paste(orig, gen, mask, 0, R, out=out),
+             "in place, whole-clip gen": lambda: K.wave_paste(work, gen, mask, 0, R, out=work),
+             "in place, region gen": lambda: K.wave_paste(work, part, mask, a * 512, R, out=work)}
+    best, ev, nbytes = {k: 1e9 for k in forms}, {k: 1e9 for k in forms}, {}
+    for _ in range(3):
+        for k, fn in forms.items():
+            best[k] = min(best[k], timeit(fn, reps=200))   # back to back: the Python wrapper's time per call included
+        for k, fn in forms.items():
+            _hip.profile_begin()                            # the library's events around each launch
+            for _ in range(200):
+                fn()
+            row = [r for r in _hip.profile_end() if "wave_paste" in r["name"]][0]
+            ev[k], nbytes[k] = min(ev[k], row["total_ms"] / row["launches"]), row["bytes"] / row["launches"]
+    for k in forms:
+        print(f"paste B={B} N={N} R={R} span {int(frames[0])}..{int(frames[-1])} {k:26s}: {ev[k] * 1e3:6.1f} us by events "
+              f"({best[k] * 1e3:6.1f} us per call back to back)  {nbytes[k] / 1e6:7.2f} MB  {nbytes[k] / ev[k] / 1e9:6.3f} TB/s "
+              f"({nbytes[k] / ev[k] / 1e9 / 6.3:5.1%} of 6.3 TB/s achievable)", flush=True)
+
+
+def bench_editlong(L=936, reps=5):
+    """edit_long on a 30 s clip (936 frames, B = 1, mixed policy, one 2 s span) from a waveform: keep_original=True
+    (decode of the span's region + one paste) against keep_original=False (decode of the whole clip); alternating,
+    host clock around a device synchronise"""
+    from audiolcm_amd import recipe
+    from audiolcm_amd.pipeline import AudioLCMPipeline
+    pipe = AudioLCMPipeline.from_recipe(0, split=True, encoder=True)
+    pipe.set_split("mixed")
+    ctx = recipe.synthetic_context(1).cuda()
+    wav = torch.rand((1, L * 512), device="cuda") - 0.5
+    mask = _span_mask(1, L, 14.0, 16.0)
+    times, regions = {True: [], False: []}, None
+    for i in range(2 + reps):
+        for keep in (True, False):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = pipe.edit_long(ctx, [0], wav=wav, mask=mask, keep_original=keep)
+            torch.cuda.synchronize()
+            regions = out.get("regions", regions)
+            if i >= 2:
+                times[keep].append((time.perf_counter() - t0) * 1e3)
+    print(f"editlong L={L} frames {mask[0].nonzero().flatten()[[0, -1]].tolist()} regions {regions}", flush=True)
+    for keep in (True, False):
+        t = sorted(times[keep])
+        print(f"editlong L={L} keep_original={keep!s:5s}: median {t[len(t) // 2]:7.2f} ms  min {t[0]:7.2f}  max {t[-1]:7.2f} "
+              f"({len(t)} calls)", flush=True)
+
+
 if __name__ == "__main__":
     _hip.require_device(0)
     which = sys.argv[1:] or ["op", "conv", "act"]
     spin(float(os.environ.get("SPIN", "3")))
     for w in which:
-        {"tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()
+        {"paste": bench_paste, "editlong": bench_editlong, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()

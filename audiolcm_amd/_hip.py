@@ -103,6 +103,7 @@ _SIGS = [
     ("alcm_latent_init", C.c_int, [fp, fp, fp, C.c_float, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp,
                                    C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_paste", C.c_int, [fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_resample", C.c_int, [fp, fp, C.c_int, i64, C.c_int, i64, C.c_int, C.c_int, fp, C.c_int, C.c_int, vp]),
     ("alcm_sincos_embedding", C.c_int, [fp, C.c_float, fp, C.c_int, C.c_int, C.c_int, fp, vp]),
     ("alcm_model_create", C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(NamedTensor), C.c_int, C.c_int,
                                     C.POINTER(vp)]),

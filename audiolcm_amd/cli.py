@@ -18,6 +18,13 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
     whole latent frames inside the spans window by window and fades them into the input over ``--fade-ms F`` (default
     32) either side: every sample further than F ms from a span is written back as it was read, and each output has
     the input's sample count.  Without it the clip is cropped to the DiT's 845 frames and synthesised again as a whole;
+  * ``--resample``: ``--init-audio`` may have any sample rate, 1 to 8 channels and PCM16, PCM24 or float32 samples; it
+    is downmixed and resampled to 16 kHz on the GPU (alcm_resample; without the flag only 16 kHz mono PCM16 is read).
+    With ``--keep-original`` the edit is done at the recording's own rate: mono, and a rate at which a latent frame is a
+    whole number of samples (48000, 32000, 8000, ...); the output has the input's rate and sample count;
+  * ``--out-sample-rate R`` resamples every output from 16 kHz to R on the GPU and writes R into the header.
+    ``--sample_rate`` (default 22050, the reference's) only labels the header of the 16 kHz samples, as in the
+    reference, and is ignored when ``--out-sample-rate`` is given;
   * ``--synthetic-seed N`` runs on the seeded recipe weights (no checkpoints offline).
 """
 from __future__ import annotations
@@ -32,11 +39,12 @@ import numpy as np
 import torch
 
 from .config import instantiate_from_config, load_config
-from .infer_api import (FRAME_SAMPLES, SAMPLE_RATE, fade_samples_of, keep_original_mask, load_init_audio,
-                        load_init_audio_whole, load_model_from_config, parse_spans, spans_to_mask, struct_caption)
+from .infer_api import (FRAME_SAMPLES, SAMPLE_RATE, check_native_keep_original, check_out_rate, fade_samples_of,
+                        keep_original_mask, load_init_audio, load_init_audio_whole, load_model_from_config,
+                        load_native_audio, parse_spans, spans_to_mask, struct_caption, to_out_rate)
 from .lcm import LCMSampler
 from .models import VocoderBigVGAN
-from .wavio import write_pcm16
+from .wavio import read_audio, write_pcm16
 
 
 def parse_args(argv: Optional[Sequence[str]] = None):
@@ -74,6 +82,12 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                    help="with --inpaint: any clip length; keep the input waveform outside the spans bit for bit")
     p.add_argument("--fade-ms", type=float, default=32.0,
                    help="with --keep-original: the fade between the input and the regenerated audio, either side")
+    p.add_argument("--resample", action="store_true",
+                   help="with --init-audio: read any rate, 1-8 channels, PCM16/PCM24/float32; resample to 16 kHz on "
+                        "the GPU (with --keep-original: edit at the recording's own rate)")
+    p.add_argument("--out-sample-rate", type=int, default=None,
+                   help="resample the output from 16 kHz to this rate on the GPU and write it into the header "
+                        "(--sample_rate only labels the header and is then ignored)")
     p.add_argument("--duration", type=float, default=None,
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--test-dataset-tsv", type=str, default=None, help="override the config's test_dataset tsv_path")
@@ -91,11 +105,17 @@ class GenSamples:
         self.channel_dim = model.channels
         self.original_inference_steps = original_inference_steps
         self.init_wav, self.init_samples = None, None
+        self.init_rate, frame = SAMPLE_RATE, FRAME_SAMPLES
         if opt.init_audio and opt.keep_original:
-            self.init_wav, self.init_samples = load_init_audio_whole(opt.init_audio)
-            self.keep_mask = keep_original_mask(parse_spans(opt.mask_spans), self.init_wav.size // FRAME_SAMPLES)
+            if opt.resample:
+                self.init_wav, self.init_samples, self.init_rate, frame = load_native_audio(opt.init_audio,
+                                                                                            opt.out_sample_rate)
+            else:
+                self.init_wav, self.init_samples = load_init_audio_whole(opt.init_audio)
+            self.keep_mask = keep_original_mask(parse_spans(opt.mask_spans), self.init_wav.size // frame)
         elif opt.init_audio:
-            self.init_wav = load_init_audio(opt.init_audio, model.unet.diffusion_model.cfg.max_latent_len)
+            self.init_wav = load_init_audio(opt.init_audio, model.unet.diffusion_model.cfg.max_latent_len,
+                                            resample=opt.resample)
 
     def generate(self, c, seeds):
         """Conditioning (B, ...) and per-clip seeds -> (mel, waveform (B, 1, L) or None)."""
@@ -111,10 +131,14 @@ class GenSamples:
             from .pipeline import AudioLCMPipeline
             pipe = AudioLCMPipeline(self.model, self.vocoder.generator, steps=self.opt.ddim_steps,
                                     latent_shape=(self.opt.H, self.opt.W), **kw)
-            out = pipe.edit_long(c, seeds, wav=np.broadcast_to(self.init_wav, (B, self.init_wav.size)).copy(),
-                                 mask=np.broadcast_to(self.keep_mask, (B, self.keep_mask.size)).copy(),
-                                 strength=self.opt.strength, keep_original=True,
-                                 fade_samples=fade_samples_of(self.opt.fade_ms))
+            wav = np.broadcast_to(self.init_wav, (B, self.init_wav.size)).copy()
+            mask = np.broadcast_to(self.keep_mask, (B, self.keep_mask.size)).copy()
+            if self.opt.resample:
+                out = pipe.edit_long_native(c, seeds, wav, self.init_rate, mask, strength=self.opt.strength,
+                                            fade_samples=fade_samples_of(self.opt.fade_ms, self.init_rate))
+            else:
+                out = pipe.edit_long(c, seeds, wav=wav, mask=mask, strength=self.opt.strength, keep_original=True,
+                                     fade_samples=fade_samples_of(self.opt.fade_ms))
             return None, out["wav"][:, :self.init_samples].unsqueeze(1)
         if self.init_wav is not None:
             from .mel import MelNet
@@ -150,7 +174,18 @@ class GenSamples:
             B = c.shape[0]
             seeds = [self.clip_seed(first_index + i, it, j) for i in range(len(prompts)) for j in range(n)]
             mel, wav = self.generate(c, seeds)
-            wav = wav.squeeze(1).cpu().numpy() if self.save_wav else None
+            rate = self.opt.sample_rate  # a label on 16 kHz samples, as in the reference
+            if self.save_wav:
+                wav = wav.squeeze(1)
+                if self.opt.keep_original and self.opt.resample:
+                    rate = self.init_rate  # the recording's own rate and samples
+                elif self.opt.keep_original and self.opt.out_sample_rate is not None:
+                    rate = self.opt.out_sample_rate  # 16000, the input's: build() refuses any other
+                elif self.opt.out_sample_rate is not None:
+                    wav, rate = to_out_rate(wav, self.opt.out_sample_rate)
+                wav = wav.cpu().numpy()
+            else:
+                wav = None
             mel_np = mel.cpu().numpy() if mel is not None else None
             for i in range(len(prompts)):
                 for j in range(n):
@@ -163,7 +198,7 @@ class GenSamples:
                         rec["mel_path"] = mp
                     if self.save_wav:
                         wp = os.path.join(self.outpath, f"{names[i]}_{idx}.wav")
-                        write_pcm16(wp, wav[k], self.opt.sample_rate,
+                        write_pcm16(wp, wav[k], rate,
                                     scale=32768.0 if self.opt.keep_original else 32767.0)
                         rec["audio_path"] = wp
                     records[i].append(rec)
@@ -183,6 +218,15 @@ def build(opt):
         raise ValueError("--mask-spans is used with --inpaint")
     if opt.init_audio and opt.duration is not None:
         raise ValueError("--init-audio and --duration do not combine")
+    if opt.resample and not opt.init_audio:
+        raise ValueError("--resample is used with --init-audio")
+    check_out_rate(opt.out_sample_rate)
+    if opt.keep_original and opt.resample:  # the file's rate and channels decide: fail before the models are built
+        x, rate = read_audio(opt.init_audio)
+        check_native_keep_original(opt.init_audio, rate, x.shape[1], opt.out_sample_rate)
+    elif opt.keep_original and opt.out_sample_rate not in (None, SAMPLE_RATE):
+        raise ValueError(f"--keep-original writes the input's own sample rate {SAMPLE_RATE}, not --out-sample-rate "
+                         f"{opt.out_sample_rate}")
     config = load_config(opt.base)
     split = {"split": True, "bf16": "bf16", "mixed": "mixed"}[opt.precision]
     if opt.synthetic_seed is not None:

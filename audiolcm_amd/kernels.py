@@ -396,6 +396,44 @@ def wave_paste(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_st
     return out
 
 
+_resample_taps = {}
+
+
+def resample_taps(rate_in: int, rate_out: int, device):
+    """(plan, device tap table (up, ntaps)) of ``resample.plan(rate_in, rate_out)``, uploaded once per rate pair and
+    device."""
+    from . import resample as _rs
+    key = (int(rate_in), int(rate_out), torch.device(device))
+    if key not in _resample_taps:
+        pl = _rs.plan(int(rate_in), int(rate_out))
+        _resample_taps[key] = (pl, torch.from_numpy(pl.taps.copy()).to(device))
+    return _resample_taps[key]
+
+
+def resample(x: torch.Tensor, rate_in: int, rate_out: int, channels: int = 1) -> torch.Tensor:
+    """Band-limited resampling ``rate_in -> rate_out`` of x (B, N_in), or (B, N_in, channels) interleaved as a WAV file
+    stores it and downmixed to the channel mean in the same launch -> (B, ceil(N_in * up / down)) (alcm_resample; the
+    filter: ``audiolcm_amd/resample.py``).  ``rate_in == rate_out`` with one channel returns ``x`` and launches nothing."""
+    if x.dim() == 2 and channels == 1:
+        x3 = x
+    elif x.dim() == 3 and x.shape[2] == channels:
+        x3 = x
+    else:
+        raise ValueError(f"x must be (B, N_in) or (B, N_in, channels = {channels}), got {tuple(x.shape)}")
+    if int(rate_in) == int(rate_out) and channels == 1:
+        return x if x.dim() == 2 else x[:, :, 0]
+    assert x3.is_cuda and x3.dtype == torch.float32 and x3.is_contiguous()
+    pl, taps = resample_taps(rate_in, rate_out, x3.device)
+    B, n_in = x3.shape[0], x3.shape[1]
+    n_out = pl.out_len(n_in)
+    y = torch.empty((B, n_out), device=x3.device, dtype=torch.float32)
+    if B == 0 or n_in == 0:
+        return y
+    check(lib().alcm_resample(ptr(x3), ptr(y), B, n_in, int(channels), n_out, pl.up, pl.down, ptr(taps), pl.ntaps,
+                              pl.first, stream_handle()), "resample")
+    return y
+
+
 def sincos_embedding(v: torch.Tensor, freqs: torch.Tensor, scale: float, cos_first: bool) -> torch.Tensor:
     B = v.shape[0]
     half = freqs.numel()

@@ -18,6 +18,7 @@ from .models import AutoencoderKL, BigVGAN, ConcatDiT2MLP
 
 
 FRAME_SAMPLES = 512  # one latent frame = 2 mel frames x hop 256
+SAMPLE_RATE = 16000
 
 
 def edit_windows(union, window: int, overlap: Optional[int] = None):
@@ -166,7 +167,6 @@ class AudioLCMPipeline:
         if keep_original and wav is None:
             raise ValueError("keep_original needs the input waveform `wav`")
         dev = torch.device("cuda")
-        S = steps or self.steps
         if wav is not None:
             wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
             if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES:
@@ -189,41 +189,110 @@ class AudioLCMPipeline:
             if halo_frames * FRAME_SAMPLES < fade_samples and any(a > 0 or b < L for a, b in regions):
                 raise ValueError("halo_frames * 512 must be at least fade_samples: the fade has to end inside the "
                                  "decoded region")
-        if any(union) and L <= W:
-            z = self._edit_latent(cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
-                                  cfg_scale)
-        else:
-            if wav is not None:
-                post = self._encode(wav)
-                e0 = None
-                if sample_posterior:
-                    Cc = post.parameters.shape[1] // 2
-                    e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(dev) if seeds is not None
-                          else torch.randn((B, Cc, L), device=dev))
-                z = kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
-                                        scale=float(self.model.scale_factor), want_x=False)[0]
-            else:
-                z = latent.to(dev).float().clone()
-            if any(union):
-                m = torch.ones((B, L)) if mask is None else mask.cpu().clone()
-                for k, s in enumerate(edit_windows(union, W, overlap)[0]):
-                    wseeds = None if seeds is None else [recipe.window_seed(sd, k) for sd in seeds]
-                    zk, _ = self.sampler.sample_edit(S=S, conditioning=cond, init=z[:, :, s:s + W].contiguous(),
-                                                     mask=m[:, s:s + W], strength=strength, seeds=wseeds,
-                                                     guidance_scale=self.guidance_scale,
-                                                     original_inference_steps=self.original_inference_steps,
-                                                     unconditional_conditioning=unconditional,
-                                                     unconditional_guidance_scale=cfg_scale)
-                    z[:, :, s:s + W] = zk
-                    m[:, s:s + W] = 0.0
+        z = self._edit_long_latent(cond, seeds, wav, latent, mask, union, W, overlap, strength, sample_posterior, steps,
+                                   unconditional, cfg_scale)
         if not keep_original:
             return dict(latent=z, **self.decode(z))
         out = wav.clone()
         pm = torch.ones((B, L), device=dev) if mask is None else mask.to(dev).contiguous()
+        self._paste_regions(out, z, pm, regions, fade_samples)
+        return dict(latent=z, wav=out, regions=regions)
+
+    def _edit_long_latent(self, cond, seeds, wav, latent, mask, union, W, overlap, strength, sample_posterior, steps,
+                          unconditional, cfg_scale):
+        """The latent of ``edit_long``: ``wav`` (B, L * 512) on the device or ``latent`` (B, C, L), ``mask`` (B, L) on
+        the host or None, ``union`` its per-frame any over the batch, W the window length."""
+        from . import kernels
+        dev = torch.device("cuda")
+        S = steps or self.steps
+        L = len(union)
+        B = wav.shape[0] if wav is not None else latent.shape[0]
+        if any(union) and L <= W:
+            return self._edit_latent(cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
+                                     cfg_scale)
+        if wav is not None:
+            post = self._encode(wav)
+            e0 = None
+            if sample_posterior:
+                Cc = post.parameters.shape[1] // 2
+                e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(dev) if seeds is not None
+                      else torch.randn((B, Cc, L), device=dev))
+            z = kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
+                                    scale=float(self.model.scale_factor), want_x=False)[0]
+        else:
+            z = latent.to(dev).float().clone()
+        if any(union):
+            m = torch.ones((B, L)) if mask is None else mask.cpu().clone()
+            for k, s in enumerate(edit_windows(union, W, overlap)[0]):
+                wseeds = None if seeds is None else [recipe.window_seed(sd, k) for sd in seeds]
+                zk, _ = self.sampler.sample_edit(S=S, conditioning=cond, init=z[:, :, s:s + W].contiguous(),
+                                                 mask=m[:, s:s + W], strength=strength, seeds=wseeds,
+                                                 guidance_scale=self.guidance_scale,
+                                                 original_inference_steps=self.original_inference_steps,
+                                                 unconditional_conditioning=unconditional,
+                                                 unconditional_guidance_scale=cfg_scale)
+                z[:, :, s:s + W] = zk
+                m[:, s:s + W] = 0.0
+        return z
+
+    def _paste_regions(self, out, z, pm, regions, fade_samples, rate: int = SAMPLE_RATE,
+                       frame_samples: int = FRAME_SAMPLES):
+        """The paste of ``edit_long(keep_original=True)``: each region [a, b) of latent frames is decoded, resampled
+        from 16 kHz to ``rate`` when that is another one ((b - a) * frame_samples samples exactly) and blended into
+        ``out`` (B, N at ``rate``) in place by one ``kernels.wave_paste``."""
+        from . import kernels
         for a, b in regions:
             gen = self.decode(z[:, :, a:b].contiguous())["wav"].contiguous()
-            kernels.wave_paste(out, gen, pm, gen_start=a * FRAME_SAMPLES, fade_samples=fade_samples,
-                               frame_samples=FRAME_SAMPLES, out=out)
+            if rate != SAMPLE_RATE:
+                gen = kernels.resample(gen, SAMPLE_RATE, rate)
+                assert gen.shape[1] == (b - a) * frame_samples
+            kernels.wave_paste(out, gen, pm, gen_start=a * frame_samples, fade_samples=fade_samples,
+                               frame_samples=frame_samples, out=out)
+
+    @torch.no_grad()
+    def edit_long_native(self, cond: torch.Tensor, seeds: Sequence[int], wav, rate: int, mask,
+                         strength: float = 0.5, window: Optional[int] = None, overlap: Optional[int] = None,
+                         sample_posterior: bool = True, steps: Optional[int] = None,
+                         unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
+                         fade_samples: int = 1536, halo_frames: int = 32) -> Dict[str, torch.Tensor]:
+        """``edit_long(keep_original=True)`` on a recording at its own sample rate.  ``wav`` (B, N) at ``rate``, where one
+        latent frame is a whole number F = 512 * rate / 16000 of samples (48000, 32000, 8000, 96000, ...; ValueError
+        otherwise) and N a multiple of F.  The recording is resampled to 16 kHz (``kernels.resample``) for the encoder
+        only; the latent is ``edit_long``'s for those 16 kHz samples.  Each decoded region is resampled back up, which
+        gives (b - a) * F samples exactly, and pasted into a copy of ``wav`` by ``kernels.wave_paste`` with
+        ``frame_samples`` = F and a fade of ``fade_samples`` samples at ``rate``: samples further than that from a
+        regenerated frame keep their bits.  ``halo_frames`` * 512 >= the fade in 16 kHz samples + |first| + 1 (``first``
+        of the 16000 -> rate filter, ``resample.plan``) is required, so that the upsampler's transient at the edges of
+        a decoded region stays outside the fade.  Returns latent, wav (B, N) and regions."""
+        from . import kernels, resample as rs
+        F = rs.frame_samples_at(rate, SAMPLE_RATE, FRAME_SAMPLES)
+        if F is None:
+            raise ValueError(f"sample rate {rate}: a latent frame is {FRAME_SAMPLES} * rate / {SAMPLE_RATE} samples, which "
+                             "must be whole (multiples of 125 Hz: 8000, 16000, 32000, 48000, 96000)")
+        dev = torch.device("cuda")
+        wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
+        if wav.dim() != 2 or wav.shape[1] % F:
+            raise ValueError(f"`wav` is (B, N) with N a multiple of {F}")
+        B, L = wav.shape[0], wav.shape[1] // F
+        mask = torch.as_tensor(mask, dtype=torch.float32)
+        if tuple(mask.shape) != (B, L):
+            raise ValueError(f"mask must be (B, L) = {(B, L)}, got {tuple(mask.shape)}")
+        if not 0 <= fade_samples <= kernels.PASTE_MAX_FADE_FRAMES * F:
+            raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * F}")
+        fade16 = -(-fade_samples * SAMPLE_RATE // rate)
+        reach = fade16 + abs(rs.plan(SAMPLE_RATE, rate).first) + 1 if rate != SAMPLE_RATE else fade16
+        if halo_frames * FRAME_SAMPLES < reach:
+            raise ValueError(f"halo_frames * 512 must be at least {reach}: the fade ({fade16} samples at 16 kHz) and the "
+                             "resampling filter's reach have to end inside the decoded region")
+        union = (mask > 0).any(0).tolist()
+        regions = paste_regions(union, halo_frames)
+        W = min(window or self.latent_shape[1], L)
+        wav16 = kernels.resample(wav, rate, SAMPLE_RATE)
+        assert wav16.shape[1] == L * FRAME_SAMPLES
+        z = self._edit_long_latent(cond, seeds, wav16, None, mask, union, W, overlap, strength, sample_posterior, steps,
+                                   unconditional, cfg_scale)
+        out = wav.clone()
+        self._paste_regions(out, z, mask.to(dev).contiguous(), regions, fade_samples, rate, F)
         return dict(latent=z, wav=out, regions=regions)
 
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):

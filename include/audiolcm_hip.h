@@ -315,6 +315,20 @@ int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, 
  * launch (Ng = 0 out of place copies orig). */
 int alcm_wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
                     int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R, alcm_stream_t stream);
+/* alcm_resample: band-limited rational resampling of a batch of clips with the mean over the channels folded into
+ * the read, one launch (no reference counterpart: the reference labels its 16 kHz samples with any rate it is given).
+ *   x (B, N_in, channels), interleaved as a WAV file stores it; y (B, N_out), N_out = ceil(N_in * up / down);
+ *   taps (up, ntaps), device: row r holds the filter at the offsets k + first - r / up, k = 0 .. ntaps - 1, in input
+ *   samples (audiolcm_amd/resample.py plans it per rate pair: up / down = rate_out / rate_in in lowest terms);
+ *   y[b][n] = sum_k taps[(n * down) mod up][k] * xm[b][floor(n * down / up) + first + k], xm the channel mean of x and 0
+ *   outside [0, N_in): output n sits at input position n * down / up.
+ * Index arithmetic is 64-bit.  Each output is one fp32 fmaf chain over k in rising order, whatever B, the output's
+ * position or the alignment of x (element loads; 8-byte loads for stereo at an 8-byte aligned x).  No atomics.
+ * ALCM_E_INVALID for a null x, y or taps, up, down or ntaps < 1, channels outside 1 .. 8, a negative size,
+ * N_out != ceil(N_in * up / down), or a rate pair so far apart that 256 outputs' input window exceeds 48 KiB of LDS.
+ * B or N_in of 0: no launch. */
+int alcm_resample(const float* x, float* y, int B, int64_t N_in, int channels, int64_t N_out, int up, int down,
+                  const float* taps, int ntaps, int first, alcm_stream_t stream);
 /* out[b] = [f(v[b]*vscale*freqs[i]) ...]: cos_first ? [cos | sin] (TimestepEmbedder, concatDiT.py:49-67)
  *                                                   : [sin | cos] (get_guidance_scale_embedding, w*1000).
  * freqs: the reference's fp32 frequency table (half entries, device pointer) */

@@ -6,6 +6,7 @@ Used to A/B kernel variants in one process and as the target of 
     python scripts/microbench.py conv       # window conv, BigVGAN stage 0-2 / VAE / DiT FFN shapes
     python scripts/microbench.py act        # standalone Activation1d
     python scripts/microbench.py paste      # alcm_wave_paste in place / out of place
+    python scripts/microbench.py resample   # alcm_resample on the recorded shapes
     python scripts/microbench.py editlong   # 30 s keep-original edit: region decode + paste vs whole-clip decode
 """
 import os
@@ -543,6 +544,29 @@ def bench_paste(B=32, N=159744, R=512):
               f"({nbytes[k] / ev[k] / 1e9 / 6.3:5.1%} of 6.3 TB/s achievable)", flush=True)
 
 
+def bench_resample():
+    """alcm_resample on the two recorded shapes: 48000 -> 16000 on a 5-minute stereo clip and 16000 -> 48000 on a 30 s
+    clip, then the 441-row pairs on 30 s; best of 3 x 50 launches by the library's per-launch events, bytes from the
+    launch's own profile row, beside the HBM roof (bytes / 8 TB/s)"""
+    cases = [("48000->16000 5 min stereo", 48000, 16000, 2, 300), ("16000->48000 30 s mono", 16000, 48000, 1, 30),
+             ("44100->16000 30 s stereo", 44100, 16000, 2, 30), ("16000->44100 30 s mono", 16000, 44100, 1, 30)]
+    for name, ri, ro, ch, sec in cases:
+        x = torch.rand((1, ri * sec, ch), device="cuda") * 2 - 1
+        x = x if ch > 1 else x[:, :, 0].contiguous()
+        K.resample(x, ri, ro, channels=ch)
+        torch.cuda.synchronize()
+        ev, nbytes, flops = 1e9, 0.0, 0.0
+        for _ in range(3):
+            _hip.profile_begin()
+            for _ in range(50):
+                K.resample(x, ri, ro, channels=ch)
+            row = [r for r in _hip.profile_end() if "resample" in r["name"]][0]
+            ev = min(ev, row["total_ms"] / row["launches"])
+            nbytes, flops, kname = row["bytes"] / row["launches"], row["flops"] / row["launches"], row["name"]
+        print(f"resample {name:26s} {kname}: {ev * 1e3:8.1f} us by events  {nbytes / 1e6:7.2f} MB  HBM roof "
+              f"{nbytes / 8e12 * 1e6:6.1f} us  {nbytes / ev / 1e9:6.3f} TB/s  {flops / ev / 1e9:6.2f} TFLOP/s fp32", flush=True)
+
+
 def bench_editlong(L=936, reps=5):
     """edit_long on a 30 s clip (936 frames, B = 1, mixed policy, one 2 s span) from a waveform: keep_original=True
     (decode of the span's region + one paste) against keep_original=False (decode of the whole clip); alternating,
@@ -576,4 +600,4 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["op", "conv", "act"]
     spin(float(os.environ.get("SPIN", "3")))
     for w in which:
-        {"paste": bench_paste, "editlong": bench_editlong, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()
+        {"resample": bench_resample, "paste": bench_paste, "editlong": bench_editlong, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()

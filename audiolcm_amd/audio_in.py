@@ -1,0 +1,204 @@
+"""The audio-input half of the front end: reading ``--init-audio`` / ``init_audio`` and planning the request.
+
+``plan_edit`` is the one place that decides what an audio-conditioned request is (a variation, an inpainting of the
+cropped clip, or a keep-original inpainting at 16 kHz or at the recording's own rate) and the one place that refuses
+one; ``AudioLCMPipeline.run_edit`` turns its ``EditPlan`` into audio.  The command line and ``AudioLCMEditInfer`` are
+callers of the two.  Importing this module does not touch the GPU (``kernels`` is imported where a file has to be
+resampled).
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .resample import frame_samples_at
+from .wavio import read_audio, read_wav
+
+SAMPLE_RATE = 16000
+FRAME_SAMPLES = 512  # one latent frame = 2 mel frames x hop 256
+
+
+def parse_spans(text: str) -> List[Tuple[float, float]]:
+    """``"2.0-4.5,7-8"`` -> [(2.0, 4.5), (7.0, 8.0)] (seconds)."""
+    spans = []
+    for part in text.split(","):
+        if not part.strip():
+            continue
+        try:
+            a, b = part.split("-")
+            spans.append((float(a), float(b)))
+        except ValueError:
+            raise ValueError(f"bad span {part!r}: expected START-END in seconds") from None
+    return spans
+
+
+def spans_to_mask(spans: Optional[Sequence[Tuple[float, float]]], n_frames: int, sample_rate: int = SAMPLE_RATE,
+                  frame_samples: int = FRAME_SAMPLES, inward: bool = False) -> np.ndarray:
+    """(n_frames,) float32 regenerate-mask of the time spans [t0, t1) in seconds: span -> latent frames
+    floor(sample_rate * t0 / frame_samples) up to (not including) ceil(sample_rate * t1 / frame_samples), so a span
+    ending mid-frame takes that frame too; clipped to the clip.  ``inward``: only the frames that lie wholly inside a
+    span (ceil at the start, floor at the end), so that nothing outside the span is regenerated."""
+    mask = np.zeros((n_frames,), dtype=np.float32)
+    first, last = (math.ceil, math.floor) if inward else (math.floor, math.ceil)
+    for t0, t1 in spans or ():
+        if t1 <= t0:
+            continue
+        lo = max(0, first(sample_rate * t0 / frame_samples))
+        hi = min(n_frames, last(sample_rate * t1 / frame_samples))
+        mask[lo:hi] = 1.0
+    return mask
+
+
+def keep_original_mask(spans: Sequence[Tuple[float, float]], n_frames: int) -> np.ndarray:
+    """The mask of a keep-original inpainting: the whole frames inside the spans, so that with a fade of F samples no
+    sample further than F from a span changes.  ValueError when no span holds a whole frame."""
+    mask = spans_to_mask(spans, n_frames, inward=True)
+    if not mask.any():
+        raise ValueError(f"no whole latent frame ({1000 * FRAME_SAMPLES // SAMPLE_RATE} ms) lies inside the spans "
+                         f"{list(spans)}")
+    return mask
+
+
+def fade_samples_of(fade_ms: float, sample_rate: int = SAMPLE_RATE) -> int:
+    return int(round(fade_ms * sample_rate / 1000.0))
+
+
+def frame_samples_of(rate: int) -> int:
+    """The samples of one latent frame at ``rate``; ValueError for a rate at which that is not a whole number."""
+    F = frame_samples_at(rate, SAMPLE_RATE, FRAME_SAMPLES)
+    if F is None:
+        raise ValueError(f"sample rate {rate}: keep_original pastes whole latent frames of {FRAME_SAMPLES} * rate / "
+                         f"{SAMPLE_RATE} samples, so it takes multiples of 125 Hz: 8000, 16000, 32000, 48000, 96000")
+    return F
+
+
+def check_native_keep_original(path: str, rate: int, channels: int, out_sample_rate: Optional[int]) -> int:
+    """What a keep-original edit of a file needs; returns the samples F of one latent frame at the file's rate."""
+    if channels != 1:
+        raise ValueError(f"{path}: {channels} channels; keep_original keeps the input's samples bit for bit, which a "
+                         "downmix cannot: pass a mono file")
+    F = frame_samples_of(rate)
+    if out_sample_rate is not None and out_sample_rate != rate:
+        raise ValueError(f"{path}: keep_original writes the input's own sample rate {rate}, not out_sample_rate "
+                         f"{out_sample_rate}")
+    return F
+
+
+def _read_mono(path: str, resample: bool, own_rate: bool = False,
+               out_sample_rate: Optional[int] = None) -> Tuple[np.ndarray, int, int]:
+    """One read of ``path`` -> (mono float32 samples, their rate, the samples of one latent frame at that rate).
+    Without ``resample`` only 16 kHz mono PCM16 is read (``read_wav``); with it any rate, 1 to 8 channels and PCM16 /
+    PCM24 / float32 (``read_audio``).  The samples are downmixed and resampled to 16 kHz on the GPU, unless
+    ``own_rate``: then they are the file's own, which ``check_native_keep_original`` has to allow."""
+    if resample:
+        x, rate = read_audio(path)
+    else:
+        x, rate = read_wav(path)
+        x = x[:, None]
+        if rate != SAMPLE_RATE:
+            raise ValueError(f"{path}: sample rate {rate}, need {SAMPLE_RATE} (resampling is not done here; pass "
+                             "resample=True, --resample on the command line, to resample on the GPU)")
+    F = check_native_keep_original(path, rate, x.shape[1], out_sample_rate) if own_rate else FRAME_SAMPLES
+    if x.shape[0] == 0:
+        raise ValueError(f"{path}: no samples")
+    if own_rate:
+        return np.ascontiguousarray(x[:, 0]), rate, F
+    return _to_16k_mono(x, rate), SAMPLE_RATE, F
+
+
+def _to_16k_mono(x: np.ndarray, rate: int) -> np.ndarray:
+    """(N, channels) at ``rate`` -> (N16,) at 16 kHz: the channel mean and the resampling in one ``kernels.resample``."""
+    if rate == SAMPLE_RATE and x.shape[1] == 1:
+        return np.ascontiguousarray(x[:, 0])
+    from . import kernels
+    xd = torch.from_numpy(np.ascontiguousarray(x)).cuda()[None]
+    return kernels.resample(xd, rate, SAMPLE_RATE, channels=x.shape[1])[0].cpu().numpy()
+
+
+def _pad_to_frames(x: np.ndarray, frame_samples: int = FRAME_SAMPLES) -> np.ndarray:
+    return np.pad(x, (0, -x.size % frame_samples))
+
+
+def load_init_audio(path: str, max_frames: Optional[int] = None, resample: bool = False) -> np.ndarray:
+    """16 kHz mono PCM16 WAV -> float32 samples, zero-padded up to a whole number of latent frames (512 samples) and
+    cropped to ``max_frames`` of them (the DiT's length limit) when given.  Another sample rate raises ValueError,
+    unless ``resample``: then the file is read by ``read_audio`` (any rate, 1 to 8 channels, PCM16 / PCM24 / float32)
+    and downmixed and resampled to 16 kHz on the GPU first."""
+    x = load_init_audio_whole(path, resample)[0]
+    return x if max_frames is None else x[:max_frames * FRAME_SAMPLES]
+
+
+def load_init_audio_whole(path: str, resample: bool = False) -> Tuple[np.ndarray, int]:
+    """``load_init_audio`` without a crop, and the sample count before padding (a keep-original edit writes that
+    many)."""
+    x = _read_mono(path, resample)[0]
+    return _pad_to_frames(x), x.size
+
+
+def load_native_audio(path: str, out_sample_rate: Optional[int] = None) -> Tuple[np.ndarray, int, int, int]:
+    """The input of a keep-original edit at the recording's own rate: (mono float32 samples zero-padded to whole latent
+    frames, the file's sample count, its rate, the samples F of one latent frame at that rate).  ValueError for more
+    than one channel, a rate at which F is not whole, or an ``out_sample_rate`` that is not the file's."""
+    x, rate, F = _read_mono(path, True, True, out_sample_rate)
+    return _pad_to_frames(x, F), x.size, rate, F
+
+
+def check_out_rate(out_sample_rate: Optional[int]) -> Optional[int]:
+    if out_sample_rate is not None and (int(out_sample_rate) != out_sample_rate or out_sample_rate < 1):
+        raise ValueError(f"out_sample_rate must be a positive whole number of Hz, got {out_sample_rate!r}")
+    return None if out_sample_rate is None else int(out_sample_rate)
+
+
+def to_out_rate(wav: torch.Tensor, out_sample_rate: Optional[int]) -> Tuple[torch.Tensor, int]:
+    """(B, L) at 16 kHz on the device -> (the waveform at ``out_sample_rate``, that rate); None keeps 16 kHz."""
+    if out_sample_rate is None or out_sample_rate == SAMPLE_RATE:
+        return wav, SAMPLE_RATE
+    from . import kernels
+    return kernels.resample(wav.contiguous(), SAMPLE_RATE, out_sample_rate), out_sample_rate
+
+
+# ---------------------------------------------------------------------------- the request plan
+@dataclass(frozen=True, eq=False)
+class EditPlan:
+    """What ``plan_edit`` decided about one audio-conditioned request; ``AudioLCMPipeline.run_edit`` runs it."""
+    mode: str                                           # "variation", "inpaint" or "keep_original"
+    samples: np.ndarray                                 # mono float32 at `rate`, zero-padded to whole latent frames
+    n_samples: int                                      # the sample count before padding
+    rate: int                                           # the rate the edit runs at
+    frame_samples: int                                  # the samples of one latent frame at `rate`
+    spans: Optional[Tuple[Tuple[float, float], ...]]    # inpaint: the spans to regenerate, in seconds
+    mask: Optional[np.ndarray]                          # keep_original: (frames,) 1 = regenerate
+    fade: int                                           # `fade_ms` in samples at `rate`
+    out_rate: int                                       # the rate to write into the header
+    resample_out: bool                                  # the output is resampled from 16 kHz to `out_rate`
+    pcm_scale: float                                    # PCM16 scale: 32768 gives kept samples back bit for bit
+    native: bool                                        # keep_original with resample: the file's own rate was read,
+    #                                                     so the header rate is no label on 16 kHz samples
+
+
+def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]]] = None, keep_original: bool = False,
+              fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
+              max_frames: Optional[int] = None) -> EditPlan:
+    """Reads ``init_audio`` once and decides the request, or refuses it with ValueError.  No ``mask_spans``: a
+    variation; with them: an inpainting of the clip (both crop to ``max_frames`` latent frames here when given;
+    ``run_edit`` crops to the DiT's limit in any case); ``keep_original``: the whole frames inside the spans are
+    regenerated in a clip of any length, at 16 kHz or, with ``resample``, at the recording's own rate."""
+    if keep_original and not mask_spans:
+        raise ValueError("keep_original needs mask_spans: the time spans to regenerate")
+    out_sample_rate = check_out_rate(out_sample_rate)
+    x, rate, F = _read_mono(init_audio, resample, keep_original, out_sample_rate)
+    samples = _pad_to_frames(x, F)
+    spans = mask = None
+    if keep_original:
+        mode, mask = "keep_original", keep_original_mask(mask_spans, samples.size // F)
+    else:
+        mode = "variation" if mask_spans is None else "inpaint"
+        spans = None if mask_spans is None else tuple((float(a), float(b)) for a, b in mask_spans)
+        samples = samples if max_frames is None else samples[:max_frames * F]
+    out_rate = rate if keep_original else out_sample_rate or SAMPLE_RATE
+    return EditPlan(mode, samples, x.size, rate, F, spans, mask, fade_samples_of(fade_ms, rate), out_rate,
+                    out_rate != rate, 32768.0 if keep_original else 32767.0, keep_original and resample)

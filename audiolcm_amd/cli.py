@@ -30,6 +30,7 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
 from __future__ import annotations
 
 import argparse
+import functools
 import math
 import os
 import sys
@@ -38,13 +39,11 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from .audio_in import FRAME_SAMPLES, SAMPLE_RATE, EditPlan, check_out_rate, parse_spans, plan_edit, to_out_rate
 from .config import instantiate_from_config, load_config
-from .infer_api import (FRAME_SAMPLES, SAMPLE_RATE, check_native_keep_original, check_out_rate, fade_samples_of,
-                        keep_original_mask, load_init_audio, load_init_audio_whole, load_model_from_config,
-                        load_native_audio, parse_spans, spans_to_mask, struct_caption, to_out_rate)
+from .infer_api import build_models, struct_caption
 from .lcm import LCMSampler
-from .models import VocoderBigVGAN
-from .wavio import read_audio, write_pcm16
+from .wavio import write_pcm16
 
 
 def parse_args(argv: Optional[Sequence[str]] = None):
@@ -98,65 +97,46 @@ class GenSamples:
     """scripts/txt2audio_for_lcm.py:96-147 (GenSamples.gen_test_sample), batched over prompts."""
 
     def __init__(self, opt, sampler: LCMSampler, model, outpath: str, vocoder, save_mel: bool = True,
-                 save_wav: bool = True, original_inference_steps: Optional[int] = None):
+                 save_wav: bool = True, original_inference_steps: Optional[int] = None,
+                 plan: Optional[EditPlan] = None):
+        """``plan``: ``build``'s plan of the ``--init-audio`` request every prompt starts from."""
         self.opt, self.sampler, self.model, self.outpath = opt, sampler, model, outpath
         self.vocoder = vocoder
         self.save_mel, self.save_wav = save_mel, save_wav
         self.channel_dim = model.channels
         self.original_inference_steps = original_inference_steps
-        self.init_wav, self.init_samples = None, None
-        self.init_rate, frame = SAMPLE_RATE, FRAME_SAMPLES
-        if opt.init_audio and opt.keep_original:
-            if opt.resample:
-                self.init_wav, self.init_samples, self.init_rate, frame = load_native_audio(opt.init_audio,
-                                                                                            opt.out_sample_rate)
-            else:
-                self.init_wav, self.init_samples = load_init_audio_whole(opt.init_audio)
-            self.keep_mask = keep_original_mask(parse_spans(opt.mask_spans), self.init_wav.size // frame)
-        elif opt.init_audio:
-            self.init_wav = load_init_audio(opt.init_audio, model.unet.diffusion_model.cfg.max_latent_len,
-                                            resample=opt.resample)
+        self.plan = plan
+
+    @functools.cached_property
+    def pipeline(self):
+        """Built at the first long-form or audio-conditioned batch; plain text-to-audio runs on ``sampler`` alone."""
+        from .pipeline import AudioLCMPipeline
+        return AudioLCMPipeline(self.model, self.vocoder.generator, steps=self.opt.ddim_steps,
+                                guidance_scale=self.opt.scale, latent_shape=(self.opt.H, self.opt.W),
+                                original_inference_steps=self.original_inference_steps)
 
     def generate(self, c, seeds):
-        """Conditioning (B, ...) and per-clip seeds -> (mel, waveform (B, 1, L) or None)."""
-        B = c.shape[0]
-        kw = dict(guidance_scale=self.opt.scale, original_inference_steps=self.original_inference_steps)
+        """Conditioning (B, ...) and per-clip seeds -> (mel or None, waveform (B, L) on the device or None, the rate for
+        the header, the PCM16 scale)."""
+        label = self.opt.out_sample_rate is None  # --sample_rate labels 16 kHz samples, as in the reference
+        if self.plan is not None:
+            wav, rate, mel = self.pipeline.run_edit(self.plan, c, seeds, self.opt.strength)
+            return mel, wav, self.opt.sample_rate if label and not self.plan.native else rate, self.plan.pcm_scale
         if self.opt.duration is not None:
-            from .pipeline import AudioLCMPipeline
-            pipe = AudioLCMPipeline(self.model, self.vocoder.generator, steps=self.opt.ddim_steps,
-                                    latent_shape=(self.opt.H, self.opt.W), **kw)
-            out = pipe.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES))
-            return out["mel"], out["wav"].unsqueeze(1)
-        if self.opt.keep_original:
-            from .pipeline import AudioLCMPipeline
-            pipe = AudioLCMPipeline(self.model, self.vocoder.generator, steps=self.opt.ddim_steps,
-                                    latent_shape=(self.opt.H, self.opt.W), **kw)
-            wav = np.broadcast_to(self.init_wav, (B, self.init_wav.size)).copy()
-            mask = np.broadcast_to(self.keep_mask, (B, self.keep_mask.size)).copy()
-            if self.opt.resample:
-                out = pipe.edit_long_native(c, seeds, wav, self.init_rate, mask, strength=self.opt.strength,
-                                            fade_samples=fade_samples_of(self.opt.fade_ms, self.init_rate))
-            else:
-                out = pipe.edit_long(c, seeds, wav=wav, mask=mask, strength=self.opt.strength, keep_original=True,
-                                     fade_samples=fade_samples_of(self.opt.fade_ms))
-            return None, out["wav"][:, :self.init_samples].unsqueeze(1)
-        if self.init_wav is not None:
-            from .mel import MelNet
-            from .models import DiagonalGaussianDistribution
-            post = self.model.encode_first_stage(MelNet()(self.init_wav))
-            T = post.mean.shape[2]
-            mask = None
-            if self.opt.inpaint:
-                mask = torch.from_numpy(spans_to_mask(parse_spans(self.opt.mask_spans), T)).expand(B, T)
-            init = DiagonalGaussianDistribution(post.parameters.expand(B, -1, -1).contiguous())
-            z, _ = self.sampler.sample_edit(S=self.opt.ddim_steps, conditioning=c, init=init, mask=mask,
-                                            strength=self.opt.strength, seeds=seeds, **kw)
+            out = self.pipeline.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES))
+            mel, wav = out["mel"], out["wav"]
         else:
+            B = c.shape[0]
             shape = [self.channel_dim, self.opt.H, self.opt.W] if self.channel_dim > 0 else [self.opt.H, self.opt.W]
             z, _ = self.sampler.sample(S=self.opt.ddim_steps, conditioning=c, batch_size=B, shape=shape,
-                                       verbose=False, seeds=seeds, **kw)
-        mel = self.model.decode_first_stage(z)
-        return mel, self.vocoder.vocode(mel) if self.save_wav else None
+                                       verbose=False, seeds=seeds, guidance_scale=self.opt.scale,
+                                       original_inference_steps=self.original_inference_steps)
+            mel = self.model.decode_first_stage(z)
+            wav = self.vocoder.vocode(mel).squeeze(1) if self.save_wav else None
+        rate = self.opt.sample_rate
+        if wav is not None and not label:
+            wav, rate = to_out_rate(wav, self.opt.out_sample_rate)
+        return mel, wav, rate, 32767.0
 
     def clip_seed(self, prompt_index: int, it: int, j: int) -> int:
         """RNG seed of sample j of iteration `it` of the prompt at global index `prompt_index` (batch-invariant)."""
@@ -171,21 +151,9 @@ class GenSamples:
             text = {"ori_caption": [p["ori_caption"] for p in prompts for _ in range(n)],
                     "struct_caption": [p["struct_caption"] for p in prompts for _ in range(n)]}
             c = self.model.get_learned_conditioning(text)
-            B = c.shape[0]
             seeds = [self.clip_seed(first_index + i, it, j) for i in range(len(prompts)) for j in range(n)]
-            mel, wav = self.generate(c, seeds)
-            rate = self.opt.sample_rate  # a label on 16 kHz samples, as in the reference
-            if self.save_wav:
-                wav = wav.squeeze(1)
-                if self.opt.keep_original and self.opt.resample:
-                    rate = self.init_rate  # the recording's own rate and samples
-                elif self.opt.keep_original and self.opt.out_sample_rate is not None:
-                    rate = self.opt.out_sample_rate  # 16000, the input's: build() refuses any other
-                elif self.opt.out_sample_rate is not None:
-                    wav, rate = to_out_rate(wav, self.opt.out_sample_rate)
-                wav = wav.cpu().numpy()
-            else:
-                wav = None
+            mel, wav, rate, scale = self.generate(c, seeds)
+            wav = wav.cpu().numpy() if self.save_wav else None
             mel_np = mel.cpu().numpy() if mel is not None else None
             for i in range(len(prompts)):
                 for j in range(n):
@@ -198,8 +166,7 @@ class GenSamples:
                         rec["mel_path"] = mp
                     if self.save_wav:
                         wp = os.path.join(self.outpath, f"{names[i]}_{idx}.wav")
-                        write_pcm16(wp, wav[k], rate,
-                                    scale=32768.0 if self.opt.keep_original else 32767.0)
+                        write_pcm16(wp, wav[k], rate, scale=scale)
                         rec["audio_path"] = wp
                     records[i].append(rec)
         return [r for rs in records for r in rs]
@@ -221,38 +188,28 @@ def build(opt):
     if opt.resample and not opt.init_audio:
         raise ValueError("--resample is used with --init-audio")
     check_out_rate(opt.out_sample_rate)
-    if opt.keep_original and opt.resample:  # the file's rate and channels decide: fail before the models are built
-        x, rate = read_audio(opt.init_audio)
-        check_native_keep_original(opt.init_audio, rate, x.shape[1], opt.out_sample_rate)
-    elif opt.keep_original and opt.out_sample_rate not in (None, SAMPLE_RATE):
-        raise ValueError(f"--keep-original writes the input's own sample rate {SAMPLE_RATE}, not --out-sample-rate "
-                         f"{opt.out_sample_rate}")
+    # the file and the flags decide: a refused request fails before the models are built
+    plan = plan_edit(opt.init_audio, parse_spans(opt.mask_spans) if opt.inpaint else None, opt.keep_original,
+                     opt.fade_ms, opt.resample, opt.out_sample_rate) if opt.init_audio else None
     config = load_config(opt.base)
     split = {"split": True, "bf16": "bf16", "mixed": "mixed"}[opt.precision]
-    if opt.synthetic_seed is not None:
-        model = load_model_from_config(config, None, split=split, synthetic_seed=opt.synthetic_seed,
-                                       encoder=bool(opt.init_audio))
-        from . import recipe
-        vocoder = VocoderBigVGAN(state=recipe.bigvgan_state(opt.synthetic_seed), split=split)
-    else:
+    if opt.synthetic_seed is None:
         if not opt.resume or not os.path.exists(str(opt.resume)):
             raise FileNotFoundError(f"checkpoint {opt.resume!r} not found (pass --synthetic-seed N to run on the "
                                     "seeded synthetic weights)")
-        model = load_model_from_config(config, opt.resume, split=split)
-        if opt.synthetic_tokenizer and model.cond_stage_model is not None:
-            model.cond_stage_model.use_synthetic_tokenizer()
         if "bigv" not in opt.vocoder_ckpt:
             raise NotImplementedError(f"vocoder {opt.vocoder_ckpt!r}: only BigVGAN checkpoints are on the path")
-        vocoder = VocoderBigVGAN(opt.vocoder_ckpt, split=split)
-    return config, model, LCMSampler(model), vocoder
+    model, vocoder = build_models(config, opt.resume, opt.vocoder_ckpt, opt.synthetic_seed, split,
+                                  opt.synthetic_tokenizer, encoder=plan is not None)
+    return config, model, LCMSampler(model), vocoder, plan
 
 
 def main(argv: Optional[Sequence[str]] = None) -> List[Dict[str, str]]:
     opt = parse_args(argv)
-    config, model, sampler, vocoder = build(opt)
+    config, model, sampler, vocoder, plan = build(opt)
     os.makedirs(opt.outdir, exist_ok=True)
     gen = GenSamples(opt, sampler, model, opt.outdir, vocoder, save_mel=False, save_wav=True,
-                     original_inference_steps=config.model.params.num_ddim_timesteps)
+                     original_inference_steps=config.model.params.num_ddim_timesteps, plan=plan)
     csv_dicts: List[Dict[str, str]] = []
     bs = max(1, opt.batch_size // max(1, opt.n_samples))
     with torch.no_grad():

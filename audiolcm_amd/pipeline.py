@@ -10,15 +10,13 @@ from __future__ import annotations
 
 from typing import Dict, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import recipe
+from .audio_in import FRAME_SAMPLES, SAMPLE_RATE, EditPlan, frame_samples_of, spans_to_mask, to_out_rate
 from .lcm import LCM_audio, LCMSampler
 from .models import AutoencoderKL, BigVGAN, ConcatDiT2MLP
-
-
-FRAME_SAMPLES = 512  # one latent frame = 2 mel frames x hop 256
-SAMPLE_RATE = 16000
 
 
 def edit_windows(union, window: int, overlap: Optional[int] = None):
@@ -110,8 +108,9 @@ class AudioLCMPipeline:
              unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0) -> Dict[str, torch.Tensor]:
         """Audio-conditioned generation (``LCMSampler.sample_edit``) from exactly one of ``wav`` (B, L) at 16 kHz, L a
         multiple of 512 (log-mel -> ``encode_first_stage``; needs the encoder weights) and ``latent`` (B, C, T) already
-        scaled.  ``mask`` None: a variation of the whole clip at ``strength``; ``mask`` (B, T), 1 = regenerate: text-guided
-        inpainting, the frames of mask 0 keep the input latent exactly.  The whole clip is decoded and vocoded again."""
+        scaled (or the encoder's posterior, as ``sample_edit`` takes it).  ``mask`` None: a variation of the whole clip
+        at ``strength``; ``mask`` (B, T), 1 = regenerate: text-guided inpainting, the frames of mask 0 keep the input
+        latent exactly.  The whole clip is decoded and vocoded again."""
         z = self._edit_latent(cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
                               cfg_scale)
         out = self.decode(z)
@@ -142,7 +141,8 @@ class AudioLCMPipeline:
                   mask=None, strength: float = 0.5, window: Optional[int] = None, overlap: Optional[int] = None,
                   sample_posterior: bool = True, steps: Optional[int] = None,
                   unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, keep_original: bool = False,
-                  fade_samples: int = 512, halo_frames: int = 32) -> Dict[str, torch.Tensor]:
+                  fade_samples: Optional[int] = None, halo_frames: int = 32,
+                  rate: int = SAMPLE_RATE) -> Dict[str, torch.Tensor]:
         """``edit`` for a clip of any length, optionally keeping the input waveform outside the regenerated frames.
 
         The input is exactly one of ``wav`` (B, N), N a multiple of 512, encoded once as a whole (z = the scaled
@@ -157,21 +157,34 @@ class AudioLCMPipeline:
         ``keep_original=False``: the whole clip is decoded; returns latent, mel, wav.  ``keep_original=True`` (needs
         ``wav``): only ``paste_regions(union, halo_frames)`` are decoded, each blended into a copy of ``wav`` by one
         ``kernels.wave_paste`` with a raised-cosine fade of ``fade_samples`` either side of the regenerated frames;
-        samples further away keep the input's bits.  Returns latent, wav (B, N) and regions.  ``halo_frames`` * 512 >=
-        ``fade_samples`` is required unless every region is cut by the clip's ends, so that a fade never reaches the
-        edge of a decoded region.  The default halo of 32 frames (1 s) also keeps the fade away from the zero-padded
-        edges of the region's decode; it is a choice, not a measurement (no trained weights here to listen to)."""
-        from . import kernels
+        samples further away keep the input's bits.  Returns latent, wav (B, N) and regions.
+
+        ``rate`` (with ``keep_original``): ``wav`` is a recording at its own rate, where one latent frame is a whole
+        number F = 512 * rate / 16000 of samples (48000, 32000, 8000, ...; ValueError otherwise) and N a multiple of F.
+        It is resampled to 16 kHz (``kernels.resample``) for the encoder only; each decoded region is resampled back
+        up, to (b - a) * F samples exactly, and pasted with ``frame_samples`` = F.  ``fade_samples`` counts samples at
+        ``rate``; None is 512 at 16 kHz and 1536 at any other rate.
+
+        The halo: at 16 kHz ``halo_frames`` * 512 >= ``fade_samples`` is required unless every region is cut by the
+        clip's ends, so that a fade never reaches the edge of a decoded region; at another rate ``halo_frames`` * 512 >=
+        the fade in 16 kHz samples + |first| + 1 (``first`` of the 16000 -> rate filter, ``resample.plan``), whatever
+        the regions, so that the upsampler's transient at a region's edges stays outside the fade too.  The default of
+        32 frames (1 s) also keeps the fade away from the zero-padded edges of the region's decode; it is a choice,
+        not a measurement (no trained weights here to listen to)."""
+        from . import kernels, resample as rs
         if (wav is None) == (latent is None):
             raise ValueError("pass exactly one of `wav` and `latent`")
         if keep_original and wav is None:
             raise ValueError("keep_original needs the input waveform `wav`")
+        if rate != SAMPLE_RATE and not keep_original:
+            raise ValueError("`rate` is used with keep_original: anything else is decoded at 16 kHz")
+        F = frame_samples_of(rate)
         dev = torch.device("cuda")
         if wav is not None:
             wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
-            if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES:
-                raise ValueError("`wav` is (B, N) with N a multiple of 512")
-            B, L = wav.shape[0], wav.shape[1] // FRAME_SAMPLES
+            if wav.dim() != 2 or wav.shape[1] % F:
+                raise ValueError(f"`wav` is (B, N) with N a multiple of {F}")
+            B, L = wav.shape[0], wav.shape[1] // F
         else:
             B, L = latent.shape[0], latent.shape[2]
         W = min(window or self.latent_shape[1], L)
@@ -183,19 +196,26 @@ class AudioLCMPipeline:
                 raise ValueError(f"mask must be (B, L) = {(B, L)}, got {tuple(mask.shape)}")
             union = (mask > 0).any(0).tolist()
         regions = paste_regions(union, halo_frames) if keep_original else None
+        native = rate != SAMPLE_RATE
         if keep_original:
-            if not 0 <= fade_samples <= kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES:
-                raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES}")
-            if halo_frames * FRAME_SAMPLES < fade_samples and any(a > 0 or b < L for a, b in regions):
-                raise ValueError("halo_frames * 512 must be at least fade_samples: the fade has to end inside the "
-                                 "decoded region")
-        z = self._edit_long_latent(cond, seeds, wav, latent, mask, union, W, overlap, strength, sample_posterior, steps,
-                                   unconditional, cfg_scale)
+            if fade_samples is None:
+                fade_samples = 1536 if native else 512
+            if not 0 <= fade_samples <= kernels.PASTE_MAX_FADE_FRAMES * F:
+                raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * F}")
+            fade16 = -(-fade_samples * SAMPLE_RATE // rate)
+            reach = fade16 + abs(rs.plan(SAMPLE_RATE, rate).first) + 1 if native else fade16
+            if halo_frames * FRAME_SAMPLES < reach and (native or any(a > 0 or b < L for a, b in regions)):
+                raise ValueError(f"halo_frames * 512 must be at least {reach}: the fade ({fade16} samples at 16 kHz), "
+                                 "and at another rate the resampling filter's reach, must end inside the decoded region")
+        wav16 = kernels.resample(wav, rate, SAMPLE_RATE) if native else wav     # for the encoder only
+        assert wav16 is None or wav16.shape[1] == L * FRAME_SAMPLES
+        z = self._edit_long_latent(cond, seeds, wav16, latent, mask, union, W, overlap, strength, sample_posterior,
+                                   steps, unconditional, cfg_scale)
         if not keep_original:
             return dict(latent=z, **self.decode(z))
         out = wav.clone()
         pm = torch.ones((B, L), device=dev) if mask is None else mask.to(dev).contiguous()
-        self._paste_regions(out, z, pm, regions, fade_samples)
+        self._paste_regions(out, z, pm, regions, fade_samples, rate, F)
         return dict(latent=z, wav=out, regions=regions)
 
     def _edit_long_latent(self, cond, seeds, wav, latent, mask, union, W, overlap, strength, sample_posterior, steps,
@@ -250,50 +270,28 @@ class AudioLCMPipeline:
                                frame_samples=frame_samples, out=out)
 
     @torch.no_grad()
-    def edit_long_native(self, cond: torch.Tensor, seeds: Sequence[int], wav, rate: int, mask,
-                         strength: float = 0.5, window: Optional[int] = None, overlap: Optional[int] = None,
-                         sample_posterior: bool = True, steps: Optional[int] = None,
-                         unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
-                         fade_samples: int = 1536, halo_frames: int = 32) -> Dict[str, torch.Tensor]:
-        """``edit_long(keep_original=True)`` on a recording at its own sample rate.  ``wav`` (B, N) at ``rate``, where one
-        latent frame is a whole number F = 512 * rate / 16000 of samples (48000, 32000, 8000, 96000, ...; ValueError
-        otherwise) and N a multiple of F.  The recording is resampled to 16 kHz (``kernels.resample``) for the encoder
-        only; the latent is ``edit_long``'s for those 16 kHz samples.  Each decoded region is resampled back up, which
-        gives (b - a) * F samples exactly, and pasted into a copy of ``wav`` by ``kernels.wave_paste`` with
-        ``frame_samples`` = F and a fade of ``fade_samples`` samples at ``rate``: samples further than that from a
-        regenerated frame keep their bits.  ``halo_frames`` * 512 >= the fade in 16 kHz samples + |first| + 1 (``first``
-        of the 16000 -> rate filter, ``resample.plan``) is required, so that the upsampler's transient at the edges of
-        a decoded region stays outside the fade.  Returns latent, wav (B, N) and regions."""
-        from . import kernels, resample as rs
-        F = rs.frame_samples_at(rate, SAMPLE_RATE, FRAME_SAMPLES)
-        if F is None:
-            raise ValueError(f"sample rate {rate}: a latent frame is {FRAME_SAMPLES} * rate / {SAMPLE_RATE} samples, which "
-                             "must be whole (multiples of 125 Hz: 8000, 16000, 32000, 48000, 96000)")
-        dev = torch.device("cuda")
-        wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
-        if wav.dim() != 2 or wav.shape[1] % F:
-            raise ValueError(f"`wav` is (B, N) with N a multiple of {F}")
-        B, L = wav.shape[0], wav.shape[1] // F
-        mask = torch.as_tensor(mask, dtype=torch.float32)
-        if tuple(mask.shape) != (B, L):
-            raise ValueError(f"mask must be (B, L) = {(B, L)}, got {tuple(mask.shape)}")
-        if not 0 <= fade_samples <= kernels.PASTE_MAX_FADE_FRAMES * F:
-            raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * F}")
-        fade16 = -(-fade_samples * SAMPLE_RATE // rate)
-        reach = fade16 + abs(rs.plan(SAMPLE_RATE, rate).first) + 1 if rate != SAMPLE_RATE else fade16
-        if halo_frames * FRAME_SAMPLES < reach:
-            raise ValueError(f"halo_frames * 512 must be at least {reach}: the fade ({fade16} samples at 16 kHz) and the "
-                             "resampling filter's reach have to end inside the decoded region")
-        union = (mask > 0).any(0).tolist()
-        regions = paste_regions(union, halo_frames)
-        W = min(window or self.latent_shape[1], L)
-        wav16 = kernels.resample(wav, rate, SAMPLE_RATE)
-        assert wav16.shape[1] == L * FRAME_SAMPLES
-        z = self._edit_long_latent(cond, seeds, wav16, None, mask, union, W, overlap, strength, sample_posterior, steps,
-                                   unconditional, cfg_scale)
-        out = wav.clone()
-        self._paste_regions(out, z, mask.to(dev).contiguous(), regions, fade_samples, rate, F)
-        return dict(latent=z, wav=out, regions=regions)
+    def run_edit(self, plan: EditPlan, cond: torch.Tensor, seeds: Optional[Sequence[int]], strength: float = 0.5):
+        """One clip per row of ``cond`` from the one recording of ``plan`` (``audio_in.plan_edit``) -> (the waveform
+        (B, samples) on the device, the rate to write it under, the mel or None).  Variation and inpainting: the clip is
+        cropped to the DiT's length limit and encoded once, the posterior is expanded to the batch, and ``edit`` makes
+        the whole clip again, resampled to the plan's output rate.  Keep-original: ``edit_long`` at the plan's rate on
+        the whole recording, cropped to the input's sample count; no whole-clip mel is decoded."""
+        B = cond.shape[0]
+        if plan.mode == "keep_original":
+            wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
+            mask = np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
+            out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, keep_original=True, rate=plan.rate,
+                                 fade_samples=plan.fade)
+            return out["wav"][:, :plan.n_samples], plan.out_rate, None
+        from .models import DiagonalGaussianDistribution
+        crop = self.model.unet.diffusion_model.cfg.max_latent_len * plan.frame_samples
+        post = self._encode(plan.samples[:crop])
+        T = post.mean.shape[2]
+        mask = None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
+        init = DiagonalGaussianDistribution(post.parameters.expand(B, -1, -1).contiguous())
+        out = self.edit(cond, seeds, latent=init, mask=mask, strength=strength)
+        wav, rate = to_out_rate(out["wav"], plan.out_rate)
+        return wav, rate, out["mel"]
 
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
         """([(start, known)], window length) of ``generate_long``: window k covers frames start .. start + window, of

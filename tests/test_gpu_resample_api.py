@@ -1,6 +1,6 @@
 """Recordings in at any rate and audio out at any rate, end to end on the HIP path with the synthetic weights:
 ``AudioLCMEditInfer(resample=True)`` on a 48 kHz stereo PCM24 file, ``out_sample_rate`` on the long-form entry point,
-the keep-original edit at the recording's own rate (``AudioLCMPipeline.edit_long_native``) and the two command-line
+the keep-original edit at the recording's own rate (``AudioLCMPipeline.edit_long(rate=...)``) and the two command-line
 flags.  The Python entry points share one model build (``infer_api._build`` is what every one of them calls first)."""
 import os
 import struct
@@ -144,11 +144,11 @@ def test_edit_long_native_needs_a_halo_past_the_filter(built):
     mask[0, 8:10] = 1.0
     # fade 1536 at 48 kHz = 512 at 16 kHz, |first| = 34: 547 samples are needed, one frame of halo has 512
     with pytest.raises(ValueError, match="halo_frames"):
-        pipe.edit_long_native(ctx, [1], wav, 48000, mask, fade_samples=F48, halo_frames=1)
+        pipe.edit_long(ctx, [1], wav=wav, mask=mask, keep_original=True, rate=48000, fade_samples=F48, halo_frames=1)
     with pytest.raises(ValueError, match="125 Hz"):
-        pipe.edit_long_native(ctx, [1], wav, 44100, mask)
+        pipe.edit_long(ctx, [1], wav=wav, mask=mask, keep_original=True, rate=44100)
     with pytest.raises(ValueError, match="multiple of 1536"):
-        pipe.edit_long_native(ctx, [1], wav[:, :-1], 48000, mask)
+        pipe.edit_long(ctx, [1], wav=wav[:, :-1], mask=mask, keep_original=True, rate=48000)
 
 
 # ---------------------------------------------------------------------------- the command line

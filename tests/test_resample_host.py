@@ -267,7 +267,7 @@ def test_cli_build_refuses_what_keep_original_cannot_do(tmp_path, monkeypatch):
 
     def no_model(*a, **k):
         raise AssertionError("a refused input must not reach the model")
-    monkeypatch.setattr(cli, "load_model_from_config", no_model)
+    monkeypatch.setattr(cli, "build_models", no_model)
     mono = np.zeros((4000, 1))
     p441 = _write(tmp_path / "a441.wav", _wav_bytes(mono, 44100, 16)[0])
     with pytest.raises(ValueError, match="48000") as e:

@@ -14,7 +14,8 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
   * ``--inpaint`` (parsed and never read by the reference) is text-guided inpainting of ``--init-audio PATH`` on the
     spans of ``--mask-spans "2.0-4.5,7-8"`` (seconds); without both it raises.  ``--init-audio`` alone is a variation
     of that clip at ``--strength F``; ``--duration SECONDS`` generates long-form clips by windowed continuation
-    (DESIGN.md §5).  ``--keep-original`` (with ``--inpaint``) takes a recording of any length, regenerates only the
+    (DESIGN.md §5), with ``--long-joint`` by denoising all windows jointly, one DiT call per clip and LCM step.
+    ``--keep-original`` (with ``--inpaint``) takes a recording of any length, regenerates only the
     whole latent frames inside the spans window by window and fades them into the input over ``--fade-ms F`` (default
     32) either side: every sample further than F ms from a span is written back as it was read, and each output has
     the input's sample count.  Without it the clip is cropped to the DiT's 845 frames and synthesised again as a whole;
@@ -89,6 +90,8 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                         "(--sample_rate only labels the header and is then ignored)")
     p.add_argument("--duration", type=float, default=None,
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
+    p.add_argument("--long-joint", action="store_true",
+                   help="with --duration: denoise the windows jointly, one DiT call per clip and LCM step (DESIGN.md §5)")
     p.add_argument("--test-dataset-tsv", type=str, default=None, help="override the config's test_dataset tsv_path")
     return p.parse_args(argv)
 
@@ -123,7 +126,8 @@ class GenSamples:
             wav, rate, mel = self.pipeline.run_edit(self.plan, c, seeds, self.opt.strength)
             return mel, wav, self.opt.sample_rate if label and not self.plan.native else rate, self.plan.pcm_scale
         if self.opt.duration is not None:
-            out = self.pipeline.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES))
+            out = self.pipeline.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES),
+                                              joint=self.opt.long_joint)
             mel, wav = out["mel"], out["wav"]
         else:
             B = c.shape[0]
@@ -185,6 +189,8 @@ def build(opt):
         raise ValueError("--mask-spans is used with --inpaint")
     if opt.init_audio and opt.duration is not None:
         raise ValueError("--init-audio and --duration do not combine")
+    if opt.long_joint and opt.duration is None:
+        raise ValueError("--long-joint is used with --duration")
     if opt.resample and not opt.init_audio:
         raise ValueError("--resample is used with --init-audio")
     check_out_rate(opt.out_sample_rate)

@@ -49,6 +49,9 @@ int lcm_step(const float* x, const float* eps, const float* eps_u, float cfg, co
 int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
                   const float* coeffs, const float* z0, const float* mask, float* prev, float* den, int B, int C, int T,
                   hipStream_t s);
+int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                   const float* coeffs, const int* starts, int K, const float* wn, float* prev, float* den, float* xw,
+                   int B, int C, int L, int W, hipStream_t s);
 int latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
                 const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
                 int C, int T, hipStream_t s);

@@ -571,6 +571,172 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
   return 0;
 }
 
+// ---------------------------------------------------------------- joint LCM step of overlapping windows
+// One long latent x (B, C, L) is covered by K windows of W frames at the frames starts[k]; the DiT ran on every window
+// of every clip as one batch, eps (K * B, C, W), row k * B + b.  Per element (b, c, t), over the windows that cover t in
+// ascending k: d_k = lcm_denoise(x, eps[k * B + b, c, t - s_k]); one covering window: d = d_k (a select: the plain
+// step's bits); several: acc = wn[0] * d_0 rounded alone, acc = fmaf(wn[k], d_k, acc), d = acc, with wn (K, W) the
+// host's normalised window weights (pipeline.joint_weights).  prev = the re-noised d, and xw (K * B, C, W) is prev
+// gathered back into window layout, the next DiT input.  eps == nullptr: only x is gathered into xw, by a kernel of
+// its own (joint_gather_kernel).
+// Items as in the edit step: V frames of kEditCh channel rows; with V = 4 every start and W are multiples of 4, so the
+// frames of one access share their covering windows.  The starts travel by value in the kernel's arguments (the window
+// index is uniform, so each is a scalar load).  No atomics: an element's value is one fixed chain, whatever B, the grid
+// or V.
+constexpr int kJointMaxWin = 32;
+struct JointStarts {
+  int s[kJointMaxWin];
+};
+__device__ __forceinline__ float joint_first(float w, float d) {
+#pragma clang fp contract(off)
+  const float a = w * d;
+  return a;
+}
+
+template <int V>
+__global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
+    const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg,
+    const float* __restrict__ noise, StepCoeffs k, JointStarts st, int K, const float* __restrict__ wn,
+    float* __restrict__ prev, float* __restrict__ den, float* __restrict__ xw, int B, int C, int L, int W,
+    int64_t items) {
+  for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+    const EditItem w = edit_item<V>(it, C, L);
+    const int64_t o0 = (w.b * C + w.c0) * L + w.t;
+    const int nch = C - w.c0 < kEditCh ? C - w.c0 : kEditCh;
+    FVec<V> xv[kEditCh], nv[kEditCh], acc[kEditCh], one[kEditCh];
+#pragma unroll
+    for (int j = 0; j < kEditCh; ++j) {
+      if (j >= nch) break;
+      xv[j] = FVec<V>::ld(x + o0 + (int64_t)j * L);
+      if (noise) nv[j] = FVec<V>::ld(noise + o0 + (int64_t)j * L);  // in flight with x, ahead of the windows' loads
+    }
+    int cover = 0;
+    for (int kk = 0; kk < K; ++kk) {
+      const int o = w.t - st.s[kk];
+      if (o < 0 || o >= W) continue;
+      const FVec<V> wv = FVec<V>::ld(wn + (int64_t)kk * W + o);
+      const int64_t e0 = (((int64_t)kk * B + w.b) * C + w.c0) * W + o;
+#pragma unroll
+      for (int j = 0; j < kEditCh; ++j) {
+        if (j >= nch) break;
+        const FVec<V> ev = FVec<V>::ld(eps + e0 + (int64_t)j * W);
+        FVec<V> uv = ev;
+        if (eps_u) uv = FVec<V>::ld(eps_u + e0 + (int64_t)j * W);
+#pragma unroll
+        for (int i = 0; i < V; ++i) {
+          const float d = lcm_denoise(xv[j].v[i], ev.v[i], eps_u != nullptr, uv.v[i], cfg, k);
+          if (cover == 0) {
+            one[j].v[i] = d;
+            acc[j].v[i] = joint_first(wv.v[i], d);
+          } else {
+            acc[j].v[i] = fmaf(wv.v[i], d, acc[j].v[i]);
+          }
+        }
+      }
+      ++cover;
+    }
+    // from here on xv holds prev
+#pragma unroll
+    for (int j = 0; j < kEditCh; ++j) {
+      if (j >= nch) break;
+      const int64_t o = o0 + (int64_t)j * L;
+      FVec<V> dv;
+#pragma unroll
+      for (int i = 0; i < V; ++i) dv.v[i] = cover == 1 ? one[j].v[i] : acc[j].v[i];
+#pragma unroll
+      for (int i = 0; i < V; ++i) xv[j].v[i] = noise ? lcm_renoise(dv.v[i], nv[j].v[i], k) : dv.v[i];
+      if (den) dv.st(den + o);
+      if (prev) xv[j].st(prev + o);
+    }
+    if (xw) {
+      for (int kk = 0; kk < K; ++kk) {
+        const int o = w.t - st.s[kk];
+        if (o < 0 || o >= W) continue;
+        const int64_t e0 = (((int64_t)kk * B + w.b) * C + w.c0) * W + o;
+#pragma unroll
+        for (int j = 0; j < kEditCh; ++j)
+          if (j < nch) xv[j].st(xw + e0 + (int64_t)j * W);
+      }
+    }
+  }
+}
+
+// the windows of the first step, cut from x: xw[k * B + b, c, t - s_k] = x[b, c, t] for every covering k
+template <int V>
+__global__ __launch_bounds__(kEditBlock) void joint_gather_kernel(const float* __restrict__ x, JointStarts st, int K,
+                                                                  float* __restrict__ xw, int B, int C, int L, int W,
+                                                                  int64_t items) {
+  for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+    const EditItem w = edit_item<V>(it, C, L);
+    const int64_t o0 = (w.b * C + w.c0) * L + w.t;
+    const int nch = C - w.c0 < kEditCh ? C - w.c0 : kEditCh;
+    FVec<V> xv[kEditCh];
+#pragma unroll
+    for (int j = 0; j < kEditCh; ++j)
+      if (j < nch) xv[j] = FVec<V>::ld(x + o0 + (int64_t)j * L);
+    for (int kk = 0; kk < K; ++kk) {
+      const int o = w.t - st.s[kk];
+      if (o < 0 || o >= W) continue;
+      const int64_t e0 = (((int64_t)kk * B + w.b) * C + w.c0) * W + o;
+#pragma unroll
+      for (int j = 0; j < kEditCh; ++j)
+        if (j < nch) xv[j].st(xw + e0 + (int64_t)j * W);
+    }
+  }
+}
+
+int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
+                   const int* starts, int K, const float* wn, float* prev, float* den, float* xw, int B, int C, int L,
+                   int W, hipStream_t s) {
+  if (!x || !wn || !c || !starts) return set_error(ALCM_E_INVALID, "lcm_step_joint: null x, wn, coeffs or starts");
+  if (!prev && !den && !xw) return set_error(ALCM_E_INVALID, "lcm_step_joint: no output");
+  if (!eps && (eps_u || noise || prev || den || !xw))
+    return set_error(ALCM_E_INVALID, "lcm_step_joint: without eps only x is gathered into xw");
+  if (B < 0 || C < 0 || L < 0 || W < 0) return set_error(ALCM_E_INVALID, "lcm_step_joint: negative B, C, L or W");
+  if (K < 1 || K > kJointMaxWin) return set_error(ALCM_E_INVALID, "lcm_step_joint: K outside 1 .. 32");
+  if (B == 0 || C == 0 || L == 0 || W == 0) return 0;
+  // the window plan: the same conditions as pipeline.joint_weights
+  JointStarts st = {};
+  bool mult4 = true;
+  for (int i = 0; i < K; ++i) {
+    st.s[i] = starts[i];
+    mult4 = mult4 && starts[i] % 4 == 0;
+    if (i == 0 ? starts[0] != 0 : starts[i] <= starts[i - 1])
+      return set_error(ALCM_E_INVALID, "lcm_step_joint: starts must begin at 0 and ascend strictly");
+    if (i > 0 && (int64_t)starts[i] > (int64_t)starts[i - 1] + W)
+      return set_error(ALCM_E_INVALID, "lcm_step_joint: a gap between two windows");
+  }
+  if ((int64_t)starts[K - 1] + W != L)
+    return set_error(ALCM_E_INVALID, "lcm_step_joint: the last window must end at L");
+  StepCoeffs k{c[0], c[1], c[2], c[3], c[4], c[5]};
+  const bool vec = mult4 && L % 4 == 0 && W % 4 == 0 && aligned16({x, eps, eps_u, noise, wn, prev, den, xw});
+  const int64_t items = edit_items(B, C, L, vec);
+  const dim3 grid(edit_blocks(items)), blk(kEditBlock);
+  const double nl = (double)B * C * L, nw = (double)K * B * C * W;
+  void* tok = prof_start(s);
+  if (!eps) {
+    if (vec) hipLaunchKernelGGL(joint_gather_kernel<4>, grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
+    else hipLaunchKernelGGL(joint_gather_kernel<1>, grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
+    prof_stop(tok, s, vec ? "alcm::joint_gather_kernel<4>" : "alcm::joint_gather_kernel<1>", 0.0, 4.0 * (nl + nw));
+    ALCM_HIP(hipGetLastError());
+    return 0;
+  }
+  if (vec)
+    hipLaunchKernelGGL(lcm_step_joint_kernel<4>, grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev, den, xw,
+                       B, C, L, W, items);
+  else
+    hipLaunchKernelGGL(lcm_step_joint_kernel<1>, grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev, den, xw,
+                       B, C, L, W, items);
+  // the window tensors (eps, eps_u, xw) count K * B * C * W elements and the long ones (x, noise, prev, den) B * C * L; the
+  // weights once per window, frame and channel group; per window element the step (8) and one multiply-add
+  prof_stop(tok, s, vec ? "alcm::lcm_step_joint_kernel<4>" : "alcm::lcm_step_joint_kernel<1>",
+            10.0 * nw + (noise ? 3.0 * nl : 0.0),
+            4.0 * (nl * (1 + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0)) +
+                   nw * (1 + (eps_u ? 1 : 0) + (xw ? 1 : 0)) + (double)K * W * B * ((C + kEditCh - 1) / kEditCh)));
+  ALCM_HIP(hipGetLastError());
+  return 0;
+}
+
 // z0 = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0) from the encoder's (B, 2C, T) moments (the posterior mode
 // scale * mean without e0; lcm_audio.py:197-204, distributions.py:24-44), or a given z0; x = the sampler's start
 // sa * z0 + sb * n0 on kept frames (m = 0), sa_r * z0 + sb_r * n0 on regenerated ones (m = 1).
@@ -908,6 +1074,13 @@ extern "C" int alcm_lcm_step_edit(const float* x, const float* eps_cond, const f
                                   float* prev_out, float* denoised_out, int B, int C, int T, alcm_stream_t stream) {
   return alcm::lcm_step_edit(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, z0, mask, prev_out, denoised_out, B, C,
                              T, (hipStream_t)stream);
+}
+extern "C" int alcm_lcm_step_joint(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                                   const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
+                                   float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
+                                   alcm_stream_t stream) {
+  return alcm::lcm_step_joint(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, prev_out, denoised_out,
+                              xw_out, B, C, L, W, (hipStream_t)stream);
 }
 extern "C" int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, float scale,
                                 const float* noise, const float* mask, float sa, float sb, float sa_r, float sb_r,

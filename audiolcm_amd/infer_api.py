@@ -201,9 +201,10 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
 def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: str = "configs/audiolcm.yaml",
                       model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
                       synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
-                      seed: Optional[int] = None, out_sample_rate: Optional[int] = None) -> str:
+                      seed: Optional[int] = None, out_sample_rate: Optional[int] = None, joint: bool = False) -> str:
     """A clip of ceil(duration_s * 16000 / 512) latent frames by long-form continuation
     (``AudioLCMPipeline.generate_long``).  ``seed`` None draws the clip's base seed from the global RNG.
+    ``joint``: the windows are denoised jointly, one DiT call per LCM step (``generate_long(joint=True)``).
     ``out_sample_rate``: the clip is resampled from 16 kHz to that rate on the GPU, cropped to
     round(duration_s * out_sample_rate) samples and written under that rate (without it the file keeps every sample
     of the last latent frame, as before).  Returns the WAV path."""
@@ -219,7 +220,7 @@ def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: st
     os.makedirs(outpath, exist_ok=True)
     with torch.no_grad():
         c = model.get_learned_conditioning({"ori_caption": [ori_prompt], "struct_caption": [struct_caption(ori_prompt)]})
-        wav, rate = to_out_rate(pipe.generate_long(c, [base], latent_len)["wav"], out_sample_rate)
+        wav, rate = to_out_rate(pipe.generate_long(c, [base], latent_len, joint=joint)["wav"], out_sample_rate)
         if out_sample_rate is not None:
             wav = wav[:, :int(round(duration_s * rate))]
         wav = wav.cpu().numpy()

@@ -339,6 +339,39 @@ def lcm_step_edit(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tens
     return prev, den
 
 
+def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional[torch.Tensor], coeffs, starts,
+                   wn: torch.Tensor, eps_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
+                   want_prev: bool = True, want_den: bool = True, want_xw: bool = True,
+                   prev: Optional[torch.Tensor] = None, den: Optional[torch.Tensor] = None,
+                   xw: Optional[torch.Tensor] = None):
+    """``lcm_step`` on one long latent ``x`` (B, C, L) whose K overlapping windows of W frames at ``starts`` went through
+    the DiT as one batch: ``eps`` (K * B, C, W), row k * B + b.  Where windows overlap their denoised estimates are
+    averaged with the normalised weights ``wn`` (K, W) (``pipeline.joint_weights``); a frame under one window is the
+    plain step bit for bit (alcm_lcm_step_joint).  Returns (prev, denoised, xw): the two (B, C, L) results and prev
+    gathered back into window layout (K * B, C, W), the next DiT input; a result not wanted is None, ``prev`` / ``den``
+    / ``xw`` give the tensors to write.  ``eps`` None: only x itself is gathered into xw.  One launch."""
+    B, Cc, L = x.shape
+    K, W = wn.shape
+    assert len(starts) == K and x.is_contiguous() and wn.is_contiguous()
+    if eps is None:
+        want_prev = want_den = False
+    else:
+        assert tuple(eps.shape) == (K * B, Cc, W) and eps.is_contiguous()
+        assert eps_uncond is None or (eps_uncond.shape == eps.shape and eps_uncond.is_contiguous())
+        assert noise is None or (noise.shape == x.shape and noise.is_contiguous())
+    if want_prev and prev is None:
+        prev = torch.empty_like(x)
+    if want_den and den is None:
+        den = torch.empty_like(x)
+    if want_xw and xw is None:
+        xw = torch.empty((K * B, Cc, W), device=x.device, dtype=torch.float32)
+    arr = (C.c_float * 6)(*[float(c) for c in coeffs])
+    st = (C.c_int * K)(*[int(s) for s in starts])
+    check(lib().alcm_lcm_step_joint(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K, ptr(wn),
+                                    ptr(prev), ptr(den), ptr(xw), B, Cc, L, W, stream_handle()), "lcm_step_joint")
+    return prev, den, xw
+
+
 def latent_init(noise: Optional[torch.Tensor], keep=(1.0, 0.0), regen=(0.0, 1.0), moments: Optional[torch.Tensor] = None,
                 z0: Optional[torch.Tensor] = None, e0: Optional[torch.Tensor] = None, scale: float = 1.0,
                 mask: Optional[torch.Tensor] = None, want_z0: bool = True,

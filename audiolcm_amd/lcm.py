@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _hip, recipe, schedule
+from . import _hip, kernels, recipe, schedule
 from ._hip import check, lib, ptr, stream_handle
 from .config import instantiate_from_config
 from .models import AutoencoderKL, ConcatDiT2MLP, DiagonalGaussianDistribution
@@ -271,6 +271,109 @@ class LCMSampler:
                 check(lib().alcm_lcm_step(ptr(img), ptr(eps), nz, coeffs, ptr(prev), ptr(denoised), n,
                                           stream_handle()), "lcm_step")
             img, prev = prev, img
+        return denoised, img
+
+    JOINT_DIT_ROWS = 64  # sample_joint: rows per DiT call, the largest batch the suite runs the DiT at
+
+    @torch.no_grad()
+    def sample_joint(self, S, conditioning, length: int, starts: Sequence[int], window: int, overlap: int,
+                     seeds: Optional[Sequence[int]] = None, x_T: Optional[torch.Tensor] = None,
+                     noise: Optional[torch.Tensor] = None, guidance_scale=5., original_inference_steps=50,
+                     unconditional_conditioning: Optional[torch.Tensor] = None,
+                     unconditional_guidance_scale: float = 1.0,
+                     clips_per_call: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Joint long-form sampling: S LCM steps on one latent of ``length`` frames covered by the K windows of
+        ``window`` frames at ``starts`` (``AudioLCMPipeline.long_windows``).  Every step runs the DiT on all windows of
+        all clips (K * B rows, row k * B + b; [uc; c] doubled with guidance as in ``sample``) and then one
+        alcm_lcm_step_joint: where windows overlap their denoised estimates are averaged with
+        ``pipeline.joint_weights(starts, window, length, overlap)``, the long latent is re-noised once, and the windows
+        of the next step are cut from it.  No window waits for another one, and every window sees both neighbours.
+
+        The DiT is called on the windows of ``clips_per_call`` clips at a time (at most ``JOINT_DIT_ROWS`` rows).  The
+        DiT picks its kernels by the rows of the call, so one and the same row differs by some 5e-6 between calls of
+        different sizes; with the default of one clip per call (K rows, S calls per clip) a call's rows do not depend
+        on the batch and neither does a clip, bit for bit.  A larger value makes fewer, larger calls (S at
+        ``clips_per_call`` >= B) and gives that up: a clip then agrees across batch sizes to about 3e-6.  With one window
+        the call is ``sample``'s own, the whole batch.
+
+        RNG: with ``seeds`` ``recipe.prompt_noise(seeds, S, C, length)``, per prompt at the clip's whole length (a clip
+        does not depend on its batch; with one window these are ``sample``'s draws and the result is ``sample``'s bit
+        for bit); ``x_T`` / ``noise`` replace the respective draw; without seeds the global device RNG.
+        Returns (denoised, last sample) like ``sample``."""
+        from .pipeline import joint_weights_device
+        self.make_schedule(verbose=False)
+        dev = torch.device("cuda")
+        dit: ConcatDiT2MLP = self.model.unet.diffusion_model
+        W, L, K = int(window), int(length), len(starts)
+        if W > dit.cfg.max_latent_len:
+            raise ValueError(f"window {W} exceeds the DiT's {dit.cfg.max_latent_len} frames")
+        wn = joint_weights_device(starts, W, L, overlap, dev)  # validates the window plan
+        cond = conditioning
+        if isinstance(cond, dict):
+            cond = cond[list(cond.keys())[0]]
+            while isinstance(cond, list):
+                cond = cond[0]
+        B, Cc = cond.shape[0], dit.cfg.in_channels
+        plan = schedule.sample_plan(S, original_inference_steps)
+        self.num_inference_steps = len(plan)
+        self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
+        n_noise = sum(1 for p in plan if p["add_noise"])
+        if seeds is not None:
+            xT_h, noise_h = recipe.prompt_noise(seeds, len(plan), Cc, L)
+            img = _h2d(xT_h, dev) if x_T is None else x_T.to(dev)
+            noise = _h2d(noise_h, dev) if noise is None else noise
+        else:
+            img = x_T.to(dev) if x_T is not None else torch.randn((B, Cc, L), device=dev)
+            if noise is None and n_noise:
+                noise = torch.randn((n_noise, B, Cc, L), device=dev)
+        img = img.float().contiguous()
+        noise = noise.to(dev).float().contiguous() if noise is not None else None
+        if tuple(img.shape) != (B, Cc, L):
+            raise ValueError(f"x_T must be (B, C, length) = {(B, Cc, L)}, got {tuple(img.shape)}")
+
+        cfg = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
+        c = cond.to(dev).float()
+        if cfg:
+            c = torch.cat([unconditional_conditioning.to(dev).float(), c], 0)
+        cemb = dit.embed_context(c)
+        w = torch.full((c.shape[0],), float(guidance_scale - 1), device=dev, dtype=torch.float32)
+        w_emb = self.get_guidance_scale_embedding(w, embedding_dim=256)
+        # DiT calls: the windows of g clips each, rows k * g + j ([uc; c] halves with guidance), so that the rows of a
+        # call, and with them the DiT's kernel plan, do not depend on the batch; one window is ``sample``'s own call
+        per_clip = K * (2 if cfg else 1)
+        g = B if K == 1 else max(1, min(int(clips_per_call), B, self.JOINT_DIT_ROWS // per_clip))
+        groups = []
+        for b0 in range(0, B, g):
+            b1 = min(b0 + g, B)
+            ce = cemb[b0:b1].repeat(K, 1, 1)
+            if cfg:
+                ce = torch.cat([ce, cemb[B + b0:B + b1].repeat(K, 1, 1)], 0)
+            groups.append((b0, b1, ce, w_emb[:1].repeat(ce.shape[0], 1)))
+        KB = K * B
+        xw = torch.empty((KB, Cc, W), device=dev, dtype=torch.float32)
+        ec = torch.empty_like(xw)
+        eu = torch.empty_like(xw) if cfg else None
+        kernels.lcm_step_joint(img, None, None, plan[0]["coeffs"], starts, wn, xw=xw)   # the first windows, cut from x_T
+        outs = [torch.empty_like(img), torch.empty_like(img)]   # never write into the caller's x_T
+        denoised = torch.empty_like(img)
+        for i, p in enumerate(plan):
+            for b0, b1, ce, we in groups:
+                n = K * (b1 - b0)
+                xg = xw.view(K, B, Cc, W)[:, b0:b1].reshape(n, Cc, W)
+                ts = torch.full((ce.shape[0],), p["t"], device=dev, dtype=torch.long)
+                whole = b1 - b0 == B
+                if not cfg:
+                    e = dit.forward_cached(xg, ts, ce, we, out=ec if whole else None)
+                else:
+                    e = dit.forward_cached(torch.cat([xg, xg], 0), ts, ce, we)
+                    eu.view(K, B, Cc, W)[:, b0:b1] = e[:n].view(K, b1 - b0, Cc, W)
+                if cfg or not whole:
+                    ec.view(K, B, Cc, W)[:, b0:b1] = e[-n:].view(K, b1 - b0, Cc, W)
+            last = i + 1 == len(plan)
+            kernels.lcm_step_joint(img, ec, noise[i] if p["add_noise"] else None, p["coeffs"], starts, wn,
+                                   eps_uncond=eu, cfg_scale=float(unconditional_guidance_scale),
+                                   prev=outs[i % 2], den=denoised, xw=None if last else xw, want_xw=not last)
+            img = outs[i % 2]
         return denoised, img
 
     @torch.no_grad()

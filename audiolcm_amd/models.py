@@ -178,7 +178,8 @@ class ConcatDiT2MLP(_HipModel):
         return cemb
 
     def forward_cached(self, x: torch.Tensor, t: torch.Tensor, cemb: torch.Tensor,
-                       w_cond: Optional[torch.Tensor]) -> torch.Tensor:
+                       w_cond: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``out``: a contiguous fp32 tensor of x's shape to write eps into (a row range of a larger batch)."""
         self._need()
         B, Cc, T = x.shape
         assert Cc == self.cfg.in_channels
@@ -189,7 +190,11 @@ class ConcatDiT2MLP(_HipModel):
         t = t.to(device=x.device, dtype=torch.int64).contiguous()
         if w_cond is not None:
             w_cond = w_cond.contiguous().float()
-        eps = torch.empty_like(x)
+        if out is None:
+            eps = torch.empty_like(x)
+        else:
+            assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous()
+            eps = out
         nb = self.workspace_bytes(B, T)
         ws = self._workspace(("fwd", B, T), nb, x.device)
         check(lib().alcm_dit_forward(self._handle, ptr(x), ptr(t), ptr(cemb), ptr(w_cond), ptr(eps), B, T, ptr(ws),

@@ -8,6 +8,7 @@ SURVEY.md §8f) and per-prompt seeds.
 """
 from __future__ import annotations
 
+import functools
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -59,6 +60,58 @@ def paste_regions(union, halo: int):
             regions.append((a, b))
         t = hi
     return regions
+
+
+JOINT_MAX_WINDOWS = 32  # alcm_lcm_step_joint: the window starts travel in the kernel's arguments
+
+
+@functools.lru_cache(maxsize=None)
+def _joint_weights(starts: tuple, W: int, L: int, overlap: int) -> np.ndarray:
+    K = len(starts)
+    if not 1 <= K <= JOINT_MAX_WINDOWS:
+        raise ValueError(f"need 1 to {JOINT_MAX_WINDOWS} windows, got {K}")
+    if W < 1 or overlap < 0:
+        raise ValueError("need window >= 1 and overlap >= 0")
+    if starts[0] != 0:
+        raise ValueError("the first window must start at frame 0")
+    for a, b in zip(starts, starts[1:]):
+        if b <= a:
+            raise ValueError(f"window starts must ascend strictly, got {list(starts)}")
+        if b > a + W:
+            raise ValueError(f"frames {a + W} .. {b - 1} are under no window")
+    if starts[-1] + W != L:
+        raise ValueError(f"the last window must end at the clip's {L} frames, it ends at {starts[-1] + W}")
+    j = np.arange(W, dtype=np.float64)
+    w = np.minimum(1.0, (np.minimum(j, W - 1 - j) + 1.0) / (overlap + 1.0))
+    total = np.zeros(L, dtype=np.float64)
+    for s in starts:
+        total[s:s + W] += w
+    wn = np.stack([w / total[s:s + W] for s in starts], 0).astype(np.float32)
+    wn.setflags(write=False)
+    return wn
+
+
+def joint_weights(starts, W: int, L: int, overlap: int) -> np.ndarray:
+    """The host plan of joint long-form denoising (``LCMSampler.sample_joint``, alcm_lcm_step_joint): the normalised
+    weights wn (K, W), fp32, of K windows of W frames at the frames ``starts`` (``long_windows``' starts) of a clip of L
+    frames.  The raw profile of a window is a linear ramp over ``overlap`` frames at each end,
+    w[j] = min(1, (min(j, W - 1 - j) + 1) / (overlap + 1)), strictly positive; wn[k][j] = w[j] over the sum of w over
+    the windows that cover frame starts[k] + j, evaluated in float64 and rounded to fp32 once: per frame the covering
+    weights sum to 1, and a frame under one window has exactly 1.0.  ValueError unless the starts begin at 0, ascend
+    strictly, leave no frame uncovered (starts[k] <= starts[k - 1] + W), end at L (starts[-1] + W == L) and are 1 to 32.
+    Built once per argument tuple; the array is read-only."""
+    return _joint_weights(tuple(int(s) for s in starts), int(W), int(L), int(overlap))
+
+
+_joint_dev = {}
+
+
+def joint_weights_device(starts, W: int, L: int, overlap: int, device) -> torch.Tensor:
+    """``joint_weights(...)`` on ``device``, uploaded once per argument tuple and device."""
+    key = (tuple(int(s) for s in starts), int(W), int(L), int(overlap), torch.device(device))
+    if key not in _joint_dev:
+        _joint_dev[key] = torch.from_numpy(joint_weights(*key[:4]).copy()).to(device)
+    return _joint_dev[key]
 
 
 class AudioLCMPipeline:
@@ -312,16 +365,31 @@ class AudioLCMPipeline:
 
     @torch.no_grad()
     def generate_long(self, cond: torch.Tensor, seeds: Sequence[int], latent_len: int, window: Optional[int] = None,
-                      overlap: Optional[int] = None, steps: Optional[int] = None) -> Dict[str, torch.Tensor]:
+                      overlap: Optional[int] = None, steps: Optional[int] = None,
+                      joint: bool = False, joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
         """Long-form continuation past the DiT's length limit: window 0 is ``generate``'s latent for the prompt's own
         seeds; window k >= 1 is a ``sample_edit`` call at strength 1 whose known context (mask 0) is the previous
         ``overlap`` frames and whose remaining frames (mask 1) are new, with seeds ``recipe.window_seed(seed, k)``.
         The windows' new frames are concatenated into one (B, C, latent_len) latent, decoded and vocoded in one call
-        each.  Defaults: window = latent_shape[1], overlap = window // 2."""
+        each.  Defaults: window = latent_shape[1], overlap = window // 2.
+
+        ``joint=True``: the same windows are denoised jointly instead of one after another
+        (``LCMSampler.sample_joint``): every LCM step runs all windows of a clip through the DiT as one batch and
+        averages their estimates where they overlap (``joint_weights``), with the noise of
+        ``recipe.prompt_noise(seeds, S, C, latent_len)``.  It is another sampler, not another route to the same clip.
+        ``joint_clips_per_call`` is ``sample_joint``'s ``clips_per_call``: 1 keeps a clip independent of its batch bit
+        for bit, a larger value packs several clips' windows into a DiT call (faster from a few clips on; a clip then
+        agrees across batch sizes to about 3e-6)."""
         B, Cc = cond.shape[0], self.latent_shape[0]
         S = steps or self.steps
         spans, W = self.long_windows(latent_len, window, overlap)
         kw = dict(guidance_scale=self.guidance_scale, original_inference_steps=self.original_inference_steps)
+        if joint:
+            ov = (window or self.latent_shape[1]) // 2 if overlap is None else overlap
+            z, _ = self.sampler.sample_joint(S=S, conditioning=cond, length=latent_len, starts=[s for s, _ in spans],
+                                             window=W, overlap=ov, seeds=seeds,
+                                             clips_per_call=joint_clips_per_call, **kw)
+            return dict(latent=z, **self.decode(z))
         z, _ = self.sampler.sample(S=S, batch_size=B, shape=(Cc, W), conditioning=cond, verbose=False, seeds=seeds,
                                    **kw)
         for k, (start, known) in enumerate(spans[1:], 1):

@@ -288,6 +288,29 @@ int alcm_lcm_step_cfg(const float* x, const float* eps_cond, const float* eps_un
 int alcm_lcm_step_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
                        const float* noise, const float* coeffs, const float* z0, const float* mask, float* prev_out,
                        float* denoised_out, int B, int C, int T, alcm_stream_t stream);
+/* alcm_lcm_step_joint: the step above (LCMSampler.step, scheduling_lcm.py:465-486; eps_uncond may be NULL: no guidance
+ * combine) on one long latent whose overlapping windows went through the DiT as one batch (no reference counterpart:
+ * the reference generates one window).
+ *   x, noise, prev_out, denoised_out (B, C, L); eps_cond, eps_uncond, xw_out (K * B, C, W), row k * B + b: window k of
+ *   clip b, frames starts[k] .. starts[k] + W of the long latent; starts: HOST array of K ints; wn (K, W), device: the
+ *   normalised window weights (audiolcm_amd/pipeline.py joint_weights: per frame the covering windows' weights sum
+ *   to 1, and a frame under one window has weight exactly 1).
+ *   Per element (b, c, t), over the windows covering t in ascending k: d_k = the step's denoised value from x[b, c, t]
+ *   and eps[k * B + b, c, t - starts[k]].  One covering window: d = d_k, alcm_lcm_step's bits.  Several:
+ *   acc = wn[k0] * d_k0 (rounded alone), acc = fmaf(wn[k], d_k, acc) for the further ones, d = acc.
+ *   denoised_out = d,  prev_out = noise ? sqrt_a_prev * d + sqrt_b_prev * noise : d,
+ *   xw_out[k * B + b, c, t - starts[k]] = prev for every covering k (the next DiT input).
+ * Any output may be NULL, not all three.  eps_cond NULL: x itself is gathered into xw_out (the first DiT input);
+ * eps_uncond, noise, prev_out and denoised_out must then be NULL.  No atomics: an element's bits do not depend on B,
+ * the grid or the access width.  16-byte accesses when L, W and every start are multiples of 4 and every pointer is
+ * 16-byte aligned, element accesses otherwise.
+ * ALCM_E_INVALID for a null x, wn, coeffs or starts, no output, a negative B, C, L or W, K outside 1 .. 32, or starts that
+ * do not begin at 0, do not ascend strictly, leave a gap (starts[k] > starts[k - 1] + W) or do not end at L
+ * (starts[K - 1] + W != L).  B, C, L or W of 0: no launch. */
+int alcm_lcm_step_joint(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                        const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
+                        float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
+                        alcm_stream_t stream);
 /* alcm_latent_init: the encoder output (or a given latent) -> the edit sampler's starting point, one launch.
  *   exactly one of moments (B, 2C, T: mean | logvar, AutoencoderKL.encode) and z0_in (B, C, T);
  *   z0 = z0_in, or scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0); e0 (B, C, T) NULL: the posterior mode

@@ -8,6 +8,7 @@ Used to A/B kernel variants in one process and as the target of 
     python scripts/microbench.py paste      # alcm_wave_paste in place / out of place
     python scripts/microbench.py resample   # alcm_resample on the recorded shapes
     python scripts/microbench.py editlong   # 30 s keep-original edit: region decode + paste vs whole-clip decode
+    python scripts/microbench.py longjoint  # 30 s long-form clip: chained windows vs windows denoised jointly
 """
 import os
 import sys
@@ -595,9 +596,51 @@ def bench_editlong(L=936, reps=5):
               f"({len(t)} calls)", flush=True)
 
 
+def bench_longjoint(L=936, reps=7):
+    """generate_long on a 30 s clip (936 frames, five windows of 312, mixed policy) at B = 1 and B = 8: the chained form,
+    joint=True (one DiT call per clip and step) and the joint sampler with all clips in one DiT call per step
+    (joint_clips_per_call=B), alternating in one process, median of 7 calls after 2 warm-ups, host
+    clock around a device synchronise; then the joint step kernel by the library's per-launch events beside its profile
+    row's bytes"""
+    from audiolcm_amd import recipe
+    from audiolcm_amd.pipeline import AudioLCMPipeline
+    pipe = AudioLCMPipeline.from_recipe(0, split=True)
+    pipe.set_split("mixed")
+    for B in (1, 8):
+        ctx, seeds = recipe.synthetic_context(B).cuda(), list(range(B))
+        z = torch.randn((B, 20, L), device="cuda")
+        forms = {"chained": lambda: pipe.generate_long(ctx, seeds, L),
+                 "joint, a clip per DiT call": lambda: pipe.generate_long(ctx, seeds, L, joint=True),
+                 "joint, all clips per DiT call": lambda: pipe.generate_long(ctx, seeds, L, joint=True,
+                                                                                 joint_clips_per_call=B),
+                 "decode + vocoder alone": lambda: pipe.decode(z)}
+        if B == 1:
+            del forms["joint, all clips per DiT call"]   # the same calls as the default
+        times = {k: [] for k in forms}
+        for i in range(2 + reps):
+            for k, fn in forms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= 2:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+        for k in forms:
+            t = sorted(times[k])
+            print(f"longjoint L={L} B={B} {k:30s}: median {t[len(t) // 2]:7.2f} ms  min {t[0]:7.2f}  max {t[-1]:7.2f} "
+                  f"({len(t)} calls)", flush=True)
+        _hip.profile_begin()
+        for _ in range(reps):
+            pipe.generate_long(ctx, seeds, L, joint=True)
+        for r in _hip.profile_end():
+            if "joint" in r["name"]:
+                print(f"longjoint L={L} B={B} {r['name']}: {r['total_ms'] / r['launches'] * 1e3:6.1f} us by events "
+                      f"({r['launches']} launches)  {r['bytes'] / r['launches'] / 1e6:6.2f} MB per launch", flush=True)
+
+
 if __name__ == "__main__":
     _hip.require_device(0)
     which = sys.argv[1:] or ["op", "conv", "act"]
     spin(float(os.environ.get("SPIN", "3")))
     for w in which:
-        {"resample": bench_resample, "paste": bench_paste, "editlong": bench_editlong, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()
+        {"resample": bench_resample, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()

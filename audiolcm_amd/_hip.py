@@ -62,6 +62,20 @@ class ConvPlanInfo(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+VOC_MAX_RB, VOC_MAX_DIL = 8, 8
+
+
+class VocStageShape(C.Structure):
+    _fields_ = [("cin", C.c_int), ("cout", C.c_int), ("rate", C.c_int), ("taps", C.c_int), ("cpad", C.c_int),
+                ("phases_share", C.c_int), ("dense_weights", C.c_int), ("act0_equal", C.c_int),
+                ("nrb", C.c_int), ("rb_k", C.c_int * VOC_MAX_RB), ("ndil", C.c_int), ("dil", C.c_int * VOC_MAX_DIL)]
+
+
+class VocStagePlan(C.Structure):
+    _fields_ = [(f, C.c_int) for f in ("prec", "ups", "planes_from_prev", "amp", "h16", "act3", "concurrent",
+                                       "own_bufs", "sum3", "writes_next")]
+
+
 class NamedTensor(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", vp), ("ndim", C.c_int), ("shape", i64 * 4)]
 
@@ -119,6 +133,8 @@ _SIGS = [
     ("alcm_debug_tconv_wg_times", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     ("alcm_debug_conv_plan", C.c_int, [C.POINTER(OpConvArgs), C.c_int, C.c_int, C.c_int, C.POINTER(ConvPlanInfo),
                                        C.POINTER(C.c_int)]),
+    ("alcm_debug_voc_plan", C.c_int, [C.POINTER(VocStageShape), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(VocStagePlan)]),
     ("alcm_debug_ksplit_parts", C.c_int, [i64, i64, C.c_int, C.c_double, C.c_double]),
     ("alcm_dit_workspace_bytes", C.c_size_t, [vp, C.c_int, C.c_int]),
     ("alcm_dit_embed_context", C.c_int, [vp, fp, C.c_int, fp, vp, C.c_size_t, vp]),
@@ -237,7 +253,25 @@ def debug_conv_plan(args, n: int = 1, form: int = PLAN_OPCONV, ncu: int = 0) -> 
             for i in range(nl.value)]
 
 
-PEAK_BF16_FLOPS = 2.5e15   # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, spec)
+VOC_UPS = ("planes", "ups2", "phases")
+VOC_AMP = ("fused", "fused_dense", "wide")
+
+
+def debug_voc_plan(shapes, policy: int, streams: bool, B: int, M: int, ncu: int = 0) -> list:
+    """Diagnostics: the stage plans alcm_bigvgan_forward would execute for the stages `shapes` (VocStageShape) at batch
+    B and M mel frames under `policy` and the current ALCM_* switches, one dict per stage (ups and amp by name).  Host
+    only (alcm_debug_voc_plan); needs no GPU when ncu is given."""
+    arr = (VocStageShape * len(shapes))(*shapes)
+    out = (VocStagePlan * len(shapes))()
+    check(lib().alcm_debug_voc_plan(arr, len(shapes), int(policy), int(bool(streams)), B, M, ncu, out),
+          "alcm_debug_voc_plan")
+    plans = [{f: getattr(p, f) for f, _ in VocStagePlan._fields_} for p in out]
+    for p in plans:
+        p["ups"], p["amp"] = VOC_UPS[p["ups"]], VOC_AMP[p["amp"]]
+    return plans
+
+
+PEAK_BF16_FLOPS = 2.5e15  # MI355X dense bf16 MFMA (MI355X_MICROARCH.md, spec)
 PEAK_HBM_BYTES = 8.0e12    # MI355X HBM3E (spec)
 
 

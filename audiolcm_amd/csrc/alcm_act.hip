@@ -594,10 +594,6 @@ int act_mfma3(const float* x, void* const y[3], int B, int T, int C, int Cp, con
   return 0;
 }
 
-bool act_mfma_ok(int C, int Cp, int prec) {
-  return knobs().act_mfma && prec == PREC_F16 && C >= 192 && C % 64 == 0 && Cp == C;
-}
-
 int act_mfma(const void* x, bool x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
              const float* inv_beta, const Taps12O& f, hipStream_t s) {
   if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return set_error(ALCM_E_INVALID, "act_mfma: alignment");

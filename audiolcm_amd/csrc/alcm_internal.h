@@ -8,6 +8,7 @@
 #include "audiolcm_hip.h"
 #include "alcm_convplan.h"
 #include "alcm_knobs.h"
+#include "alcm_vocplan.h"
 
 namespace alcm {
 
@@ -71,8 +72,7 @@ int activation1d_x3(const float* x, void* const y[3], int B, int T, int C, int C
 int activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
                     const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
                     hipStream_t s);
-// Activation1d with both FIRs on MFMA, fp16 planes out (alcm_act.hip; C >= 192, C % 64 == 0, PREC_F16, Cp == C)
-bool act_mfma_ok(int C, int Cp, int prec);
+// Activation1d with both FIRs on MFMA, fp16 planes out (alcm_act.hip; where act_mfma_ok, alcm_vocplan.h)
 // x16: x is an fp16 plane [B][T][C] (the wide-stage conv1 output, alcm_opconv's out_plane) instead of fp32
 int act_mfma3(const float* x, void* const y[3], int B, int T, int C, int Cp, const float* const alpha_exp[3],
               const float* const inv_beta[3], const Taps12O& f, hipStream_t s);
@@ -103,8 +103,8 @@ int opconv_dense(const alcm_opconv_args& a, hipStream_t s);
 
 struct Taps12O;
 
-// BigVGAN stride-2 / kernel-4 upsampler, both phases in one split-precision pass (alcm_ups.hip)
-bool ups2_supported(int cin, int cout, int cpad, int rate, int taps);
+// BigVGAN stride-2 / kernel-4 upsampler, both phases in one split-precision pass (alcm_ups.hip; where ups2_supported,
+// alcm_vocplan.h)
 int ups2(const float* x, float* out, int B, int T, int cin, int cout, const unsigned short* w0, const unsigned short* w1,
          int64_t lo, int kpad, const int pad[2], const int off[2], const float* bias, hipStream_t s);
 // bf16x3 1x1 conv on split operand planes (alcm_sgemm.hip)

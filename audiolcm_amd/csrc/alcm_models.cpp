@@ -133,6 +133,7 @@ struct VocW {
   float* post_w32 = nullptr;  // conv_post weight [tap][C] fp32 (the fused output head, act_conv_post)
   float post_bias = 0.f;
   std::vector<StageW> st;
+  std::vector<VocStageShape> shape;  // st[i] as the stage planner reads it (alcm_vocplan.h)
   ActW post_act;
 };
 
@@ -529,6 +530,29 @@ static ActW build_act(Ingest& I, const std::string& p, int C) {
   return a;
 }
 
+static VocStageShape stage_shape(const StageW& S) {
+  VocStageShape h;
+  std::memset(&h, 0, sizeof(h));
+  h.cin = S.cin; h.cout = S.cout; h.rate = S.rate;
+  h.taps = S.phase[0].w.taps; h.cpad = S.phase[0].w.cpad;
+  h.phases_share = 1;
+  for (const ConvW& ph : S.phase) h.phases_share &= ph.w.kpad == S.phase[0].w.kpad && ph.w.lo == S.phase[0].w.lo;
+  h.nrb = (int)S.rb.size();
+  h.ndil = S.rb.empty() ? 0 : (int)S.rb[0].dil.size();
+  if (h.nrb > ALCM_VOC_MAX_RB || h.ndil > ALCM_VOC_MAX_DIL)
+    throw Error(ALCM_E_INVALID, "bigvgan: at most 8 resblocks per stage and 8 dilations per resblock");
+  h.dense_weights = h.nrb && h.ndil && S.rb[0].c1[0].dw.p;
+  h.act0_equal = h.ndil > 0;
+  for (int j = 0; j < h.nrb; ++j) {
+    h.rb_k[j] = S.rb[j].k;
+    if (h.ndil)
+      h.act0_equal &= !std::memcmp(S.rb[j].act[0].fup, S.rb[0].act[0].fup, sizeof(S.rb[0].act[0].fup)) &&
+                      !std::memcmp(S.rb[j].act[0].fdn, S.rb[0].act[0].fdn, sizeof(S.rb[0].act[0].fdn));
+  }
+  for (int l = 0; l < h.ndil; ++l) h.dil[l] = S.rb[0].dil[l];
+  return h;
+}
+
 static void build_voc(Ingest& I, const int* ic, int nic) {
   VocW& G = I.m->voc;
   std::vector<int> rates = {4, 4, 2, 2, 2, 2}, kernels = {8, 8, 4, 4, 4, 4}, rk = {3, 7, 11}, dil = {1, 3, 5};
@@ -594,6 +618,7 @@ static void build_voc(Ingest& I, const int* ic, int nic) {
         A.act.push_back(build_act(I, rp + "activations." + std::to_string(a) + ".", S.cout));
       S.rb.push_back(A);
     }
+    G.shape.push_back(stage_shape(S));
     G.st.push_back(S);
   }
   const int ch = G.st.back().cout;
@@ -1278,17 +1303,25 @@ static int mel_forward(alcm_model* m, const float* wav, float* mel, int B, int L
 }
 
 // ------------------------------------------------------------------ BigVGAN
-struct VocChain {  // per-resblock scratch: running state ping-pong and the two operand-plane buffers
-  float *rb, *t;
-  u16 *pl, *pl2;  // Activation1d outputs as MFMA operand planes (each 2 planes of B * T * Cp)
+struct VocChain {  // a resblock chain's scratch
+  float *rb, *t;   // the fp32 running state and its spare
+  u16 *pl, *pl2;   // Activation1d outputs as MFMA operand planes (each 2 planes of B * T * Cp)
 };
+// Who may use which buffer when (the one statement of it; the code below relies on it):
+//   x      the stage input; from the chains' last convs on, the stage output (the mean over the resblocks)
+//   y      the upsampler output u: every chain's input and first residual until the stage closes
+//   ch[j]  chain j's, from the stage's fork (after the upsampler and activation1d_x3) to its close; a stage whose
+//          plan has no own_bufs runs every chain in ch[0], one after the other.  pl holds the planes the next conv
+//          reads and rb the running state.  The fused form puts conv1's Activation1d planes in pl2 and ping-pongs
+//          the state between rb and t (conv2's overlapping tiles re-read residual rows of their neighbours); the
+//          wide form passes conv1's output (fp32, or the h16 plane) through t
+//   between a close and the next fork only the caller's stream runs, and it uses the chains' buffers: conv_pre
+//          stages the channels-last mel in ch[1].t, a planes-form upsampler reads ch[0].pl (to_planes of x) or
+//          ch[0].pl2 (left by the previous stage's sum-form close), activation1d_x3 fills the three ch[j].pl, and
+//          activation_post -> conv_post goes through ch[0].pl
 struct VocWs {
   float *x, *y;
   VocChain ch[3];
-  int64_t pl_lo;
-  // legacy single-chain names (chain 0)
-  float *rb, *t;
-  u16 *pl, *pl2;
 };
 static size_t voc_elems(const VocW& G, int M) {
   size_t big = (size_t)M * G.c0;
@@ -1316,30 +1349,11 @@ static VocWs plan_voc(const VocW& G, Bump& bp, int B, int M) {
     c.pl = bp.take<u16>(2 * pe);
     c.pl2 = bp.take<u16>(2 * pe);
   }
-  w.rb = w.ch[0].rb;
-  w.t = w.ch[0].t;
-  w.pl = w.ch[0].pl;
-  w.pl2 = w.ch[0].pl2;
-  w.pl_lo = (int64_t)pe;
   return w;
 }
 
-// MFMA precision of the AMPBlock layers of stage si (scripts/precision_emulate.py):
-// mixed policy: fp16 for the three wide stages (~96% of the BigVGAN FLOPs), fp16 activation x fp16 hi+lo
-// weight for the narrow tail (the tail is sensitive to weight rounding, not to activation rounding);
-// conv_post stays bf16x3 (bigvgan_forward)
-static int voc_prec(const alcm_model* m, int si) {
-  if (m->policy == ALCM_POLICY_BF16) return PREC_BF16;
-  if (m->policy == ALCM_POLICY_SPLIT) return PREC_SPLIT;
-  // stage 3 (C = 96, the costliest tail stage) tolerates fp16 weights: +1e-5 waveform rel-L2 emulated,
-  // vs +2.5e-4 (stage 4) and +4.3e-4 (stage 5) (scripts/precision_emulate.py 96 tail)
-  return si < 4 ? PREC_F16 : PREC_F16W2;
-}
-
-static int act_planes(hipStream_t s, const ActW& a, const float* x, const VocWs& w, int B, int T, int C, int prec,
-                      u16* planes = nullptr) {
-  return activation1d_op(x, planes ? planes : w.pl, B, T, C, round_up(C, 32), a.aexp, a.ibeta, a.fup, a.fdn, prec,
-                         s);
+static int act_planes(hipStream_t s, const ActW& a, const float* x, u16* planes, int B, int T, int C, int prec) {
+  return activation1d_op(x, planes, B, T, C, round_up(C, 32), a.aexp, a.ibeta, a.fup, a.fdn, prec, s);
 }
 
 // the auxiliary resblock streams / events of caller stream s (nullptr: run the chains serially on s)
@@ -1362,52 +1376,153 @@ static const alcm_model::AuxSet* voc_streams(alcm_model* m, hipStream_t s) {
   return &(m->aux[s] = a);
 }
 
-// conv on the operand planes `in`; with `act` the epilogue also writes Activation1d(conv + bias (+ res)) into
-// the planes `act_out` (alcm_actepi.h), and `out` may be null
-// the narrow stages' AMPBlock convs on the resident-weight kernel (alcm_tconv.hip): every conv of the stage or none
-// (its planes keep stale operand-padding channels, which only that kernel ignores)
-static bool stage_tconv(const StageW& S, int prec) {
-  if (S.rb.empty() || !S.rb[0].c1[0].dw.p) return false;
-  for (const AmpW& A : S.rb)
-    for (size_t l = 0; l < A.dil.size(); ++l)
-      if (!tconv_supported(knobs(), prec, S.cout, S.cout, A.k, A.dil[l])) return false;
-  return true;
-}
-
-// the alcm_opconv arguments of a same-length conv of the planes `in` (default: the workspace planes); dense: the
-// alcm_opconv_dense arguments, which differ in the weight packing (cw.dw)
-static alcm_opconv_args plane_args(const ConvW& cw, const VocWs& w, int B, int T, int dil, const float* res, float* out,
-                                   float out_scale, int accumulate, int out_act, int prec, const u16* in,
-                                   bool dense = false) {
+// the alcm_opconv arguments of a same-length conv of the operand planes `in`, with no output yet: the caller names
+// what it wants (out, res, out_scale, accumulate, out_act, out_plane, act_epilogue).  dense: the alcm_opconv_dense
+// arguments, which differ in the weight packing (cw.dw)
+static alcm_opconv_args plane_args(const ConvW& cw, const u16* in, int B, int T, int dil, int prec, bool dense = false) {
   const Packed& pk = dense ? cw.dw : cw.w;
   alcm_opconv_args g;
   std::memset(&g, 0, sizeof(g));
-  g.a = in ? in : w.pl; g.a_lo_off = (int64_t)B * T * cw.w.cpad;
+  g.a = in; g.a_lo_off = (int64_t)B * T * cw.w.cpad;
   g.B = B; g.T = T; g.C = cw.w.cin; g.Cp = cw.w.cpad;
   g.ksize = cw.w.taps; g.dil = dil; g.pad = (cw.w.taps - 1) * dil / 2;
   g.w = pk.p; g.w_lo_off = pk.lo; g.kpad = pk.kpad; g.N = cw.w.rows;
-  g.bias = cw.b; g.res = res; g.out = out; g.out_act = out_act; g.accumulate = accumulate;
-  g.out_scale = out_scale; g.prec = prec;
+  g.bias = cw.b; g.out_scale = 1.f; g.prec = prec;
   return g;
 }
-
-static int plane_conv(hipStream_t s, const ConvW& cw, const VocWs& w, int B, int T, int dil, const float* res,
-                      float* out, float out_scale, int accumulate, int out_act, int prec, const u16* in = nullptr,
-                      const ActW* act = nullptr, u16* act_out = nullptr, bool dense = false,
-                      void* out_plane = nullptr) {
-  alcm_opconv_args g = plane_args(cw, w, B, T, dil, res, out, out_scale, accumulate, out_act, prec, in, dense);
-  if (act) {
-    g.act_plane = act_out;
-    g.act_plane_lo_off = (int64_t)B * T * round_up(cw.w.rows, 32);
-    g.act_alpha_exp = act->aexp;
-    g.act_inv_beta = act->ibeta;
-    g.act_up_filter = act->fup;
-    g.act_down_filter = act->fdn;
-  }
-  g.out_plane = out_plane;
-  return dense ? opconv_dense(g, s) : opconv(g, s);
+// the epilogue also writes Activation1d(conv + bias (+ res)) into the operand planes `planes` (alcm_actepi.h)
+static void act_epilogue(alcm_opconv_args& g, const ActW& act, u16* planes) {
+  g.act_plane = planes;
+  g.act_plane_lo_off = (int64_t)g.B * g.T * round_up(g.N, 32);
+  g.act_alpha_exp = act.aexp;
+  g.act_inv_beta = act.ibeta;
+  g.act_up_filter = act.fup;
+  g.act_down_filter = act.fdn;
 }
 
+// The upsampler forms (VocUps): ConvTranspose1d as S.rate phase convs (models.py:160-165, 187-188),
+// x (B, T, cin) -> u (B, T * rate, cout).
+// VU_PLANES: plane convs with a strided epilogue on the operand planes pl of x, made here unless the previous
+// stage's close left them (x == nullptr)
+static int ups_planes(hipStream_t s, const StageW& S, int prec, int B, int T, const float* x, u16* pl, float* u) {
+  if (x) ALCM_TRY(to_planes(x, pl, (int64_t)B * T, S.cin, S.cin, prec, s));
+  for (int r = 0; r < S.rate; ++r) {
+    alcm_opconv_args g = plane_args(S.phase[r], pl, B, T, 1, prec);
+    g.pad = S.pad[r];
+    g.out = u; g.out_stride = S.rate; g.out_offset = S.off[r]; g.out_rows = T * S.rate;
+    ALCM_TRY(opconv(g, s));
+  }
+  return 0;
+}
+// VU_UPS2: both phases of a stride-2 stage in one split-precision pass over x
+static int ups_two(hipStream_t s, const StageW& S, int B, int T, const float* x, float* u) {
+  return ups2(x, u, B, T, S.cin, S.cout, S.phase[0].w.p, S.phase[1].w.p, S.phase[0].w.lo, S.phase[0].w.kpad,
+              S.pad.data(), S.off.data(), S.phase[0].b, s);
+}
+// VU_PHASES: fp32-operand convs at the base precision
+static int ups_phases(hipStream_t s, const StageW& S, int split, int B, int T, const float* x, float* u) {
+  for (int r = 0; r < S.rate; ++r) {
+    ConvOpts o;
+    o.pad = S.pad[r];
+    ALCM_TRY(conv(s, split, B, T, cl(x, T, S.cin), S.phase[r],
+                  Out{u, (int64_t)T * S.rate * S.cout, S.cout, 1, S.rate, S.off[r]}, o));
+  }
+  return 0;
+}
+
+// the three chains' first Activation1d in one pass over u, into their own planes (VocStagePlan::act3)
+static int act_first3(hipStream_t s, const StageW& S, int prec, int B, int T, const float* u, const VocWs& w) {
+  void* ys[3] = {w.ch[0].pl, w.ch[1].pl, w.ch[2].pl};
+  const float* ae[3] = {S.rb[0].act[0].aexp, S.rb[1].act[0].aexp, S.rb[2].act[0].aexp};
+  const float* ib[3] = {S.rb[0].act[0].ibeta, S.rb[1].act[0].ibeta, S.rb[2].act[0].ibeta};
+  return activation1d_x3(u, ys, B, T, S.cout, round_up(S.cout, 32), ae, ib, S.rb[0].act[0].fup, S.rb[0].act[0].fdn,
+                         prec, s);
+}
+
+// One resblock chain of a stage: AMPBlock1(k, dilations)(u) / nrb into x (models.py:190-199, 72-81); each half-layer
+// is Activation1d -> operand planes -> implicit-GEMM conv on the planes.  Chain j runs on stream sj in the buffers cb;
+// before its last layer it waits for `turn` (the chain before it has added its share to x), if there is one.
+struct VocStage {  // what the chains of a stage share
+  const StageW& S;
+  const VocStagePlan& p;
+  int B, T;        // T: the stage's output length
+  const float* u;  // the upsampler output
+  float* x;        // the stage output
+};
+
+// The fused forms (VA_FUSED, VA_FUSED_DENSE): only the chain's first Activation1d runs standalone (unless act3 ran
+// it); every later one runs in the epilogue of the conv that produces its input.  conv1 writes only planes; conv2
+// writes the fp32 running state plus planes.
+static int chain_fused(const VocStage& st, size_t j, const VocChain& cb, hipStream_t sj, hipEvent_t turn) {
+  const AmpW& A = st.S.rb[j];
+  const int B = st.B, T = st.T, prec = st.p.prec;
+  const bool dense = st.p.amp == VA_FUSED_DENSE;
+  const auto run = dense ? opconv_dense : opconv;
+  const float* cur = st.u;
+  float* nxt = cb.rb;
+  for (size_t l = 0; l < A.dil.size(); ++l) {
+    const bool last = l + 1 == A.dil.size();
+    if (last && turn) ALCM_HIP(hipStreamWaitEvent(sj, turn, 0));
+    if (l == 0 && !st.p.act3) ALCM_TRY(act_planes(sj, A.act[0], cur, cb.pl, B, T, st.S.cout, prec));
+    alcm_opconv_args c1 = plane_args(A.c1[l], cb.pl, B, T, A.dil[l], prec, dense);
+    act_epilogue(c1, A.act[2 * l + 1], cb.pl2);
+    ALCM_TRY(run(c1, sj));
+    alcm_opconv_args c2 = plane_args(A.c2[l], cb.pl2, B, T, 1, prec, dense);
+    c2.res = cur;
+    if (last) {
+      c2.out = st.x; c2.out_scale = 1.0f / (float)st.S.rb.size(); c2.accumulate = j > 0;
+    } else {
+      c2.out = nxt;
+      act_epilogue(c2, A.act[2 * l + 2], cb.pl);
+    }
+    ALCM_TRY(run(c2, sj));
+    cur = nxt;
+    nxt = nxt == cb.rb ? cb.t : cb.rb;  // never the buffer the next conv2 takes its residual from
+  }
+  return 0;
+}
+
+// The wide form (VA_WIDE): every Activation1d standalone (the first by act3 where planned).  h16: conv1's only
+// consumer is the next Activation1d, whose MFMA kernel rounds its input to fp16, so conv1 writes that fp16 plane
+// (into the fp32 scratch cb.t) and the activation reads it, bit-identical at half the bytes.  sum_term (the plan's
+// sum3): the last conv2 is not launched but returned as the chain's term of the stage's alcm_opconv_sum.
+static int chain_wide(const VocStage& st, size_t j, const VocChain& cb, hipStream_t sj, hipEvent_t turn,
+                      alcm_opconv_args* sum_term) {
+  const AmpW& A = st.S.rb[j];
+  const int B = st.B, T = st.T, C = st.S.cout, prec = st.p.prec;
+  const float* cur = st.u;
+  for (size_t l = 0; l < A.dil.size(); ++l) {
+    const bool last = l + 1 == A.dil.size();
+    if (last && turn) ALCM_HIP(hipStreamWaitEvent(sj, turn, 0));
+    if (!(l == 0 && st.p.act3)) ALCM_TRY(act_planes(sj, A.act[2 * l], cur, cb.pl, B, T, C, prec));
+    alcm_opconv_args c1 = plane_args(A.c1[l], cb.pl, B, T, A.dil[l], prec);
+    const ActW& a2 = A.act[2 * l + 1];
+    if (st.p.h16) {
+      c1.out_plane = cb.t;
+      ALCM_TRY(opconv(c1, sj));
+      ALCM_TRY(activation1d_op_h16(cb.t, cb.pl, B, T, C, round_up(C, 32), a2.aexp, a2.ibeta, a2.fup, a2.fdn, prec, sj));
+    } else {
+      c1.out = cb.t;
+      ALCM_TRY(opconv(c1, sj));
+      ALCM_TRY(act_planes(sj, a2, cb.t, cb.pl, B, T, C, prec));
+    }
+    alcm_opconv_args c2 = plane_args(A.c2[l], cb.pl, B, T, 1, prec);
+    c2.res = cur;
+    c2.out = last ? st.x : cb.rb;
+    if (last) c2.out_scale = 1.0f / (float)st.S.rb.size();
+    if (last && sum_term) {
+      if (j > 0) c2.out = nullptr;  // a sum writes through its first term
+      *sum_term = c2;
+    } else {
+      c2.accumulate = last && j > 0;
+      ALCM_TRY(opconv(c2, sj));
+    }
+    cur = cb.rb;
+  }
+  return 0;
+}
+
+// Executes the stage plans (alcm_vocplan.h), which hold every decision: this function only launches.
 static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, int M, void* ws, size_t wsb,
                            hipStream_t s) {
   const VocW& G = m->voc;
@@ -1416,12 +1531,18 @@ static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, i
   Bump bp(ws, wsb);
   VocWs w = plan_voc(G, bp, B, M);
   if (!ws || bp.off > wsb) return set_error(ALCM_E_WORKSPACE, "bigvgan_forward: workspace too small");
+  // whether the chains' auxiliary streams exist is a run-time fact (switched off, or not creatable: serial chains);
+  // the plan is made with it
+  const alcm_model::AuxSet* ax = voc_streams(m, s);
+  std::vector<VocStagePlan> plan(G.st.size());
+  if (voc_plan(G.shape.data(), (int)G.shape.size(), m->policy, ax != nullptr, B, M, device_cus(), knobs(), plan.data()))
+    return set_error(ALCM_E_INVALID, "bigvgan_forward: stage shapes the planner does not take");
   // conv_pre k7 on the NCT mel (models.py:183)
   {
     ConvOpts o;
     o.pad = 3;
-    // the NCT mel as channels-last rows (chain 1's fp32 scratch, free until the first stage's chains), read as whole
-    // vectors instead of a stride-M gather per element (ALCM_NCT_CL=0: the gather)
+    // the NCT mel as channels-last rows, read as whole vectors instead of a stride-M gather per element
+    // (ALCM_NCT_CL=0: the gather)
     const int cp = G.pre.w.cpad;
     View mv{mel, (int64_t)G.num_mels * M, 1, M, M, G.num_mels};
     if (knobs().nct_cl && cp % 4 == 0) {
@@ -1430,169 +1551,46 @@ static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, i
     }
     ALCM_TRY(conv(s, split, B, M, mv, G.pre, ocl(w.x, M, G.c0), o));
   }
-  // buffer roles: x = stage input and (after the upsampler) stage output accumulator,
-  // u = upsampler output (resblock input), rb = resblock running state, a / y = scratch
   int T = M;
   float* x = w.x;
   float* u = w.y;
-  float* rb = w.rb;
-  float* y = w.t;
-  // stage si's upsampler runs on operand planes of its input (mixed policy: stages 0-3, +1.9e-4 waveform rel-L2
-  // emulated, scripts/precision_emulate.py 96 tail): a plane conv of x with a strided epilogue (the wide-layer kernel
-  // for N % 192 == 0, opconv_kernel for N <= 96) — the same eligibility opconv's strided paths check (the wide-layer
-  // kernel needs Cp % 64 == 0 and a tap window of at most 64 rows; otherwise the fp32-operand phase conv below)
-  auto ups_planes_of = [&](size_t si) {
-    const StageW& S = G.st[si];
-    const int pamp = voc_prec(m, (int)si);
-    const bool wide_ok = S.cout % 192 == 0 && S.cin % 64 == 0 && S.phase[0].w.taps - 1 <= 64;
-    return (pamp == PREC_F16 || pamp == PREC_BF16) && S.cin % 32 == 0 &&
-           (wide_ok || (S.cout <= 96 && S.cout % 4 == 0)) && S.phase[0].w.cpad == S.cin;
-  };
-  const u16* xpl = nullptr;  // the stage input's planes when the previous stage's sum-form conv wrote them
   for (size_t si = 0; si < G.st.size(); ++si) {
     const StageW& S = G.st[si];
+    const VocStagePlan& p = plan[si];
     const int To = T * S.rate;
-    const int pamp = voc_prec(m, (int)si);
-    // ConvTranspose1d as S.rate phase convolutions (models.py:160-165, 187-188): on operand planes of x where
-    // ups_planes_of(si), the fp32-operand conv at the base precision otherwise
-    const bool ups_planes = ups_planes_of(si);
-    const u16* upl = xpl ? xpl : w.pl;
-    if (ups_planes && !xpl) ALCM_TRY(to_planes(x, w.pl, (int64_t)B * T, S.cin, S.cin, pamp, s));
-    xpl = nullptr;
-    // the split-precision stride-2 stages with the kernel's widths (stages 4-5): both phases in one pass over x
-    const bool ups_two = !ups_planes && split == PREC_SPLIT && S.rate == 2 &&
-                         ups2_supported(S.cin, S.cout, S.phase[0].w.cpad, S.rate, S.phase[0].w.taps) &&
-                         S.phase[1].w.kpad == S.phase[0].w.kpad && S.phase[1].w.lo == S.phase[0].w.lo;
-    if (ups_two)
-      ALCM_TRY(ups2(x, u, B, T, S.cin, S.cout, S.phase[0].w.p, S.phase[1].w.p, S.phase[0].w.lo, S.phase[0].w.kpad,
-                    S.pad.data(), S.off.data(), S.phase[0].b, s));
-    for (int r = 0; r < S.rate && !ups_two; ++r) {
-      if (ups_planes) {
-        const ConvW& cw = S.phase[r];
-        alcm_opconv_args g;
-        std::memset(&g, 0, sizeof(g));
-        g.a = upl; g.a_lo_off = (int64_t)B * T * S.cin;
-        g.B = B; g.T = T; g.C = S.cin; g.Cp = S.cin;
-        g.ksize = cw.w.taps; g.dil = 1; g.pad = S.pad[r];
-        g.w = cw.w.p; g.w_lo_off = cw.w.lo; g.kpad = cw.w.kpad; g.N = cw.w.rows;
-        g.bias = cw.b; g.out = u; g.out_scale = 1.f; g.prec = pamp;
-        g.out_stride = S.rate; g.out_offset = S.off[r]; g.out_rows = To;
-        ALCM_TRY(opconv(g, s));
-        continue;
-      }
-      ConvOpts o;
-      o.pad = S.pad[r];
-      ALCM_TRY(conv(s, split, B, T, cl(x, T, S.cin), S.phase[r],
-                    Out{u, (int64_t)To * S.cout, S.cout, 1, S.rate, S.off[r]}, o));
+    if (p.ups == VU_PLANES)
+      ALCM_TRY(ups_planes(s, S, p.prec, B, T, p.planes_from_prev ? nullptr : x,
+                          p.planes_from_prev ? w.ch[0].pl2 : w.ch[0].pl, u));
+    else if (p.ups == VU_UPS2) ALCM_TRY(ups_two(s, S, B, T, x, u));
+    else ALCM_TRY(ups_phases(s, S, split, B, T, x, u));
+    if (p.act3) ALCM_TRY(act_first3(s, S, p.prec, B, To, u, w));
+    const alcm_model::AuxSet* fork = p.concurrent ? ax : nullptr;
+    if (fork) {  // the chains start after the upsampler wrote u
+      ALCM_HIP(hipEventRecord(fork->ev[0], s));
+      for (auto a : fork->s) ALCM_HIP(hipStreamWaitEvent(a, fork->ev[0], 0));
     }
-    // x = mean over k in (3,7,11) of AMPBlock1(k, (1,3,5))(u)  (models.py:190-199, 72-81); each half-layer
-    // is Activation1d -> operand planes -> implicit-GEMM conv on the planes.  Fused form (every stage the
-    // kernels support at this precision): the first Activation1d of a resblock runs standalone (act_op); every
-    // later one runs in the epilogue of the conv that produces its input (conv1 writes only planes; conv2
-    // writes the fp32 running state, ping-ponged between rb and y since its tiles overlap, plus planes)
-    const float inv = 1.0f / (float)S.rb.size();
-    const bool fuse = opconv_act_supported(pamp, S.cout, round_up(S.cout, 32));
-    const bool dense = fuse && stage_tconv(S, pamp);
-    const alcm_model::AuxSet* ax = S.rb.size() <= 3 ? voc_streams(m, s) : nullptr;
-    const bool conc = ax != nullptr;
-    // the wide stages' conv1 -> Activation1d hand-off as an fp16 plane (ALCM_CONV1_H16=0: fp32, the A/B reference).
-    // Only from B * To >= 1024 rows, where the fp32 route takes the same wide kernel (below it the fp32 output would
-    // go to opconv_kernel, whose K order differs): the A/B stays bit-exact at every size
-    const bool h16 = knobs().conv1_h16 && pamp == PREC_F16 && act_mfma_ok(S.cout, round_up(S.cout, 32), pamp) &&
-                     (int64_t)B * To >= 1024;
-    // the three chains' first Activation1d in one pass over u (their own planes, same taps) — with the chains on
-    // their streams and serialised alike (each chain on its own buffers then), so the serialised profile pass runs
-    // the same kernels as the concurrent one
-    // (the narrow fused stages: the VALU kernel; the wide MFMA-FIR stages: its three-set form, ALCM_ACT_X3_MFMA)
-    const bool amok = act_mfma_ok(S.cout, round_up(S.cout, 32), pamp);
-    bool act3 = S.rb.size() == 3 && (fuse ? !amok : (amok && knobs().act_x3_mfma));
-    for (size_t j = 1; act3 && j < S.rb.size(); ++j)
-      act3 = !std::memcmp(S.rb[j].act[0].fup, S.rb[0].act[0].fup, sizeof(S.rb[0].act[0].fup)) &&
-             !std::memcmp(S.rb[j].act[0].fdn, S.rb[0].act[0].fdn, sizeof(S.rb[0].act[0].fdn));
-    if (act3) {
-      void* ys[3] = {w.ch[0].pl, w.ch[1].pl, w.ch[2].pl};
-      const float* ae[3] = {S.rb[0].act[0].aexp, S.rb[1].act[0].aexp, S.rb[2].act[0].aexp};
-      const float* ib[3] = {S.rb[0].act[0].ibeta, S.rb[1].act[0].ibeta, S.rb[2].act[0].ibeta};
-      ALCM_TRY(activation1d_x3(u, ys, B, To, S.cout, round_up(S.cout, 32), ae, ib, S.rb[0].act[0].fup,
-                               S.rb[0].act[0].fdn, pamp, s));
-    }
-    if (conc) {  // chains start after the upsampler wrote u
-      ALCM_HIP(hipEventRecord(ax->ev[0], s));
-      for (auto a : ax->s) ALCM_HIP(hipStreamWaitEvent(a, ax->ev[0], 0));
-    }
-    // the wide stages' mean over the three chains in one sum-form launch of their last conv2 + residual
-    // (alcm_opconv_sum): x written once, not read and rewritten per chain (ALCM_WCONV_SUM=0: three accumulating
-    // launches, the chains' last convs in order)
-    const bool sum3 = !fuse && S.rb.size() == 3 && (conc || act3) && knobs().wconv_sum;
+    const VocStage st{S, p, B, To, u, x};
     alcm_opconv_args lastc[3];
     for (size_t j = 0; j < S.rb.size(); ++j) {
-      const AmpW& A = S.rb[j];
-      const VocChain& cb = w.ch[(conc || act3) ? j : 0];
-      const hipStream_t sj = (conc && j > 0) ? ax->s[j - 1] : s;
-      const float* cur = u;
-      float* nxt = cb.rb;
-      for (size_t l = 0; l < A.dil.size(); ++l) {
-        const bool last = l + 1 == A.dil.size();
-        // the mean over resblocks accumulates into x: the chains' last convs run in order (j-1 before j)
-        if (last && conc && j > 0 && !sum3) ALCM_HIP(hipStreamWaitEvent(sj, ax->ev[j], 0));
-        if (fuse) {
-          if (l == 0 && !act3) ALCM_TRY(act_planes(sj, A.act[0], cur, w, B, To, S.cout, pamp, cb.pl));
-          ALCM_TRY(plane_conv(sj, A.c1[l], w, B, To, A.dil[l], nullptr, nullptr, 1.f, 0, 0, pamp, cb.pl,
-                              &A.act[2 * l + 1], cb.pl2, dense));
-          if (last) {
-            ALCM_TRY(plane_conv(sj, A.c2[l], w, B, To, 1, cur, x, inv, j > 0, 0, pamp, cb.pl2, nullptr, nullptr,
-                                dense));
-          } else {
-            ALCM_TRY(plane_conv(sj, A.c2[l], w, B, To, 1, cur, nxt, 1.f, 0, 0, pamp, cb.pl2, &A.act[2 * l + 2],
-                                cb.pl, dense));
-            cur = nxt;
-            nxt = nxt == cb.rb ? cb.t : cb.rb;
-          }
-        } else {
-          if (!(l == 0 && act3)) ALCM_TRY(act_planes(sj, A.act[2 * l], cur, w, B, To, S.cout, pamp, cb.pl));
-          if (h16) {
-            // conv1's only consumer is the next Activation1d, whose MFMA kernel rounds its input to fp16: conv1 writes
-            // that fp16 plane (into the fp32 scratch cb.t) and the activation reads it, bit-identical at half the bytes
-            ALCM_TRY(plane_conv(sj, A.c1[l], w, B, To, A.dil[l], nullptr, nullptr, 1.f, 0, 0, pamp, cb.pl, nullptr,
-                                nullptr, false, cb.t));
-            const ActW& a2 = A.act[2 * l + 1];
-            ALCM_TRY(activation1d_op_h16(cb.t, cb.pl, B, To, S.cout, round_up(S.cout, 32), a2.aexp, a2.ibeta, a2.fup,
-                                         a2.fdn, pamp, sj));
-          } else {
-            ALCM_TRY(plane_conv(sj, A.c1[l], w, B, To, A.dil[l], nullptr, cb.t, 1.f, 0, 0, pamp, cb.pl));
-            ALCM_TRY(act_planes(sj, A.act[2 * l + 1], cb.t, w, B, To, S.cout, pamp, cb.pl));
-          }
-          if (last && sum3)
-            lastc[j] = plane_args(A.c2[l], w, B, To, 1, cur, j == 0 ? x : nullptr, inv, 0, 0, pamp, cb.pl);
-          else
-            ALCM_TRY(plane_conv(sj, A.c2[l], w, B, To, 1, cur, last ? x : cb.rb, last ? inv : 1.f, last && j > 0, 0,
-                                pamp, cb.pl));
-          cur = cb.rb;
-        }
-        if (last && conc) ALCM_HIP(hipEventRecord(ax->ev[j + 1], sj));
-      }
+      const VocChain& cb = w.ch[p.own_bufs ? j : 0];
+      const hipStream_t sj = (fork && j > 0) ? fork->s[j - 1] : s;
+      // the mean over the resblocks accumulates into x: the chains' last convs run in order (j - 1 before j), unless
+      // the sum form takes all three
+      const hipEvent_t turn = (fork && j > 0 && !p.sum3) ? fork->ev[j] : nullptr;
+      if (p.amp == VA_WIDE) ALCM_TRY(chain_wide(st, j, cb, sj, turn, p.sum3 ? &lastc[j] : nullptr));
+      else ALCM_TRY(chain_fused(st, j, cb, sj, turn));
+      if (fork) ALCM_HIP(hipEventRecord(fork->ev[j + 1], sj));
     }
-    if (sum3) {
-      if (conc)
-        for (size_t j = 1; j < S.rb.size(); ++j) ALCM_HIP(hipStreamWaitEvent(s, ax->ev[j + 1], 0));
-      // the next stage's upsampler reads only the operand planes of this output: the sum-form epilogue writes them
-      // (the rounding to_planes applies to the fp32 value, bit for bit) into chain 0's spare plane buffer, free
-      // until the next stage's chains start
-      if (knobs().wconv_sum == 1 && si + 1 < G.st.size() && ups_planes_of(si + 1) && voc_prec(m, (int)si + 1) == pamp &&
-          G.st[si + 1].cin == S.cout) {
-        alcm_opconv_args pc[3] = {lastc[0], lastc[1], lastc[2]};
-        pc[0].out = nullptr;
-        pc[0].out_plane = w.ch[0].pl2;
-        ConvPlan pl[3];
-        int launches = 0;
-        if (conv_sum_plan(pc, 3, device_cus(), knobs(), pl, &launches) == 0 && pl[0].kernel == CK_WCONV3_SUM) {
-          lastc[0] = pc[0];
-          xpl = w.ch[0].pl2;
-        }
+    if (p.sum3) {
+      if (fork)
+        for (size_t j = 1; j < S.rb.size(); ++j) ALCM_HIP(hipStreamWaitEvent(s, fork->ev[j + 1], 0));
+      if (p.writes_next) {  // the next stage's input planes instead of the fp32 output
+        lastc[0].out = nullptr;
+        lastc[0].out_plane = w.ch[0].pl2;
       }
       ALCM_TRY(opconv_sum(lastc, 3, s));
-    } else if (conc) {
-      ALCM_HIP(hipStreamWaitEvent(s, ax->ev[S.rb.size()], 0));  // the stage output is complete
+    } else if (fork) {
+      ALCM_HIP(hipStreamWaitEvent(s, fork->ev[S.rb.size()], 0));  // the stage output is complete
     }
     T = To;
   }
@@ -1615,8 +1613,10 @@ static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, i
     }
     return 0;
   }
-  ALCM_TRY(act_planes(s, G.post_act, x, w, B, T, G.st.back().cout, ppost));
-  return plane_conv(s, G.post, w, B, T, 1, nullptr, wav, 1.f, 0, ACT_TANH, ppost);
+  ALCM_TRY(act_planes(s, G.post_act, x, w.ch[0].pl, B, T, G.st.back().cout, ppost));
+  alcm_opconv_args g = plane_args(G.post, w.ch[0].pl, B, T, 1, ppost);
+  g.out = wav; g.out_act = ACT_TANH;
+  return opconv(g, s);
 }
 
 // ------------------------------------------------------------------ text conditioning
@@ -2059,6 +2059,13 @@ extern "C" int alcm_bigvgan_forward(alcm_model* m, const float* mel, float* wav_
                                     size_t ws_bytes, alcm_stream_t stream) {
   if (!m || m->kind != ALCM_MODEL_BIGVGAN || !mel || !wav_out) return set_error(ALCM_E_INVALID, "bigvgan: bad args");
   return bigvgan_forward(m, mel, wav_out, B, M, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int alcm_debug_voc_plan(const alcm_voc_stage_shape* shapes, int n, int policy, int streams, int B, int M,
+                                   int ncu, alcm_voc_stage_plan* out) {
+  if (voc_plan(shapes, n, policy, streams != 0, B, M, ncu > 0 ? ncu : device_cus(), knobs(), out))
+    return set_error(ALCM_E_INVALID, "debug_voc_plan: bad arguments");
+  return 0;
 }
 
 extern "C" size_t alcm_text_workspace_bytes(const alcm_model* m, int B, int L) {

@@ -45,7 +45,7 @@ int activation1d_x3(const float* x, void* const y[3], int B, int T, int C, int C
   }
   void* tok = prof_start(s);
   // the wide stages' MFMA FIR kernel where it applies (its fp16 FIR inputs: the mixed policy's stages 0-2)
-  const bool am = knobs().act_x3_mfma && act_mfma_ok(C, Cp, prec) && !(((uintptr_t)x) & 15) &&
+  const bool am = knobs().act_x3_mfma && act_mfma_ok(knobs(), C, Cp, prec) && !(((uintptr_t)x) & 15) &&
                   !(((uintptr_t)y[0]) & 15) && !(((uintptr_t)y[1]) & 15) && !(((uintptr_t)y[2]) & 15);
   if (am) ALCM_TRY(act_mfma3(x, y, B, T, C, Cp, alpha_exp, inv_beta, f, s));
   else ALCM_TRY(act_coop(x, y, 3, B, T, C, Cp, alpha_exp, inv_beta, f, prec, s));
@@ -68,7 +68,7 @@ int activation1d_op_h16(const void* x16, void* y, int B, int T, int C, int Cp, c
                         hipStream_t s) {
   if (!x16 || !y || !alpha_exp || !inv_beta || !up_filter || !down_filter || B <= 0 || T <= 0 || C <= 0)
     return set_error(ALCM_E_INVALID, "activation1d_op_f16in: bad arguments");
-  if (!act_mfma_ok(C, Cp, prec) || (((uintptr_t)x16) & 15) || (((uintptr_t)y) & 15))
+  if (!act_mfma_ok(knobs(), C, Cp, prec) || (((uintptr_t)x16) & 15) || (((uintptr_t)y) & 15))
     return set_error(ALCM_E_INVALID, "activation1d_op_f16in: needs prec F16, C >= 192, C % 64 == 0, Cp == C and "
                                      "16-byte aligned x / y");
   Taps12O f;
@@ -101,7 +101,7 @@ int activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const 
     f.up[k] = 2.0f * up_filter[k];
     f.dn[k] = down_filter[k];
   }
-  if (act_mfma_ok(C, Cp, prec) && !(((uintptr_t)x) & 15) && !(((uintptr_t)y) & 15)) {  // both FIRs on MFMA (alcm_act.hip): the wide stages under the mixed policy
+  if (act_mfma_ok(knobs(), C, Cp, prec) && !(((uintptr_t)x) & 15) && !(((uintptr_t)y) & 15)) {  // both FIRs on MFMA (alcm_act.hip): the wide stages under the mixed policy
     void* tok = prof_start(s);
     ALCM_TRY(act_mfma(x, false, y, B, T, C, Cp, alpha_exp, inv_beta, f, s));
     if (tok) {

@@ -188,11 +188,6 @@ __global__ __launch_bounds__(512, (UpsGeo<CP, NOUT>::OCC)) void ups2_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------------------ host
-bool ups2_supported(int cin, int cout, int cpad, int rate, int taps) {
-  if (rate != 2 || taps != 2) return false;
-  return (cin == 96 && cpad == 96 && cout == 48) || (cin == 48 && cpad == 48 && cout == 24);
-}
-
 int ups2(const float* x, float* out, int B, int T, int cin, int cout, const u16* w0, const u16* w1, int64_t lo,
          int kpad, const int pad[2], const int off[2], const float* bias, hipStream_t s) {
   const int cpad = cin;

@@ -535,6 +535,30 @@ def conv_plan(args, ncu: int = 0, dense: bool = False) -> list:
     return _hip.debug_conv_plan(arr, len(args), _hip.PLAN_SUM, ncu)
 
 
+def voc_stage_shapes(cfg) -> list:
+    """The BigVGAN stages of a recipe.BigVGANConfig as the stage planner reads them (_hip.VocStageShape), as the
+    library's loader derives them from the packed weights: phase weights of one shape, the tail convs' dense packing
+    for cout <= 96 with cout % 8 == 0, and the resblocks' Activation1d filters equal (one kaiser-sinc design)."""
+    shapes = []
+    for i, (rate, k) in enumerate(zip(cfg.upsample_rates, cfg.upsample_kernel_sizes)):
+        h = _hip.VocStageShape()
+        h.cin, h.cout, h.rate, h.taps = cfg.upsample_initial_channel >> i, cfg.stage_channels(i), rate, k // rate
+        h.cpad = (h.cin + 7) // 8 * 8
+        h.phases_share = h.act0_equal = 1
+        h.dense_weights = int(h.cout <= 96 and h.cout % 8 == 0)
+        h.nrb, h.ndil = len(cfg.resblock_kernel_sizes), len(cfg.resblock_dilation_sizes[0])
+        h.rb_k[:h.nrb] = cfg.resblock_kernel_sizes
+        h.dil[:h.ndil] = cfg.resblock_dilation_sizes[0]
+        shapes.append(h)
+    return shapes
+
+
+def voc_plan(cfg, policy, streams: bool, B: int, M: int, ncu: int = 0) -> list:
+    """What every BigVGAN stage of `cfg` runs at batch B and M mel frames under the policy (a name in _hip.POLICIES or
+    its code) and the current ALCM_* switches: one dict of the alcm_voc_stage_plan fields per stage."""
+    return _hip.debug_voc_plan(voc_stage_shapes(cfg), _hip.POLICIES.get(policy, policy), streams, B, M, ncu)
+
+
 def opconv_sum(terms, prec: int, out_scale: float = 1.0, accumulate_into: Optional[torch.Tensor] = None,
                out_plane: bool = False):
     """alcm_opconv_sum: out (B, T, N) = (sum over terms of conv_k(planes) + bias + residual) * out_scale (+ out) — the

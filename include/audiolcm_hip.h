@@ -416,6 +416,38 @@ typedef struct alcm_conv_plan_info {
 } alcm_conv_plan_info;
 int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int form, int ncu, alcm_conv_plan_info* out,
                          int* launches);
+/* The BigVGAN stage planner (alcm_vocplan.h).  A stage's static shape: the upsampler ConvTranspose1d cin -> cout
+ * at `rate` as `rate` phase convs of `taps` taps on input rows padded to `cpad` channels, and nrb AMPBlock1 resblocks of
+ * kernel size rb_k[j] with the ndil dilations dil[] (one set for the stage's resblocks). */
+enum { ALCM_VOC_MAX_RB = 8, ALCM_VOC_MAX_DIL = 8 };
+typedef struct alcm_voc_stage_shape {
+  int cin, cout, rate, taps, cpad;
+  int phases_share;  /* the phases' packed weights share kpad and the lo-plane offset */
+  int dense_weights; /* the resblock convs also have the tail convs' dense packing */
+  int act0_equal;    /* the resblocks' first Activation1d FIR taps are equal */
+  int nrb, rb_k[ALCM_VOC_MAX_RB];
+  int ndil, dil[ALCM_VOC_MAX_DIL];
+} alcm_voc_stage_shape;
+/* What a stage runs.  ups: 0 = phase convs on operand planes of the stage input, 1 = both phases of a
+ * stride-2 stage in one split-precision pass (ups2), 2 = fp32-operand phase convs.  amp: 0 = fused (Activation1d in
+ * the conv epilogues), 1 = fused on the tail convs' dense weights, 2 = wide (standalone Activation1d). */
+typedef struct alcm_voc_stage_plan {
+  int prec;             /* ALCM_PREC_* of the AMPBlock convs (and of a planes-form upsampler) */
+  int ups;
+  int planes_from_prev; /* ups == 0: the previous stage's sum-form close wrote the input planes */
+  int amp;
+  int h16;              /* wide: conv1 hands its Activation1d an fp16 plane */
+  int act3;             /* the three chains' first Activation1d in one launch */
+  int concurrent;       /* chains 1.. on the auxiliary streams */
+  int own_bufs;         /* chain j works in its own buffers (otherwise every chain in chain 0's) */
+  int sum3;             /* wide: the three chains' last conv2 + residual as one alcm_opconv_sum call */
+  int writes_next;      /* sum3: one launch, which writes the next stage's input planes instead of fp32 */
+} alcm_voc_stage_plan;
+/* diagnostics: the plans alcm_bigvgan_forward would execute for n stages at batch B and M mel frames under `policy`
+ * (ALCM_POLICY_*) and the current ALCM_* switches, with the resblock streams on or off, on ncu compute units (<= 0:
+ * the current device's), one per stage into out.  Host only; with ncu > 0 no device is needed. */
+int alcm_debug_voc_plan(const alcm_voc_stage_shape* shapes, int n, int policy, int streams, int B, int M, int ncu,
+                        alcm_voc_stage_plan* out);
 /* diagnostics: the K-part count both K-split users take (alcm_convplan.h ksplit_parts) */
 int alcm_debug_ksplit_parts(int64_t tiles, int64_t slots, int chunks, double elems, double ws_floats);
 /* diagnostics: the BigVGAN tail-conv phase trace (ALCM_TCONV_TRACE=1, which selects the tail convs' diagnostics

@@ -711,7 +711,88 @@ static int conv(hipStream_t s, int split, int B, int rows_per_batch, const View&
   return gemm(g, s);
 }
 
-static int lin(hipStream_t s, int prec, int R, const float* x, int C, const ConvW& w, float* y, const ConvOpts& o);
+// y (R, N) = x (R, C) W^T (+ bias) with the conv helper (k = 1): rows are one "batch" of R tokens
+static int lin(hipStream_t s, int prec, int R, const float* x, int C, const ConvW& w, float* y, const ConvOpts& o) {
+  return conv(s, prec, 1, R, View{x, 0, C, 1, R, C}, w, Out{y, 0, w.w.rows, 1, 1, 0}, o);
+}
+
+// The alcm_opconv arguments of a same-length conv of the operand planes `in`, with no output yet: the caller names
+// what it wants (out, res, out_scale, accumulate, out_act, out_plane, geglu_plane, ksplit_ws, act_epilogue).  The one
+// place that fills them.  A linear over R rows is B = 1, T = R.  The lo plane of a bf16x3 operand lies B * T * cpad
+// elements behind the hi plane; the single-rounding precisions never read it.  dense: the alcm_opconv_dense arguments,
+// which differ in the weight packing (cw.dw)
+static alcm_opconv_args plane_args(const ConvW& cw, const u16* in, int B, int T, int dil, int prec, bool dense = false) {
+  const Packed& pk = dense ? cw.dw : cw.w;
+  alcm_opconv_args g;
+  std::memset(&g, 0, sizeof(g));
+  g.a = in; g.a_lo_off = (int64_t)B * T * cw.w.cpad;
+  g.B = B; g.T = T; g.C = cw.w.cin; g.Cp = cw.w.cpad;
+  g.ksize = cw.w.taps; g.dil = dil; g.pad = (cw.w.taps - 1) * dil / 2;
+  g.w = pk.p; g.w_lo_off = pk.lo; g.kpad = pk.kpad; g.N = cw.w.rows;
+  g.bias = cw.b; g.out_scale = 1.f; g.prec = prec;
+  return g;
+}
+// alcm_opconv on planes the caller wrote `width` channels wide (the DiT, VAE and text forwards, whose planes are as
+// wide as the activation): refused unless that is the weight's packed Cin
+static int plane_conv(hipStream_t s, const alcm_opconv_args& g, int width) {
+  if (g.Cp != width || g.C != width) return set_error(ALCM_E_INVALID, "plane_conv: plane width != packed Cin");
+  return opconv(g, s);
+}
+
+// 1x1 conv at the base precision on channels-last rows: out[b,t,:] = W (x[b,t,:] (* scale[b] + shift[b])) + bias
+// (+ res[b,t,:]; out may alias res).  bf16x3 through split operand planes (alcm_sgemm.hip) where the layer qualifies,
+// the planes (B*T*C*4 bytes) going to `scratch`; conv() elsewhere
+static int conv_1x1(hipStream_t s, int prec, int B, int T, const float* x, int C, const float* scale,
+                    const float* shift, const ConvW& cw, const float* res, float* out, u16* scratch) {
+  const int N = cw.w.rows;
+  if (prec == PREC_SPLIT && scratch && cw.w.taps == 1 && cw.w.cpad == C && cw.w.cin == C &&
+      sgemm_planes_ok(C, N, cw.w.kpad)) {
+    const int64_t rows = (int64_t)B * T;
+    ALCM_TRY(split_planes(x, rows, C, T, scale, shift, scratch, s));
+    return sgemm_planes(scratch, rows * C, (int)rows, C, cw.w.p, cw.w.lo, cw.w.kpad, N, cw.b, res, N, out, N, 1.f, s);
+  }
+  ConvOpts o;
+  if (scale) o.pro = Pro{scale, shift, C, nullptr, nullptr, 0};
+  if (res) o.res = Res{res, (int64_t)T * N, N, 1};
+  return conv(s, prec, B, T, cl(x, T, C), cw, ocl(out, T, N), o);
+}
+
+// multi-head self-attention core on a fused qkv buffer (B, L, 3I), I = nh * dh, as two batched GEMMs over
+// z = b * nh + head with the scores S (B, nh, L, round_up(L, 8)) in HBM:
+// O[b, t, h*dh + d] = softmax_j(scale * q_t . k_j (+ bias[h][t][j])) v_j  (no mask)
+static int mha(hipStream_t s, int prec, int B, int L, int nh, int dh, const float* qkv, float scale,
+               const float* bias, int bld, float* S, float* O) {
+  const int I = nh * dh, Lp = round_up(L, 8);
+  alcm_gemm_args g;
+  std::memset(&g, 0, sizeof(g));
+  g.M = L; g.N = L; g.Kpad = round_up(dh, kBK); g.batch = B * nh; g.zdiv = nh;
+  g.a.kind = ALCM_OPND_ACT; g.a.ptr = qkv; g.a.sb = 0; g.a.st = 3 * I; g.a.sc = 1;
+  g.a.T_in = L; g.a.C_in = dh; g.a.Cpad = dh; g.a.ksize = 1; g.a.dil = 1; g.a.up = 1; g.a.rows_per_batch = L;
+  g.a.zs1 = (int64_t)L * 3 * I; g.a.zs2 = dh;
+  g.b = g.a;
+  g.b.ptr = qkv + I;
+  g.acc_scale = scale;
+  g.out_scale = 1.f;
+  g.out = S; g.o_sb = 0; g.o_st = Lp; g.o_sc = 1; g.o_zs1 = (int64_t)nh * L * Lp; g.o_zs2 = (int64_t)L * Lp;
+  g.out_rows_per_batch = L; g.out_step = 1;
+  g.prec = prec;
+  ALCM_TRY(gemm(g, s));
+  if (bias) ALCM_TRY(softmax_rows_bias(S, B * nh * L, L, Lp, L, nh, bias, bld, s));
+  else ALCM_TRY(softmax_rows(S, B * nh * L, L, Lp, s));
+  alcm_gemm_args p;
+  std::memset(&p, 0, sizeof(p));
+  p.M = L; p.N = dh; p.Kpad = round_up(Lp, kBK); p.batch = B * nh; p.zdiv = nh;
+  p.a.kind = ALCM_OPND_ACT; p.a.ptr = S; p.a.sb = 0; p.a.st = Lp; p.a.sc = 1; p.a.T_in = L; p.a.C_in = Lp;
+  p.a.Cpad = Lp; p.a.ksize = 1; p.a.dil = 1; p.a.up = 1; p.a.rows_per_batch = L;
+  p.a.zs1 = (int64_t)nh * L * Lp; p.a.zs2 = (int64_t)L * Lp;
+  p.b.kind = ALCM_OPND_ACT_T; p.b.ptr = qkv + 2 * I; p.b.st = 3 * I; p.b.sc = 1; p.b.T_in = L; p.b.rows = dh;
+  p.b.zs1 = (int64_t)L * 3 * I; p.b.zs2 = dh;
+  p.acc_scale = 1.f; p.out_scale = 1.f;
+  p.out = O; p.o_sb = 0; p.o_st = I; p.o_sc = 1; p.o_zs1 = (int64_t)L * I; p.o_zs2 = dh;
+  p.out_rows_per_batch = L; p.out_step = 1;
+  p.prec = prec;
+  return gemm(p, s);
+}
 
 struct Bump {
   char* base;
@@ -755,40 +836,11 @@ static DitWs plan_dit(const DitW& D, Bump& bp, int B, int T) {
 
 // attention core over a fused qkv buffer (B, L, 3H): O[b, t, h*dh + d] (new_attention.py:107-126)
 static int dit_attention(hipStream_t s, int split, const DitW& D, int B, int L, const float* qkv, float* S, float* O) {
-  const int H = D.hidden, nh = D.heads, dh = H / nh, Lp = round_up(L, 8);
+  const int H = D.hidden, nh = D.heads, dh = H / nh;
   // single-rounding policies: fused kernel, scores never leave the chip (alcm_attn.hip)
   if ((split == PREC_F16 || split == PREC_BF16) && dh <= 72 && dh % 4 == 0)
     return flash_attention(qkv, O, B, L, H, nh, split, s);
-  alcm_gemm_args g;
-  std::memset(&g, 0, sizeof(g));
-  // S = (Q K^T) * dh^-1/2, batched over z = b*nh + head
-  g.M = L; g.N = L; g.Kpad = round_up(dh, kBK); g.batch = B * nh; g.zdiv = nh;
-  g.a.kind = ALCM_OPND_ACT; g.a.ptr = qkv; g.a.sb = 0; g.a.st = 3 * H; g.a.sc = 1;
-  g.a.T_in = L; g.a.C_in = dh; g.a.Cpad = dh; g.a.ksize = 1; g.a.dil = 1; g.a.up = 1; g.a.rows_per_batch = L;
-  g.a.zs1 = (int64_t)L * 3 * H; g.a.zs2 = dh;
-  g.b = g.a;
-  g.b.ptr = qkv + H;
-  g.acc_scale = 1.0f / sqrtf((float)dh);
-  g.out_scale = 1.f;
-  g.out = S; g.o_sb = 0; g.o_st = Lp; g.o_sc = 1; g.o_zs1 = (int64_t)nh * L * Lp; g.o_zs2 = (int64_t)L * Lp;
-  g.out_rows_per_batch = L; g.out_step = 1;
-  g.prec = split;
-  ALCM_TRY(gemm(g, s));
-  ALCM_TRY(softmax_rows(S, B * nh * L, L, Lp, s));
-  // O = P V
-  alcm_gemm_args p;
-  std::memset(&p, 0, sizeof(p));
-  p.M = L; p.N = dh; p.Kpad = round_up(Lp, kBK); p.batch = B * nh; p.zdiv = nh;
-  p.a.kind = ALCM_OPND_ACT; p.a.ptr = S; p.a.sb = 0; p.a.st = Lp; p.a.sc = 1; p.a.T_in = L; p.a.C_in = Lp;
-  p.a.Cpad = Lp; p.a.ksize = 1; p.a.dil = 1; p.a.up = 1; p.a.rows_per_batch = L;
-  p.a.zs1 = (int64_t)nh * L * Lp; p.a.zs2 = (int64_t)L * Lp;
-  p.b.kind = ALCM_OPND_ACT_T; p.b.ptr = qkv + 2 * H; p.b.st = 3 * H; p.b.sc = 1; p.b.T_in = L; p.b.rows = dh;
-  p.b.zs1 = (int64_t)L * 3 * H; p.b.zs2 = dh;
-  p.acc_scale = 1.f; p.out_scale = 1.f;
-  p.out = O; p.o_sb = 0; p.o_st = H; p.o_sc = 1; p.o_zs1 = (int64_t)L * H; p.o_zs2 = dh;
-  p.out_rows_per_batch = L; p.out_step = 1;
-  p.prec = split;
-  return gemm(p, s);
+  return mha(s, split, B, L, nh, dh, qkv, 1.0f / sqrtf((float)dh), nullptr, 0, S, O);
 }
 
 static int dit_embed_context(alcm_model* m, const float* ctx, int B, float* cemb, void* ws, size_t wsb,
@@ -866,56 +918,36 @@ static int dit_forward(alcm_model* m, const float* x, const int64_t* t, const fl
     }
     ALCM_TRY(conv(s, split, B, T, xv, D.proj_in, Out{w.h, (int64_t)L * H, H, 1, 1, E}, o));
   }
-  const View hv = cl(w.h, L, H), uv = cl(w.u, L, H), ov = cl(w.o, L, H);
-  const Out ho = ocl(w.h, L, H), uo = ocl(w.u, L, H);
-  const Res ur{w.u, (int64_t)L * H, H, 1}, hr{w.h, (int64_t)L * H, H, 1};
+  const View uv = cl(w.u, L, H), ov = cl(w.o, L, H);
+  const Out uo = ocl(w.u, L, H);
+  const Res ur{w.u, (int64_t)L * H, H, 1};
+  // the TemporalTransformer 1x1 convs' split planes go to w.g, which is free outside the feed-forward
+  u16* spl = reinterpret_cast<u16*>(w.g);
   for (const DitBlock& blk : D.blocks) {
     // TemporalTransformer (concatDiT.py:159-171): GN32 -> 1x1 -> block -> 1x1 -> +x
+    // (on split planes the GroupNorm affine is applied once, while the planes are written)
     ALCM_TRY(group_norm_affine(w.h, B, L, H, (int64_t)L * H, H, 32, 1e-6f, blk.gn.g, blk.gn.b, w.gsc, w.gsh, s));
-    // bf16x3 1x1 convs on split planes (alcm_sgemm.hip): the GroupNorm affine applied once while the planes are
-    // written; w.g is free outside the feed-forward
-    const bool sg = split == PREC_SPLIT && sgemm_planes_ok(H, H, blk.proj_in.w.kpad) &&
-                    sgemm_planes_ok(H, H, blk.proj_out.w.kpad) && blk.proj_in.w.cpad == H && blk.proj_out.w.cpad == H;
-    u16* spl = reinterpret_cast<u16*>(w.g);
-    if (sg) {
-      ALCM_TRY(split_planes(w.h, (int64_t)B * L, H, L, w.gsc, w.gsh, spl, s));
-      ALCM_TRY(sgemm_planes(spl, (int64_t)B * L * H, B * L, H, blk.proj_in.w.p, blk.proj_in.w.lo, blk.proj_in.w.kpad,
-                            H, blk.proj_in.b, nullptr, 0, w.u, H, 1.f, s));
-    } else {
-      ConvOpts o;
-      o.pro = Pro{w.gsc, w.gsh, H, nullptr, nullptr, 0};
-      ALCM_TRY(conv(s, split, B, L, hv, blk.proj_in, uo, o));
-    }
+    ALCM_TRY(conv_1x1(s, split, B, L, w.h, H, w.gsc, w.gsh, blk.proj_in, nullptr, w.u, spl));
     // BasicTransformerBlock (concatDiT.py:120-125)
     const bool planes = (pff == PREC_F16 || pff == PREC_BF16) && (H / D.heads) <= 72 && (H / D.heads) % 4 == 0;
     for (int a = 0; a < 2 && planes; ++a) {
       // attention sub-block on operand planes: LayerNorm -> plane, fused q/k/v projection (k = 1 on the
       // wide-layer kernel), flash attention writing the to_out operand plane, to_out + bias + residual in place
       const NormW& ln = a ? blk.ln2 : blk.ln1;
-      const ConvW& wq = a ? blk.qkv2 : blk.qkv1;
-      const ConvW& wo = a ? blk.out2 : blk.out1;
       u16* pln = reinterpret_cast<u16*>(w.g);  // w.g is free until the feed-forward below
       u16* opl = pln + (size_t)B * L * H;
       ALCM_TRY(layer_norm_plane(w.u, B * L, H, H, 1e-5f, ln.g, ln.b, pln, pff, s));
-      alcm_opconv_args g;
-      std::memset(&g, 0, sizeof(g));
-      g.a = pln; g.B = B; g.T = L; g.C = H; g.Cp = wq.w.cpad; g.ksize = 1; g.dil = 1; g.pad = 0;
-      g.w = wq.w.p; g.w_lo_off = wq.w.lo; g.kpad = wq.w.kpad; g.N = wq.w.rows;
-      g.bias = wq.b; g.out = w.qkv; g.out_scale = 1.f; g.prec = pff;
+      alcm_opconv_args q = plane_args(a ? blk.qkv2 : blk.qkv1, pln, B, L, 1, pff);
       // q / k / v as an operand plane (attention rounds them to pff anyway): half the bytes written and staged
-      const bool qp = wq.w.rows % 4 == 0 && L <= 512;
-      if (qp) {
-        g.out = nullptr;
-        g.out_plane = w.qkv;
-      }
-      ALCM_TRY(opconv(g, s));
+      const bool qp = q.N % 4 == 0 && L <= 512;
+      if (qp) q.out_plane = w.qkv;
+      else q.out = w.qkv;
+      ALCM_TRY(plane_conv(s, q, H));
       if (qp) ALCM_TRY(flash_attention(nullptr, nullptr, B, L, H, D.heads, pff, s, opl, nullptr, 0, 0.f, w.qkv));
       else ALCM_TRY(flash_attention(w.qkv, nullptr, B, L, H, D.heads, pff, s, opl));
-      std::memset(&g, 0, sizeof(g));
-      g.a = opl; g.B = B; g.T = L; g.C = H; g.Cp = wo.w.cpad; g.ksize = 1; g.dil = 1; g.pad = 0;
-      g.w = wo.w.p; g.w_lo_off = wo.w.lo; g.kpad = wo.w.kpad; g.N = wo.w.rows;
-      g.bias = wo.b; g.res = w.u; g.out = w.u; g.out_scale = 1.f; g.prec = pff;
-      ALCM_TRY(opconv(g, s));
+      alcm_opconv_args o = plane_args(a ? blk.out2 : blk.out1, opl, B, L, 1, pff);
+      o.res = w.u; o.out = w.u;
+      ALCM_TRY(plane_conv(s, o, H));
     }
     for (int a = 0; a < 2 && !planes; ++a) {
       const NormW& ln = a ? blk.ln2 : blk.ln1;
@@ -936,21 +968,14 @@ static int dit_forward(alcm_model* m, const float* x, const int64_t* t, const fl
       u16* p2 = reinterpret_cast<u16*>(w.g);
       u16* p1 = p2 + (size_t)B * L * inner;
       ALCM_TRY(layer_norm_plane(w.u, B * L, H, H, 1e-5f, blk.ln3.g, blk.ln3.b, p1, pff, s));
-      alcm_opconv_args g;
-      std::memset(&g, 0, sizeof(g));
-      g.a = p1; g.a_lo_off = 0; g.B = B; g.T = L; g.C = H; g.Cp = blk.ff0.w.cpad;
-      g.ksize = D.ff_k; g.dil = 1; g.pad = D.ff_k / 2;
-      g.w = blk.ff0.w.p; g.w_lo_off = blk.ff0.w.lo; g.kpad = blk.ff0.w.kpad; g.N = blk.ff0.w.rows;
-      g.bias = blk.ff0.b; g.out_scale = 1.f; g.prec = pff; g.geglu_plane = p2;
-      ALCM_TRY(opconv(g, s));
-      std::memset(&g, 0, sizeof(g));
-      g.a = p2; g.a_lo_off = 0; g.B = B; g.T = L; g.C = inner; g.Cp = blk.ff2.w.cpad;
-      g.ksize = D.ff_k; g.dil = 1; g.pad = D.ff_k / 2;
-      g.w = blk.ff2.w.p; g.w_lo_off = blk.ff2.w.lo; g.kpad = blk.ff2.w.kpad; g.N = blk.ff2.w.rows;
-      g.bias = blk.ff2.b; g.res = w.u; g.out = w.u; g.out_scale = 1.f; g.prec = pff;
+      alcm_opconv_args up = plane_args(blk.ff0, p1, B, L, 1, pff);
+      up.geglu_plane = p2;
+      ALCM_TRY(plane_conv(s, up, H));
+      alcm_opconv_args dn = plane_args(blk.ff2, p2, B, L, 1, pff);
+      dn.res = w.u; dn.out = w.u;
       // 192 tiles of 256 x 192 at B = 32: K parts fill the chip (alcm_wconv.hip wconv3_parts)
-      g.ksplit_ws = w.kp; g.ksplit_ws_floats = w.kp_floats;
-      ALCM_TRY(opconv(g, s));
+      dn.ksplit_ws = w.kp; dn.ksplit_ws_floats = w.kp_floats;
+      ALCM_TRY(plane_conv(s, dn, inner));
     } else {
       ALCM_TRY(row_stats(w.u, B * L, H, H, 1e-5f, w.mean, w.rstd, s));
       ConvOpts o;
@@ -963,15 +988,7 @@ static int dit_forward(alcm_model* m, const float* x, const int64_t* t, const fl
       o2.res = ur;
       ALCM_TRY(conv(s, pff, B, L, cl(w.g, L, 4 * H), blk.ff2, uo, o2));
     }
-    if (sg) {
-      ALCM_TRY(split_planes(w.u, (int64_t)B * L, H, 0, nullptr, nullptr, spl, s));
-      ALCM_TRY(sgemm_planes(spl, (int64_t)B * L * H, B * L, H, blk.proj_out.w.p, blk.proj_out.w.lo,
-                            blk.proj_out.w.kpad, H, blk.proj_out.b, w.h, H, w.h, H, 1.f, s));
-    } else {
-      ConvOpts o;
-      o.res = hr;
-      ALCM_TRY(conv(s, split, B, L, uv, blk.proj_out, ho, o));
-    }
+    ALCM_TRY(conv_1x1(s, split, B, L, w.u, H, nullptr, nullptr, blk.proj_out, w.h, w.h, spl));
   }
   // final layer on the latent tokens: GN16(eps 1e-5) -> 1x1 -> eps (NCT)  (concatDiT.py:77-89, 302-303)
   const float* hl = w.h + (int64_t)E * H;
@@ -991,18 +1008,6 @@ struct VaeWs {
 // the VAE's k3 convs read operand planes on the wide-layer kernel
 static bool vae_planes(int pk3) {
   return pk3 == PREC_F16 || pk3 == PREC_BF16;
-}
-// conv k3 (same length) on an operand plane: out = conv(plane) + bias (+ res); out may alias res
-static int plane_conv3(hipStream_t s, int prec, int B, int T, int C, const u16* plane, const ConvW& cw,
-                       const float* res, float* out) {
-  if (cw.w.cpad != C || cw.w.cin != C) return set_error(ALCM_E_INVALID, "plane_conv3: plane width != packed Cin");
-  alcm_opconv_args g;
-  std::memset(&g, 0, sizeof(g));
-  g.a = plane; g.a_lo_off = 0; g.B = B; g.T = T; g.C = C; g.Cp = cw.w.cpad;
-  g.ksize = cw.w.taps; g.dil = 1; g.pad = cw.w.taps / 2;
-  g.w = cw.w.p; g.w_lo_off = cw.w.lo; g.kpad = cw.w.kpad; g.N = cw.w.rows;
-  g.bias = cw.b; g.res = res; g.out = out; g.out_scale = 1.f; g.prec = prec;
-  return opconv(g, s);
 }
 static VaeWs plan_vae(const VaeW& V, Bump& bp, int B, int T) {
   // largest channels x time of any activation on the decode path
@@ -1034,68 +1039,51 @@ static VaeWs plan_vae(const VaeW& V, Bump& bp, int B, int T) {
   return w;
 }
 
-// bf16x3 1x1 conv through split operand planes (alcm_sgemm.hip) when the layer qualifies: out[b,t,:] =
-// W (x[b,t,:] (* scale[b] + shift[b])) + bias (+ res), rows of ld C in / ldo out; `scratch` holds B*T*C*4 bytes of
-// planes.  Returns 1 when it ran, 0 when the caller should use conv(), or an error code (negative never)
-static int split_1x1(hipStream_t s, int prec, int B, int T, const float* x, int C, const float* scale,
-                     const float* shift, const ConvW& cw, const float* res, float* out, int ldo, u16* scratch,
-                     int* rc) {
-  *rc = 0;
-  if (prec != PREC_SPLIT || !scratch || cw.w.taps != 1 || cw.w.cpad != C || cw.w.cin != C ||
-      !sgemm_planes_ok(C, cw.w.rows, cw.w.kpad))
-    return 0;
-  const int64_t rows = (int64_t)B * T;
-  if ((*rc = split_planes(x, rows, C, T, scale, shift, scratch, s))) return 1;
-  *rc = sgemm_planes(scratch, rows * C, (int)rows, C, cw.w.p, cw.w.lo, cw.w.kpad, cw.w.rows, cw.b, res, ldo, out,
-                     ldo, 1.f, s);
-  return 1;
+// half of a ResnetBlock1D: out = conv_k(swish(x * gsc + gsh)) + bias (+ res; out may alias it), x (B, T, C) with its
+// GroupNorm affine in w.gsc / w.gsh.  F16 / BF16: affine + swish -> plane, the conv on the wide-layer kernel;
+// else both in conv()'s prologue
+static int vae_half(hipStream_t s, int pk3, int B, int T, int C, const float* x, const ConvW& cw, const float* res,
+                    float* out, VaeWs& w) {
+  if (vae_planes(pk3)) {
+    ALCM_TRY(affine_plane(x, B, T, C, 1, w.gsc, w.gsh, 1, w.pl, pk3, s));
+    alcm_opconv_args g = plane_args(cw, w.pl, B, T, 1, pk3);
+    g.res = res; g.out = out;
+    return plane_conv(s, g, C);
+  }
+  const int N = cw.w.rows;
+  ConvOpts o;
+  o.pad = cw.w.taps / 2;
+  o.pro = Pro{w.gsc, w.gsh, C, nullptr, nullptr, ACT_SILU};
+  if (res) o.res = Res{res, (int64_t)T * N, N, 1};
+  return conv(s, pk3, B, T, cl(x, T, C), cw, ocl(out, T, N), o);
 }
 
 // ResnetBlock1D (autoencoder1d.py:212-235): out = x' + conv2(swish(GN(conv1(swish(GN(x))))))
 static int vae_res(hipStream_t s, int split, int pk3, int B, int T, const ResW& r, const float* x, float* tmp,
                    float* sc, float* out, VaeWs& w) {
   ALCM_TRY(group_norm_affine(x, B, T, r.cin, (int64_t)T * r.cin, r.cin, 32, 1e-6f, r.n1.g, r.n1.b, w.gsc, w.gsh, s));
-  if (vae_planes(pk3)) {
-    // GN affine + swish -> plane, conv1 on the wide-layer kernel; again for conv2 with bias + residual
-    ALCM_TRY(affine_plane(x, B, T, r.cin, 1, w.gsc, w.gsh, 1, w.pl, pk3, s));
-    ALCM_TRY(plane_conv3(s, pk3, B, T, r.cin, w.pl, r.c1, nullptr, tmp));
-    ALCM_TRY(group_norm_affine(tmp, B, T, r.cout, (int64_t)T * r.cout, r.cout, 32, 1e-6f, r.n2.g, r.n2.b, w.gsc,
-                               w.gsh, s));
-    const float* resid = x;
-    if (r.has_nin) {
-      int rc;  // `out` is free until conv2 writes it: the split planes of x go there
-      if (!split_1x1(s, split, B, T, x, r.cin, nullptr, nullptr, r.nin, nullptr, sc, r.cout,
-                     reinterpret_cast<u16*>(out), &rc))
-        ALCM_TRY(conv(s, split, B, T, cl(x, T, r.cin), r.nin, ocl(sc, T, r.cout), ConvOpts{}));
-      ALCM_TRY(rc);
-      resid = sc;
-    }
-    ALCM_TRY(affine_plane(tmp, B, T, r.cout, 1, w.gsc, w.gsh, 1, w.pl, pk3, s));
-    return plane_conv3(s, pk3, B, T, r.cout, w.pl, r.c2, resid, out);
-  }
-  ConvOpts o1;
-  o1.pad = r.c1.w.taps / 2;
-  o1.pro = Pro{w.gsc, w.gsh, r.cin, nullptr, nullptr, ACT_SILU};
-  ALCM_TRY(conv(s, pk3, B, T, cl(x, T, r.cin), r.c1, ocl(tmp, T, r.cout), o1));
+  ALCM_TRY(vae_half(s, pk3, B, T, r.cin, x, r.c1, nullptr, tmp, w));
   ALCM_TRY(group_norm_affine(tmp, B, T, r.cout, (int64_t)T * r.cout, r.cout, 32, 1e-6f, r.n2.g, r.n2.b, w.gsc, w.gsh, s));
   const float* resid = x;
   if (r.has_nin) {
-    int rc;
-    if (!split_1x1(s, split, B, T, x, r.cin, nullptr, nullptr, r.nin, nullptr, sc, r.cout, reinterpret_cast<u16*>(out),
-                   &rc))
-      ALCM_TRY(conv(s, split, B, T, cl(x, T, r.cin), r.nin, ocl(sc, T, r.cout), ConvOpts{}));
-    ALCM_TRY(rc);
+    // `out` is free until conv2 writes it: the split planes of x go there
+    ALCM_TRY(conv_1x1(s, split, B, T, x, r.cin, nullptr, nullptr, r.nin, nullptr, sc, reinterpret_cast<u16*>(out)));
     resid = sc;
   }
-  ConvOpts o2;
-  o2.pad = r.c2.w.taps / 2;
-  o2.pro = Pro{w.gsc, w.gsh, r.cout, nullptr, nullptr, ACT_SILU};
-  o2.res = Res{resid, (int64_t)T * r.cout, r.cout, 1};
-  return conv(s, pk3, B, T, cl(tmp, T, r.cout), r.c2, ocl(out, T, r.cout), o2);
+  return vae_half(s, pk3, B, T, r.cout, tmp, r.c2, resid, out, w);
 }
 
+// AttnBlock1D (autoencoder1d.py:259-278): single head over T, logit scale C^-1/2; h += proj_out(attn(GN(h)));
+// o_scratch (B, T, C) holds the attention output and must not alias h
 static int vae_attn(hipStream_t s, int split, int B, int T, int C, const NormW& nw, const ConvW& qkvw, const ConvW& ow,
-                    float* h, float* o_scratch, VaeWs& w);
+                    float* h, float* o_scratch, VaeWs& w) {
+  if (o_scratch == h) return set_error(ALCM_E_INVALID, "vae_attn: scratch aliases the activation");
+  u16* spl = reinterpret_cast<u16*>(w.b);  // w.b (the ResnetBlock1D scratch) is free here: the split planes go there
+  ALCM_TRY(group_norm_affine(h, B, T, C, (int64_t)T * C, C, 32, 1e-6f, nw.g, nw.b, w.gsc, w.gsh, s));
+  ALCM_TRY(conv_1x1(s, split, B, T, h, C, w.gsc, w.gsh, qkvw, nullptr, w.qkv, spl));
+  ALCM_TRY(mha(s, split, B, T, 1, C, w.qkv, 1.0f / sqrtf((float)C), nullptr, 0, w.S, o_scratch));
+  return conv_1x1(s, split, B, T, o_scratch, C, nullptr, nullptr, ow, h, h, spl);
+}
 
 static int vae_decode(alcm_model* m, const float* z, float inv_scale, float* mel, int B, int T, void* ws, size_t wsb,
                       hipStream_t s) {
@@ -1146,7 +1134,9 @@ static int vae_decode(alcm_model* m, const float* z, float inv_scale, float* mel
     if (V.up[lvl].w.p && vae_planes(pk3)) {
       // Upsample1D: nearest x2 written as a duplicated-row plane, conv k3 on the wide-layer kernel
       ALCM_TRY(affine_plane(h, B, Tc, C, 2, nullptr, nullptr, 0, w.pl, pk3, s));
-      ALCM_TRY(plane_conv3(s, pk3, B, 2 * Tc, C, w.pl, V.up[lvl], nullptr, spare));
+      alcm_opconv_args g = plane_args(V.up[lvl], w.pl, B, 2 * Tc, 1, pk3);
+      g.out = spare;
+      ALCM_TRY(plane_conv(s, g, C));
       std::swap(h, spare);
       Tc *= 2;
     } else if (V.up[lvl].w.p) {
@@ -1164,55 +1154,6 @@ static int vae_decode(alcm_model* m, const float* z, float inv_scale, float* mel
   o.pad = V.ksz / 2;
   o.pro = Pro{w.gsc, w.gsh, C, nullptr, nullptr, ACT_SILU};
   return conv(s, split, B, Tc, cl(h, Tc, C), V.conv_out, Out{mel, (int64_t)V.out_ch * Tc, 1, Tc, 1, 0}, o);
-}
-
-// AttnBlock1D (autoencoder1d.py:259-278): single head over T, logit scale C^-1/2; h += proj_out(attn(GN(h)));
-// o_scratch (B, T, C) holds the attention output and must not alias h
-static int vae_attn(hipStream_t s, int split, int B, int T, int C, const NormW& nw, const ConvW& qkvw, const ConvW& ow,
-                    float* h, float* o_scratch, VaeWs& w) {
-  if (o_scratch == h) return set_error(ALCM_E_INVALID, "vae_attn: scratch aliases the activation");
-  {
-    ALCM_TRY(group_norm_affine(h, B, T, C, (int64_t)T * C, C, 32, 1e-6f, nw.g, nw.b, w.gsc, w.gsh, s));
-    int rc;  // w.b (the ResnetBlock1D scratch) is free here: the split planes go there
-    if (!split_1x1(s, split, B, T, h, C, w.gsc, w.gsh, qkvw, nullptr, w.qkv, 3 * C, reinterpret_cast<u16*>(w.b), &rc)) {
-      ConvOpts o;
-      o.pro = Pro{w.gsc, w.gsh, C, nullptr, nullptr, 0};
-      ALCM_TRY(conv(s, split, B, T, cl(h, T, C), qkvw, ocl(w.qkv, T, 3 * C), o));
-    }
-    ALCM_TRY(rc);
-    const int Tp = round_up(T, 8);
-    alcm_gemm_args g;
-    std::memset(&g, 0, sizeof(g));
-    g.M = T; g.N = T; g.Kpad = round_up(C, kBK); g.batch = B; g.zdiv = 1;
-    g.a.kind = ALCM_OPND_ACT; g.a.ptr = w.qkv; g.a.st = 3 * C; g.a.sc = 1; g.a.T_in = T; g.a.C_in = C; g.a.Cpad = C;
-    g.a.ksize = 1; g.a.dil = 1; g.a.up = 1; g.a.rows_per_batch = T; g.a.zs1 = (int64_t)T * 3 * C;
-    g.b = g.a;
-    g.b.ptr = w.qkv + C;
-    g.acc_scale = 1.0f / sqrtf((float)C);
-    g.out_scale = 1.f;
-    g.out = w.S; g.o_st = Tp; g.o_sc = 1; g.o_zs1 = (int64_t)T * Tp; g.out_rows_per_batch = T; g.out_step = 1;
-    g.prec = split;
-    ALCM_TRY(gemm(g, s));
-    ALCM_TRY(softmax_rows(w.S, B * T, T, Tp, s));
-    alcm_gemm_args p;
-    std::memset(&p, 0, sizeof(p));
-    p.M = T; p.N = C; p.Kpad = round_up(Tp, kBK); p.batch = B; p.zdiv = 1;
-    p.a.kind = ALCM_OPND_ACT; p.a.ptr = w.S; p.a.st = Tp; p.a.sc = 1; p.a.T_in = T; p.a.C_in = Tp; p.a.Cpad = Tp;
-    p.a.ksize = 1; p.a.dil = 1; p.a.up = 1; p.a.rows_per_batch = T; p.a.zs1 = (int64_t)T * Tp;
-    p.b.kind = ALCM_OPND_ACT_T; p.b.ptr = w.qkv + 2 * C; p.b.st = 3 * C; p.b.sc = 1; p.b.T_in = T; p.b.rows = C;
-    p.b.zs1 = (int64_t)T * 3 * C;
-    p.acc_scale = 1.f; p.out_scale = 1.f;
-    p.out = o_scratch; p.o_st = C; p.o_sc = 1; p.o_zs1 = (int64_t)T * C; p.out_rows_per_batch = T; p.out_step = 1;
-    p.prec = split;
-    ALCM_TRY(gemm(p, s));
-    if (!split_1x1(s, split, B, T, o_scratch, C, nullptr, nullptr, ow, h, h, C, reinterpret_cast<u16*>(w.b), &rc)) {
-      ConvOpts oo;
-      oo.res = Res{h, (int64_t)T * C, C, 1};
-      ALCM_TRY(conv(s, split, B, T, cl(o_scratch, T, C), ow, ocl(h, T, C), oo));
-    }
-    ALCM_TRY(rc);
-  }
-  return 0;
 }
 
 // Encoder1D + quant_conv (autoencoder1d.py:319-413, AutoencoderKL.encode :54-58): mel (B, in_ch, M) NCT ->
@@ -1376,21 +1317,7 @@ static const alcm_model::AuxSet* voc_streams(alcm_model* m, hipStream_t s) {
   return &(m->aux[s] = a);
 }
 
-// the alcm_opconv arguments of a same-length conv of the operand planes `in`, with no output yet: the caller names
-// what it wants (out, res, out_scale, accumulate, out_act, out_plane, act_epilogue).  dense: the alcm_opconv_dense
-// arguments, which differ in the weight packing (cw.dw)
-static alcm_opconv_args plane_args(const ConvW& cw, const u16* in, int B, int T, int dil, int prec, bool dense = false) {
-  const Packed& pk = dense ? cw.dw : cw.w;
-  alcm_opconv_args g;
-  std::memset(&g, 0, sizeof(g));
-  g.a = in; g.a_lo_off = (int64_t)B * T * cw.w.cpad;
-  g.B = B; g.T = T; g.C = cw.w.cin; g.Cp = cw.w.cpad;
-  g.ksize = cw.w.taps; g.dil = dil; g.pad = (cw.w.taps - 1) * dil / 2;
-  g.w = pk.p; g.w_lo_off = pk.lo; g.kpad = pk.kpad; g.N = cw.w.rows;
-  g.bias = cw.b; g.out_scale = 1.f; g.prec = prec;
-  return g;
-}
-// the epilogue also writes Activation1d(conv + bias (+ res)) into the operand planes `planes` (alcm_actepi.h)
+// the epilogue of a plane conv (plane_args) also writes Activation1d(conv + bias (+ res)) into the operand planes `planes` (alcm_actepi.h)
 static void act_epilogue(alcm_opconv_args& g, const ActW& act, u16* planes) {
   g.act_plane = planes;
   g.act_plane_lo_off = (int64_t)g.B * g.T * round_up(g.N, 32);
@@ -1754,63 +1681,6 @@ static TextWs plan_text(const TextW& X, Bump& bp, int B, int L) {
   return w;
 }
 
-// multi-head self-attention core on a fused qkv buffer (B, L, 3I), I = nh * dh:
-// O[b, t, h*dh + d] = softmax_j(scale * q_t . k_j (+ bias[h][t][j])) v_j  (no mask)
-static int mha(hipStream_t s, int prec, int B, int L, int nh, int dh, const float* qkv, float scale,
-               const float* bias, int bld, float* S, float* O) {
-  const int I = nh * dh, Lp = round_up(L, 8);
-  alcm_gemm_args g;
-  std::memset(&g, 0, sizeof(g));
-  g.M = L; g.N = L; g.Kpad = round_up(dh, kBK); g.batch = B * nh; g.zdiv = nh;
-  g.a.kind = ALCM_OPND_ACT; g.a.ptr = qkv; g.a.sb = 0; g.a.st = 3 * I; g.a.sc = 1;
-  g.a.T_in = L; g.a.C_in = dh; g.a.Cpad = dh; g.a.ksize = 1; g.a.dil = 1; g.a.up = 1; g.a.rows_per_batch = L;
-  g.a.zs1 = (int64_t)L * 3 * I; g.a.zs2 = dh;
-  g.b = g.a;
-  g.b.ptr = qkv + I;
-  g.acc_scale = scale;
-  g.out_scale = 1.f;
-  g.out = S; g.o_sb = 0; g.o_st = Lp; g.o_sc = 1; g.o_zs1 = (int64_t)nh * L * Lp; g.o_zs2 = (int64_t)L * Lp;
-  g.out_rows_per_batch = L; g.out_step = 1;
-  g.prec = prec;
-  ALCM_TRY(gemm(g, s));
-  if (bias) ALCM_TRY(softmax_rows_bias(S, B * nh * L, L, Lp, L, nh, bias, bld, s));
-  else ALCM_TRY(softmax_rows(S, B * nh * L, L, Lp, s));
-  alcm_gemm_args p;
-  std::memset(&p, 0, sizeof(p));
-  p.M = L; p.N = dh; p.Kpad = round_up(Lp, kBK); p.batch = B * nh; p.zdiv = nh;
-  p.a.kind = ALCM_OPND_ACT; p.a.ptr = S; p.a.sb = 0; p.a.st = Lp; p.a.sc = 1; p.a.T_in = L; p.a.C_in = Lp;
-  p.a.Cpad = Lp; p.a.ksize = 1; p.a.dil = 1; p.a.up = 1; p.a.rows_per_batch = L;
-  p.a.zs1 = (int64_t)nh * L * Lp; p.a.zs2 = (int64_t)L * Lp;
-  p.b.kind = ALCM_OPND_ACT_T; p.b.ptr = qkv + 2 * I; p.b.st = 3 * I; p.b.sc = 1; p.b.T_in = L; p.b.rows = dh;
-  p.b.zs1 = (int64_t)L * 3 * I; p.b.zs2 = dh;
-  p.acc_scale = 1.f; p.out_scale = 1.f;
-  p.out = O; p.o_sb = 0; p.o_st = I; p.o_sc = 1; p.o_zs1 = (int64_t)L * I; p.o_zs2 = dh;
-  p.out_rows_per_batch = L; p.out_step = 1;
-  p.prec = prec;
-  return gemm(p, s);
-}
-
-// y (R, N) = x (R, C) W^T (+ bias) with the conv helper (k = 1): rows are one "batch" of R tokens
-static int lin(hipStream_t s, int prec, int R, const float* x, int C, const ConvW& w, float* y, const ConvOpts& o) {
-  return conv(s, prec, 1, R, View{x, 0, C, 1, R, C}, w, Out{y, 0, w.w.rows, 1, 1, 0}, o);
-}
-
-// the same linear on an F16 / BF16 operand plane (alcm_opconv, k = 1: the wide-layer / plane conv kernels): y (R, N) =
-// plane (R, C) W^T (+ bias) (+ res) with out_act; the plane is written by the caller
-static int plane_lin(hipStream_t s, int prec, int R, const u16* plane, int C, const ConvW& w, float* y,
-                     const float* res, int act, int64_t plane_lo = 0, void* out_plane = nullptr,
-                     float* kws = nullptr, int64_t kws_floats = 0) {
-  if (w.w.cpad != C || w.w.taps != 1) return set_error(ALCM_E_INVALID, "plane_lin: plane width != packed Cin");
-  alcm_opconv_args g;
-  std::memset(&g, 0, sizeof(g));
-  g.a = plane; g.a_lo_off = plane_lo; g.B = 1; g.T = R; g.C = C; g.Cp = C; g.ksize = 1; g.dil = 1; g.pad = 0;
-  g.w = w.w.p; g.w_lo_off = w.w.lo; g.kpad = w.w.kpad; g.N = w.w.rows;
-  g.bias = w.b; g.res = res; g.out = y; g.out_act = act; g.out_scale = 1.f; g.prec = prec;
-  g.out_plane = out_plane;  // (then y == nullptr: the result as a PREC plane)
-  g.ksplit_ws = kws; g.ksplit_ws_floats = kws_floats;  // K parts where the grid under-fills the chip (alcm_wconv.hip)
-  return opconv(g, s);
-}
-
 static int text_encode(alcm_model* m, const int64_t* clap_ids, const int64_t* t5_ids, float* out, int B, int L,
                        void* ws, size_t wsb, hipStream_t s) {
   const TextW& X = m->text;
@@ -1835,20 +1705,31 @@ static int text_encode(alcm_model* m, const int64_t* clap_ids, const int64_t* t5
   for (const BertLayerW& Ly : X.bl) {
     if (planes) {
       ALCM_TRY(to_planes(w.x, w.pl, R, H, H, pl, s));
+      alcm_opconv_args qkv = plane_args(Ly.qkv, w.pl, 1, R, 1, pl);
       if (tflash) {  // q / k / v as a plane, fused attention writing the out-projection's plane (resident K / V)
-        ALCM_TRY(plane_lin(s, pl, R, w.pl, H, Ly.qkv, nullptr, nullptr, 0, 0, w.qkv));
+        qkv.out_plane = w.qkv;
+        ALCM_TRY(plane_conv(s, qkv, H));
         ALCM_TRY(flash_attention(nullptr, nullptr, B, L, H, X.b_heads, pl, s, w.pl, nullptr, 0, 0.f, w.qkv));
       } else {
-        ALCM_TRY(plane_lin(s, pl, R, w.pl, H, Ly.qkv, w.qkv, nullptr, 0));
+        qkv.out = w.qkv;
+        ALCM_TRY(plane_conv(s, qkv, H));
         ALCM_TRY(mha(s, pl, B, L, X.b_heads, bdh, w.qkv, 1.0f / sqrtf((float)bdh), nullptr, 0, w.S, w.O));
         ALCM_TRY(to_planes(w.O, w.pl, R, H, H, pl, s));
       }
-      ALCM_TRY(plane_lin(s, pl, R, w.pl, H, Ly.ao, w.tmp, w.x, 0, 0, nullptr, w.kp, w.kp_floats));
+      alcm_opconv_args ao = plane_args(Ly.ao, w.pl, 1, R, 1, pl);
+      ao.res = w.x; ao.out = w.tmp;
+      ao.ksplit_ws = w.kp; ao.ksplit_ws_floats = w.kp_floats;  // K parts: the grid under-fills the chip (alcm_wconv.hip)
+      ALCM_TRY(plane_conv(s, ao, H));
       ALCM_TRY(layer_norm_plane(w.tmp, R, H, H, X.b_eps, Ly.ln1.g, Ly.ln1.b, w.pl, pl, s));
       ALCM_TRY(layer_norm(w.tmp, R, H, H, X.b_eps, Ly.ln1.g, Ly.ln1.b, nullptr, 0, w.x, H, s));
-      ALCM_TRY(plane_lin(s, pl, R, w.pl, H, Ly.inter, w.inter, nullptr, ACT_GELU_ERF));
+      alcm_opconv_args up = plane_args(Ly.inter, w.pl, 1, R, 1, pl);
+      up.out = w.inter; up.out_act = ACT_GELU_ERF;
+      ALCM_TRY(plane_conv(s, up, H));
       ALCM_TRY(to_planes(w.inter, w.pl, R, X.b_inter, X.b_inter, pl, s));
-      ALCM_TRY(plane_lin(s, pl, R, w.pl, X.b_inter, Ly.out, w.tmp, w.x, 0, 0, nullptr, w.kp, w.kp_floats));
+      alcm_opconv_args dn = plane_args(Ly.out, w.pl, 1, R, 1, pl);
+      dn.res = w.x; dn.out = w.tmp;
+      dn.ksplit_ws = w.kp; dn.ksplit_ws_floats = w.kp_floats;
+      ALCM_TRY(plane_conv(s, dn, X.b_inter));
       ALCM_TRY(layer_norm(w.tmp, R, H, H, X.b_eps, Ly.ln2.g, Ly.ln2.b, nullptr, 0, w.x, H, s));
       continue;
     }
@@ -1884,23 +1765,32 @@ static int text_encode(alcm_model* m, const int64_t* clap_ids, const int64_t* t5
   for (const T5BlockW& Bk : X.tb) {
     if (planes) {
       ALCM_TRY(rms_norm_plane(w.x, R, D, X.t_eps, Bk.ln0, w.pl, pl, s));
+      alcm_opconv_args qkv = plane_args(Bk.qkv, w.pl, 1, R, 1, pl);
       if (tflash) {  // unscaled scores + the relative-position bias inside the fused kernel
-        ALCM_TRY(plane_lin(s, pl, R, w.pl, D, Bk.qkv, nullptr, nullptr, 0, 0, w.qkv));
+        qkv.out_plane = w.qkv;
+        ALCM_TRY(plane_conv(s, qkv, D));
         ALCM_TRY(flash_attention(nullptr, nullptr, B, L, TI, X.t_heads, pl, s, w.pl, X.t_bias, X.max_len, 1.0f,
                                  w.qkv));
       } else {
-        ALCM_TRY(plane_lin(s, pl, R, w.pl, D, Bk.qkv, w.qkv, nullptr, 0));
+        qkv.out = w.qkv;
+        ALCM_TRY(plane_conv(s, qkv, D));
         ALCM_TRY(mha(s, pl, B, L, X.t_heads, X.t_dkv, w.qkv, 1.0f, X.t_bias, X.max_len, w.S, w.O));
         ALCM_TRY(to_planes(w.O, w.pl, R, TI, TI, pl, s));
       }
-      ALCM_TRY(plane_lin(s, pl, R, w.pl, TI, Bk.o, w.x, w.x, 0, 0, nullptr, w.kp, w.kp_floats));
+      alcm_opconv_args o = plane_args(Bk.o, w.pl, 1, R, 1, pl);
+      o.res = w.x; o.out = w.x;
+      o.ksplit_ws = w.kp; o.ksplit_ws_floats = w.kp_floats;
+      ALCM_TRY(plane_conv(s, o, TI));
       ALCM_TRY(rms_norm_plane(w.x, R, D, X.t_eps, Bk.ln1, w.pl, pl, s));
-      ALCM_TRY(plane_lin(s, pl, R, w.pl, D, Bk.wi, w.wi, nullptr, 0));
+      alcm_opconv_args wi = plane_args(Bk.wi, w.pl, 1, R, 1, pl);
+      wi.out = w.wi;
+      ALCM_TRY(plane_conv(s, wi, D));
       if (ps == PREC_SPLIT) {
         // wo on bf16 hi / lo planes of the gated-GELU product (fp32 range, bf16x3 products; see below)
-        const int64_t lo = (int64_t)R * X.t_ff;
-        ALCM_TRY(geglu_split_planes(w.wi, R, X.t_ff, w.pl, lo, s));
-        ALCM_TRY(plane_lin(s, PREC_SPLIT, R, w.pl, X.t_ff, Bk.wo, w.x, w.x, 0, lo));
+        alcm_opconv_args wo = plane_args(Bk.wo, w.pl, 1, R, 1, PREC_SPLIT);
+        wo.res = w.x; wo.out = w.x;
+        ALCM_TRY(geglu_split_planes(w.wi, R, X.t_ff, w.pl, wo.a_lo_off, s));
+        ALCM_TRY(plane_conv(s, wo, X.t_ff));
       } else {
         ALCM_TRY(geglu_pairs(w.wi, R, X.t_ff, w.inter, s));
         ConvOpts r2;

@@ -161,6 +161,46 @@ def to_out_rate(wav: torch.Tensor, out_sample_rate: Optional[int]) -> Tuple[torc
     return kernels.resample(wav.contiguous(), SAMPLE_RATE, out_sample_rate), out_sample_rate
 
 
+@dataclass(frozen=True)
+class Level:
+    """What ``check_level`` decided about the level of the output; ``finish_output`` applies it."""
+    loudness: Optional[float]   # target integrated loudness in LUFS, None: none
+    peak_dbfs: Optional[float]  # peak ceiling in dBFS, None: none
+    true_peak: bool             # the ceiling acts on the 4x oversampled peak estimate
+
+
+def check_level(loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
+                true_peak: bool = False) -> Optional[Level]:
+    """Validates the level options; None when none is given (the output is then written as it is).  A target is
+    within -70 .. 0 LUFS, a ceiling is at most 0 dBFS, ``true_peak`` needs one of them, and a target alone implies a
+    ceiling of -1 dBFS, so that a normalised file never clips."""
+    from .loudness import ABS_GATE, DEFAULT_CEILING_DBFS
+    if loudness is None and peak_dbfs is None:
+        if true_peak:
+            raise ValueError("true_peak says how the peak is measured: give it with loudness or peak_dbfs")
+        return None
+    if loudness is not None and not (ABS_GATE <= float(loudness) <= 0.0):   # refuses NaN too
+        raise ValueError(f"loudness must lie within {ABS_GATE:g} .. 0 LUFS, got {loudness!r}")
+    if peak_dbfs is not None and not (-math.inf < float(peak_dbfs) <= 0.0):
+        raise ValueError(f"peak_dbfs must be a finite ceiling of at most 0 dBFS, got {peak_dbfs!r}")
+    return Level(None if loudness is None else float(loudness),
+                 DEFAULT_CEILING_DBFS if peak_dbfs is None else float(peak_dbfs), bool(true_peak))
+
+
+def finish_output(wav16: torch.Tensor, out_sample_rate: Optional[int], level: Optional[Level] = None,
+                  n_out: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """The output stage: (B, L) at 16 kHz on the device -> (what is written, its rate).  ``to_out_rate``, then a crop
+    to ``n_out`` samples when given, then with ``level`` the normalisation of exactly those samples at that rate
+    (``kernels.normalize_loudness``).  ``level`` None launches nothing more than ``to_out_rate``."""
+    wav, rate = to_out_rate(wav16, out_sample_rate)
+    if n_out is not None:
+        wav = wav[:, :n_out]
+    if level is not None:
+        from . import kernels
+        wav = kernels.normalize_loudness(wav, rate, level.loudness, level.peak_dbfs, level.true_peak)["wav"]
+    return wav, rate
+
+
 # ---------------------------------------------------------------------------- the request plan
 @dataclass(frozen=True, eq=False)
 class EditPlan:
@@ -178,17 +218,24 @@ class EditPlan:
     pcm_scale: float                                    # PCM16 scale: 32768 gives kept samples back bit for bit
     native: bool                                        # keep_original with resample: the file's own rate was read,
     #                                                     so the header rate is no label on 16 kHz samples
+    level: Optional[Level] = None                       # the level of the output (`check_level`), None: as generated
 
 
 def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]]] = None, keep_original: bool = False,
               fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
-              max_frames: Optional[int] = None) -> EditPlan:
+              max_frames: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
+              true_peak: bool = False) -> EditPlan:
     """Reads ``init_audio`` once and decides the request, or refuses it with ValueError.  No ``mask_spans``: a
     variation; with them: an inpainting of the clip (both crop to ``max_frames`` latent frames here when given;
     ``run_edit`` crops to the DiT's limit in any case); ``keep_original``: the whole frames inside the spans are
-    regenerated in a clip of any length, at 16 kHz or, with ``resample``, at the recording's own rate."""
+    regenerated in a clip of any length, at 16 kHz or, with ``resample``, at the recording's own rate.  ``loudness``,
+    ``peak_dbfs``, ``true_peak``: the level of the output (``check_level``); refused with ``keep_original``."""
     if keep_original and not mask_spans:
         raise ValueError("keep_original needs mask_spans: the time spans to regenerate")
+    level = check_level(loudness, peak_dbfs, true_peak)
+    if keep_original and level is not None:
+        raise ValueError("keep_original keeps the input's samples bit for bit outside the spans; loudness, peak_dbfs and "
+                         "true_peak would scale them")
     out_sample_rate = check_out_rate(out_sample_rate)
     x, rate, F = _read_mono(init_audio, resample, keep_original, out_sample_rate)
     samples = _pad_to_frames(x, F)
@@ -201,4 +248,4 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
         samples = samples if max_frames is None else samples[:max_frames * F]
     out_rate = rate if keep_original else out_sample_rate or SAMPLE_RATE
     return EditPlan(mode, samples, x.size, rate, F, spans, mask, fade_samples_of(fade_ms, rate), out_rate,
-                    out_rate != rate, 32768.0 if keep_original else 32767.0, keep_original and resample)
+                    out_rate != rate, 32768.0 if keep_original else 32767.0, keep_original and resample, level)

@@ -26,6 +26,10 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
   * ``--out-sample-rate R`` resamples every output from 16 kHz to R on the GPU and writes R into the header.
     ``--sample_rate`` (default 22050, the reference's) only labels the header of the 16 kHz samples, as in the
     reference, and is ignored when ``--out-sample-rate`` is given;
+  * ``--loudness LUFS`` brings every output to that ITU-R BS.1770 integrated loudness, measured on the GPU on the
+    samples that are written; ``--peak DBFS`` scales a clip down where its peak would pass that ceiling (-1 dBFS when
+    only ``--loudness`` is given); ``--true-peak`` lets the ceiling act on the 4x oversampled peak estimate.  Refused
+    with ``--keep-original``, whose kept samples they would scale;
   * ``--synthetic-seed N`` runs on the seeded recipe weights (no checkpoints offline).
 """
 from __future__ import annotations
@@ -40,7 +44,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .audio_in import FRAME_SAMPLES, SAMPLE_RATE, EditPlan, check_out_rate, parse_spans, plan_edit, to_out_rate
+from .audio_in import (FRAME_SAMPLES, SAMPLE_RATE, EditPlan, check_level, check_out_rate, finish_output, parse_spans,
+                       plan_edit)
 from .config import instantiate_from_config, load_config
 from .infer_api import build_models, struct_caption
 from .lcm import LCMSampler
@@ -88,6 +93,12 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--out-sample-rate", type=int, default=None,
                    help="resample the output from 16 kHz to this rate on the GPU and write it into the header "
                         "(--sample_rate only labels the header and is then ignored)")
+    p.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                   help="bring every output to this ITU-R BS.1770 integrated loudness (-70 .. 0) on the GPU")
+    p.add_argument("--peak", type=float, default=None, metavar="DBFS",
+                   help="peak ceiling of every output in dBFS, at most 0 (default with --loudness: -1)")
+    p.add_argument("--true-peak", action="store_true",
+                   help="with --loudness or --peak: the ceiling acts on the 4x oversampled peak estimate")
     p.add_argument("--duration", type=float, default=None,
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--long-joint", action="store_true",
@@ -109,6 +120,7 @@ class GenSamples:
         self.channel_dim = model.channels
         self.original_inference_steps = original_inference_steps
         self.plan = plan
+        self.level = check_level(opt.loudness, opt.peak, opt.true_peak)
 
     @functools.cached_property
     def pipeline(self):
@@ -138,8 +150,9 @@ class GenSamples:
             mel = self.model.decode_first_stage(z)
             wav = self.vocoder.vocode(mel).squeeze(1) if self.save_wav else None
         rate = self.opt.sample_rate
-        if wav is not None and not label:
-            wav, rate = to_out_rate(wav, self.opt.out_sample_rate)
+        if wav is not None and (not label or self.level is not None):
+            wav, out_rate = finish_output(wav, self.opt.out_sample_rate, self.level)
+            rate = rate if label else out_rate
         return mel, wav, rate, 32767.0
 
     def clip_seed(self, prompt_index: int, it: int, j: int) -> int:
@@ -194,9 +207,11 @@ def build(opt):
     if opt.resample and not opt.init_audio:
         raise ValueError("--resample is used with --init-audio")
     check_out_rate(opt.out_sample_rate)
+    check_level(opt.loudness, opt.peak, opt.true_peak)
     # the file and the flags decide: a refused request fails before the models are built
     plan = plan_edit(opt.init_audio, parse_spans(opt.mask_spans) if opt.inpaint else None, opt.keep_original,
-                     opt.fade_ms, opt.resample, opt.out_sample_rate) if opt.init_audio else None
+                     opt.fade_ms, opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
+                     true_peak=opt.true_peak) if opt.init_audio else None
     config = load_config(opt.base)
     split = {"split": True, "bf16": "bf16", "mixed": "mixed"}[opt.precision]
     if opt.synthetic_seed is None:

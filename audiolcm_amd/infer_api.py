@@ -17,9 +17,10 @@ import numpy as np
 import torch
 
 from . import recipe
-from .audio_in import (FRAME_SAMPLES, SAMPLE_RATE, EditPlan, check_native_keep_original, check_out_rate,  # noqa: F401
-                       fade_samples_of, keep_original_mask, load_init_audio, load_init_audio_whole, load_native_audio,
-                       parse_spans, plan_edit, spans_to_mask, to_out_rate)
+from .audio_in import (FRAME_SAMPLES, SAMPLE_RATE, EditPlan, Level, check_level,  # noqa: F401
+                       check_native_keep_original, check_out_rate, fade_samples_of, finish_output, keep_original_mask,
+                       load_init_audio, load_init_audio_whole, load_native_audio, parse_spans, plan_edit, spans_to_mask,
+                       to_out_rate)
 from .ckpt import load_checkpoint, state_dict_of
 from .config import instantiate_from_config, load_config
 from .lcm import LCM_audio, LCMSampler
@@ -55,9 +56,11 @@ class GenSamples:
 
     def __init__(self, sampler: LCMSampler, model: LCM_audio, outpath: str, vocoder=None, save_mel=True,
                  save_wav=True, original_inference_steps=None, steps: int = 2, guidance_scale: float = 5.0,
-                 out_sample_rate: Optional[int] = None):
+                 out_sample_rate: Optional[int] = None, loudness: Optional[float] = None,
+                 peak_dbfs: Optional[float] = None, true_peak: bool = False):
         self.sampler, self.model, self.outpath = sampler, model, outpath
         self.out_sample_rate = check_out_rate(out_sample_rate)
+        self.level = check_level(loudness, peak_dbfs, true_peak)
         if save_wav:
             assert vocoder is not None
         self.vocoder = vocoder
@@ -76,7 +79,7 @@ class GenSamples:
         mel = self.model.decode_first_stage(z)
         wav, rate = None, SAMPLE_RATE
         if self.save_wav:
-            wav, rate = to_out_rate(self.vocoder.vocode(mel).squeeze(1), self.out_sample_rate)
+            wav, rate = finish_output(self.vocoder.vocode(mel).squeeze(1), self.out_sample_rate, self.level)
             wav = wav.cpu().numpy()
         mel_np = mel.cpu().numpy()
         records = []
@@ -129,18 +132,26 @@ def AudioLCMBatchInfer(ori_prompts: List[str], config_path: str = "configs/audio
                        model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
                        batch_size: int = 32, synthetic_seed: Optional[int] = None, split: bool = True,
                        outpath: str = "results/test", seed: Optional[int] = None,
-                       synthetic_tokenizer: bool = False, out_sample_rate: Optional[int] = None) -> str:
+                       synthetic_tokenizer: bool = False, out_sample_rate: Optional[int] = None,
+                       loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
+                       true_peak: bool = False) -> str:
     """InferAPI.py:135-166. Returns the path of the last prompt's WAV.  ``seed``: per-prompt RNG seeds
     seed + i (default None: the global device RNG, as the reference).  ``synthetic_tokenizer``: run checkpoint
     weights on the hash-id tokenizer stand-in when the tokenizer directories are absent (tests only).
-    ``out_sample_rate``: resample the 16 kHz waveform to that rate on the GPU and write it under that rate."""
+    ``out_sample_rate``: resample the 16 kHz waveform to that rate on the GPU and write it under that rate.
+    ``loudness``: bring each clip to that ITU-R BS.1770 integrated loudness in LUFS (-70 .. 0), measured on the GPU on
+    the samples that are written; ``peak_dbfs``: scale a clip down where its peak would pass that ceiling (at most 0
+    dBFS; -1 when only ``loudness`` is given, so a normalised file never clips); ``true_peak``: the ceiling acts on the
+    4x oversampled peak estimate.  Without the three the samples are written as generated."""
     check_out_rate(out_sample_rate)
+    check_level(loudness, peak_dbfs, true_peak)
     prompts = [dict(ori_caption=p, struct_caption=struct_caption(p)) for p in ori_prompts]
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  synthetic_tokenizer)
     os.makedirs(outpath, exist_ok=True)
     gen = GenSamples(sampler, model, outpath, vocoder, save_mel=False, save_wav=True,
-                     original_inference_steps=orig_steps, out_sample_rate=out_sample_rate)
+                     original_inference_steps=orig_steps, out_sample_rate=out_sample_rate, loudness=loudness,
+                     peak_dbfs=peak_dbfs, true_peak=true_peak)
     names = [wav_name_for(p["ori_caption"]) for p in prompts]
     with torch.no_grad():
         for lo in range(0, len(prompts), batch_size):
@@ -154,10 +165,12 @@ def AudioLCMBatchInfer(ori_prompts: List[str], config_path: str = "configs/audio
 def AudioLCMInfer(ori_prompt: str, config_path: str = "configs/audiolcm.yaml",
                   model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
                   synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
-                  seed: Optional[int] = None, out_sample_rate: Optional[int] = None) -> str:
-    """InferAPI.py:103-133."""
+                  seed: Optional[int] = None, out_sample_rate: Optional[int] = None,
+                  loudness: Optional[float] = None, peak_dbfs: Optional[float] = None, true_peak: bool = False) -> str:
+    """InferAPI.py:103-133.  ``loudness``, ``peak_dbfs``, ``true_peak``: as ``AudioLCMBatchInfer``."""
     return AudioLCMBatchInfer([ori_prompt], config_path, model_path, vocoder_path, 1, synthetic_seed, split, outpath,
-                              seed, out_sample_rate=out_sample_rate)
+                              seed, out_sample_rate=out_sample_rate, loudness=loudness, peak_dbfs=peak_dbfs,
+                              true_peak=true_peak)
 
 
 # ---------------------------------------------------------------------------- audio-conditioned generation
@@ -170,7 +183,9 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
                       config_path: str = "configs/audiolcm.yaml", model_path: str = "./model/000184.ckpt",
                       vocoder_path: str = "./model/vocoder", synthetic_seed: Optional[int] = None, split: bool = True,
                       outpath: str = "results/test", seed: Optional[int] = None, keep_original: bool = False,
-                      fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None) -> str:
+                      fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
+                      loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
+                      true_peak: bool = False) -> str:
     """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength``, or, with ``mask_spans``
     ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
     clip is synthesised again from the latent, cropped to the DiT's 845 frames.  ``keep_original`` (needs
@@ -182,9 +197,12 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
     then done at the recording's own rate (``AudioLCMPipeline.edit_long(rate=...)``; mono, and a rate at which a latent
     frame is a whole number of samples: 48000, 32000, 8000, ...) and the output has the input's rate and sample count.
     ``out_sample_rate``: the output is resampled from 16 kHz to that rate on the GPU and written under it (with
-    ``keep_original`` it may only name the input's rate).  Returns the WAV path (``<prompt-with-dashes>_0.wav``)."""
+    ``keep_original`` it may only name the input's rate).  ``loudness``, ``peak_dbfs``, ``true_peak``: the level of the
+    output, as ``AudioLCMBatchInfer``; refused with ``keep_original``, whose kept samples they would scale.  Returns the
+    WAV path (``<prompt-with-dashes>_0.wav``)."""
     from .pipeline import AudioLCMPipeline
-    plan = plan_edit(init_audio, mask_spans, keep_original, fade_ms, resample, out_sample_rate)  # before any model
+    plan = plan_edit(init_audio, mask_spans, keep_original, fade_ms, resample, out_sample_rate, loudness=loudness,
+                     peak_dbfs=peak_dbfs, true_peak=true_peak)  # before any model
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  encoder=True)
     pipe = AudioLCMPipeline(model, vocoder.generator, steps=2, original_inference_steps=orig_steps,
@@ -201,15 +219,19 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
 def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: str = "configs/audiolcm.yaml",
                       model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
                       synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
-                      seed: Optional[int] = None, out_sample_rate: Optional[int] = None, joint: bool = False) -> str:
+                      seed: Optional[int] = None, out_sample_rate: Optional[int] = None, joint: bool = False,
+                      loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
+                      true_peak: bool = False) -> str:
     """A clip of ceil(duration_s * 16000 / 512) latent frames by long-form continuation
     (``AudioLCMPipeline.generate_long``).  ``seed`` None draws the clip's base seed from the global RNG.
     ``joint``: the windows are denoised jointly, one DiT call per LCM step (``generate_long(joint=True)``).
     ``out_sample_rate``: the clip is resampled from 16 kHz to that rate on the GPU, cropped to
     round(duration_s * out_sample_rate) samples and written under that rate (without it the file keeps every sample
-    of the last latent frame, as before).  Returns the WAV path."""
+    of the last latent frame, as before).  ``loudness``, ``peak_dbfs``, ``true_peak``: the level of the output, as
+    ``AudioLCMBatchInfer``, measured at the output rate on the cropped clip.  Returns the WAV path."""
     from .pipeline import AudioLCMPipeline
     check_out_rate(out_sample_rate)
+    level = check_level(loudness, peak_dbfs, true_peak)
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split)
     latent_len = math.ceil(duration_s * SAMPLE_RATE / FRAME_SAMPLES)
     if latent_len < 1:
@@ -220,9 +242,9 @@ def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: st
     os.makedirs(outpath, exist_ok=True)
     with torch.no_grad():
         c = model.get_learned_conditioning({"ori_caption": [ori_prompt], "struct_caption": [struct_caption(ori_prompt)]})
-        wav, rate = to_out_rate(pipe.generate_long(c, [base], latent_len, joint=joint)["wav"], out_sample_rate)
-        if out_sample_rate is not None:
-            wav = wav[:, :int(round(duration_s * rate))]
+        n_out = None if out_sample_rate is None else int(round(duration_s * out_sample_rate))
+        wav, rate = finish_output(pipe.generate_long(c, [base], latent_len, joint=joint)["wav"], out_sample_rate, level,
+                                  n_out)
         wav = wav.cpu().numpy()
     path = os.path.join(outpath, wav_name_for(ori_prompt) + "_0.wav")
     write_pcm16(path, wav[0], rate)

@@ -467,6 +467,90 @@ def resample(x: torch.Tensor, rate_in: int, rate_out: int, channels: int = 1) ->
     return y
 
 
+_loudness_coef = {}
+
+
+def loudness_coef(rate: int, device) -> torch.Tensor:
+    """``loudness.tables(rate)`` on ``device`` (float64), uploaded once per rate and device."""
+    from . import loudness as _ld
+    key = (int(rate), torch.device(device))
+    if key not in _loudness_coef:
+        _loudness_coef[key] = torch.from_numpy(_ld.tables(int(rate)).copy()).to(device)
+    return _loudness_coef[key]
+
+
+def _row_stride(wav: torch.Tensor) -> int:
+    """The row stride of a (B, N) fp32 device tensor with unit column stride."""
+    assert wav.is_cuda and wav.dtype == torch.float32 and wav.dim() == 2
+    assert wav.shape[1] <= 1 or wav.stride(1) == 1, "samples must be contiguous within a clip"
+    ld = wav.stride(0) if wav.shape[0] > 1 else max(wav.stride(0), wav.shape[1])
+    assert ld >= wav.shape[1], "rows overlap"
+    return int(ld)
+
+
+def _loudness_pass(wav: torch.Tensor, coef: Optional[torch.Tensor], hop: int, want_sums: bool, want_peak: bool):
+    """One ``alcm_loudness_hops``: (hop sums (B, N // hop) float64 or None, peak (B,) or None)."""
+    B, N = wav.shape
+    sums = torch.empty((B, N // hop), device=wav.device, dtype=torch.float64) if want_sums else None
+    peak = torch.empty((B,), device=wav.device, dtype=torch.float32) if want_peak else None
+    if B == 0:
+        return sums, peak
+    nbytes = lib().alcm_loudness_workspace_bytes(B, N, hop)
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, device=wav.device, dtype=torch.float64)
+    check(lib().alcm_loudness_hops(ptr(wav), B, N, _row_stride(wav), ptr(coef) if want_sums else None, hop, ptr(sums),
+                                   ptr(peak), ptr(ws), ws.numel() * 8, stream_handle()), "loudness_hops")
+    return sums, peak
+
+
+def _measure(wav: torch.Tensor, rate: int, true_peak: bool):
+    from . import loudness as _ld
+    pl = _ld.plan(rate, wav.shape[1])
+    sums, peak = _loudness_pass(wav, loudness_coef(rate, wav.device), pl.hop, True, not true_peak)
+    if true_peak:
+        peak = _loudness_pass(resample(wav.contiguous(), rate, 4 * int(rate)), None, pl.hop, False, True)[1]
+    return pl, sums, peak
+
+
+def _loudness_gain(pl, sums, peak, target: float, ceiling: float, want_lufs: bool, want_gain: bool):
+    B = sums.shape[0]
+    lufs = torch.empty((B,), device=sums.device, dtype=torch.float32) if want_lufs else None
+    gain = torch.empty((B,), device=sums.device, dtype=torch.float32) if want_gain else None
+    check(lib().alcm_loudness_gain(ptr(sums), ptr(peak), B, pl.nh, pl.hop, float(target), float(ceiling), ptr(lufs),
+                                   ptr(gain), stream_handle()), "loudness_gain")
+    return lufs, gain
+
+
+def loudness(wav: torch.Tensor, rate: int, true_peak: bool = False):
+    """ITU-R BS.1770 integrated loudness of the mono clips wav (B, N) at ``rate`` -> (lufs (B,) fp32, -inf for a clip
+    no block of which passes the absolute gate; peak (B,) fp32: max |wav|, or with ``true_peak`` the same maximum over
+    ``resample(wav, rate, 4 * rate)``; hop_sums (B, N // hop) float64), all on the device and without a host
+    synchronisation (alcm_loudness_hops, alcm_loudness_gain; the plan: ``audiolcm_amd/loudness.py``).  ValueError for a
+    clip under 400 ms."""
+    pl, sums, peak = _measure(wav, rate, true_peak)
+    lufs, _ = _loudness_gain(pl, sums, peak, float("nan"), 0.0, True, False)
+    return lufs, peak, sums
+
+
+def normalize_loudness(wav: torch.Tensor, rate: int, target: Optional[float] = None,
+                       peak_dbfs: Optional[float] = None, true_peak: bool = False,
+                       out: Optional[torch.Tensor] = None) -> dict:
+    """Scale each clip of wav (B, N) to ``target`` LUFS, and by less where its peak would pass ``peak_dbfs``: ->
+    dict(wav, lufs (the input's), gain, peak (the input's)), device tensors.  ``target`` None: only the ceiling acts;
+    ``peak_dbfs`` None: no ceiling.  The ceiling holds exactly for the sample peak: no |out| exceeds
+    fp32(10^(peak_dbfs / 20)); with ``true_peak`` the peak is the 4x oversampled estimate and the ceiling holds for
+    it up to rounding.  ``out`` None: a new tensor; ``out=wav`` scales in place.  A gain of 1 returns the input's bits."""
+    pl, sums, peak = _measure(wav, rate, true_peak)
+    ceiling = 0.0 if peak_dbfs is None else 10.0 ** (float(peak_dbfs) / 20.0)
+    lufs, gain = _loudness_gain(pl, sums, peak, float("nan") if target is None else float(target), ceiling, True, True)
+    if out is None:
+        out = torch.empty(wav.shape, device=wav.device, dtype=torch.float32)
+    assert out.shape == wav.shape
+    B, N = wav.shape
+    check(lib().alcm_wave_gain(ptr(wav), ptr(gain), ptr(out), B, N, _row_stride(wav), _row_stride(out), stream_handle()),
+          "wave_gain")
+    return dict(wav=out, lufs=lufs, gain=gain, peak=peak)
+
+
 def sincos_embedding(v: torch.Tensor, freqs: torch.Tensor, scale: float, cos_first: bool) -> torch.Tensor:
     B = v.shape[0]
     half = freqs.numel()

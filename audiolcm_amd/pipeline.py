@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import recipe
-from .audio_in import FRAME_SAMPLES, SAMPLE_RATE, EditPlan, frame_samples_of, spans_to_mask, to_out_rate
+from .audio_in import FRAME_SAMPLES, SAMPLE_RATE, EditPlan, finish_output, frame_samples_of, spans_to_mask
 from .lcm import LCM_audio, LCMSampler
 from .models import AutoencoderKL, BigVGAN, ConcatDiT2MLP
 
@@ -327,8 +327,9 @@ class AudioLCMPipeline:
         """One clip per row of ``cond`` from the one recording of ``plan`` (``audio_in.plan_edit``) -> (the waveform
         (B, samples) on the device, the rate to write it under, the mel or None).  Variation and inpainting: the clip is
         cropped to the DiT's length limit and encoded once, the posterior is expanded to the batch, and ``edit`` makes
-        the whole clip again, resampled to the plan's output rate.  Keep-original: ``edit_long`` at the plan's rate on
-        the whole recording, cropped to the input's sample count; no whole-clip mel is decoded."""
+        the whole clip again, resampled to the plan's output rate and brought to the plan's level
+        (``audio_in.finish_output``).  Keep-original: ``edit_long`` at the plan's rate on the whole recording, cropped
+        to the input's sample count; no whole-clip mel is decoded."""
         B = cond.shape[0]
         if plan.mode == "keep_original":
             wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
@@ -343,7 +344,7 @@ class AudioLCMPipeline:
         mask = None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
         init = DiagonalGaussianDistribution(post.parameters.expand(B, -1, -1).contiguous())
         out = self.edit(cond, seeds, latent=init, mask=mask, strength=strength)
-        wav, rate = to_out_rate(out["wav"], plan.out_rate)
+        wav, rate = finish_output(out["wav"], plan.out_rate, plan.level)
         return wav, rate, out["mel"]
 
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):

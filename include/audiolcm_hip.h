@@ -352,6 +352,45 @@ int alcm_wave_paste(const float* orig, const float* gen, const float* mask, cons
  * B or N_in of 0: no launch. */
 int alcm_resample(const float* x, float* y, int B, int64_t N_in, int channels, int64_t N_out, int up, int down,
                   const float* taps, int ntaps, int first, alcm_stream_t stream);
+/* alcm_loudness_hops: the K-weighted energy of a batch of mono clips per 100 ms hop and their sample peak (ITU-R
+ * BS.1770; no reference counterpart: the reference writes the vocoder's waveform as it is).
+ *   x (B, N) fp32, row stride ld >= N; y = x through the two biquads of coef in cascade from zero state;
+ *   hop_sums_out[b][h] = sum of y^2 over the samples h * hop .. (h + 1) * hop, h = 0 .. N / hop - 1, (B, N / hop)
+ *   fp64 (a trailing partial hop is left out); peak_out[b] = max |x[b][n]| (B) fp32, exact.
+ *   coef (device, 154 fp64, audiolcm_amd/loudness.py tables(rate)): the high shelf's and the high pass's
+ *   (b0, b1, b2, a1, a2), then the cascade's 4 x 4 state-transition matrix M (row-major, state s1, s2, t1, t2 of the
+ *   transposed direct form II) to the powers 32 * 2^j, j = 0 .. 7, and 8192.
+ * Either output may be NULL, not both; hop_sums_out NULL is a peak-only pass that does not read coef.  The
+ * recursion runs in parallel over time: a thread per 32 samples, a workgroup per 8192, the states joined by a scan of
+ * the chunks' affine maps; state and sums are fp64.  Three launches (two for peak only), no atomics: the partial sums
+ * are added in rising order and a clip's bits depend on neither B, ld nor the other clips.  Index arithmetic is
+ * 64-bit; 16-byte loads when x is 16-byte aligned and ld a multiple of 4, element loads otherwise, same values.
+ * ws: alcm_loudness_workspace_bytes(B, N, hop) bytes of device memory, 8-byte aligned (0 for an empty or invalid
+ * problem).  ALCM_E_INVALID for a null x, no output, hop_sums_out without coef, a negative B or N, hop < 1, ld < N or
+ * a workspace that is null, misaligned or too small.  B or N of 0: no launch. */
+size_t alcm_loudness_workspace_bytes(int B, int64_t N, int hop);
+int alcm_loudness_hops(const float* x, int B, int64_t N, int64_t ld, const double* coef, int hop, double* hop_sums_out,
+                       float* peak_out, void* ws, size_t ws_bytes, alcm_stream_t stream);
+/* alcm_loudness_gain: gated integrated loudness of each clip from its hop sums, and the gain to a target under a peak
+ * ceiling; one launch, one wave per clip, fp64, no host synchronisation.
+ *   hop_sums (B, nh) fp64 and peak (B) fp32 as alcm_loudness_hops writes them; block j = hops j .. j + 3, nh - 3
+ *   blocks: z_j = (S_j + S_j+1 + S_j+2 + S_j+3) / (4 hop), l_j = -0.691 + 10 log10 z_j;
+ *   absolute gate: l_j > -70; relative gate: l_j > -0.691 + 10 log10(mean z of the blocks past the absolute gate) - 10;
+ *   L = -0.691 + 10 log10(mean z of the blocks past both gates), -inf when none passes the absolute gate (or nh < 4);
+ *   gain = 10^((target_lufs - L) / 20) rounded to fp32, 1 when target_lufs is NaN or L = -inf; then, with ceiling > 0
+ *   (linear) and fl(peak * gain) > ceiling: gain = fl(ceiling / peak), stepped down one ulp while
+ *   fl(peak * gain) > ceiling, so that no sample of |x| <= peak times gain exceeds the ceiling.
+ * lufs_out, gain_out (B) fp32; either may be NULL, not both; peak may be NULL without a ceiling.
+ * ALCM_E_INVALID for no output, a negative B or nh, hop < 1, null hop_sums with nh > 0 or a ceiling without peak.
+ * B of 0: no launch. */
+int alcm_loudness_gain(const double* hop_sums, const float* peak, int B, int64_t nh, int hop, float target_lufs,
+                       float ceiling, float* lufs_out, float* gain_out, alcm_stream_t stream);
+/* alcm_wave_gain: y[b][n] = x[b][n] * gain[b], one fp32 rounding; x (B, N) row stride ldx, y (B, N) row stride ldy,
+ * gain (B) device.  y may be x itself; a gain of 1 leaves the bits as they are.  16-byte accesses when x and y are
+ * 16-byte aligned and ldx, ldy multiples of 4, element accesses otherwise.
+ * ALCM_E_INVALID for a null x, gain or y, a negative B or N, or a stride < N.  B or N of 0: no launch. */
+int alcm_wave_gain(const float* x, const float* gain, float* y, int B, int64_t N, int64_t ldx, int64_t ldy,
+                   alcm_stream_t stream);
 /* out[b] = [f(v[b]*vscale*freqs[i]) ...]: cos_first ? [cos | sin] (TimestepEmbedder, concatDiT.py:49-67)
  *                                                   : [sin | cos] (get_guidance_scale_embedding, w*1000).
  * freqs: the reference's fp32 frequency table (half entries, device pointer) */

@@ -7,6 +7,7 @@ Used to A/B kernel variants in one process and as the target of 
     python scripts/microbench.py act        # standalone Activation1d
     python scripts/microbench.py paste      # alcm_wave_paste in place / out of place
     python scripts/microbench.py resample   # alcm_resample on the recorded shapes
+    python scripts/microbench.py loudness   # the loudness launches beside alcm_resample 16 -> 48 kHz
     python scripts/microbench.py editlong   # 30 s keep-original edit: region decode + paste vs whole-clip decode
     python scripts/microbench.py longjoint  # 30 s long-form clip: chained windows vs windows denoised jointly
 """
@@ -568,6 +569,33 @@ def bench_resample():
               f"{nbytes / 8e12 * 1e6:6.1f} us  {nbytes / ev / 1e9:6.3f} TB/s  {flops / ev / 1e9:6.2f} TFLOP/s fp32", flush=True)
 
 
+def bench_loudness():
+    """normalize_loudness on the headline batch (B = 32, 10 s) and on one 30 s clip at 16 kHz: every launch of it by the
+    library's per-launch events, best of 3 x 50 calls, beside alcm_resample 16000 -> 48000 on the same waveforms (a
+    kernel that reads the same bytes); bytes from the launches' own profile rows"""
+    for B, N in ((32, 160000), (1, 480000)):
+        x = torch.rand((B, N), device="cuda") - 0.5
+        out = torch.empty_like(x)
+        K.normalize_loudness(x, 16000, -23.0, -1.0, out=out)
+        K.resample(x, 16000, 48000)
+        torch.cuda.synchronize()
+        best = {}
+        for _ in range(3):
+            _hip.profile_begin()
+            for _ in range(50):
+                K.normalize_loudness(x, 16000, -23.0, -1.0, out=out)
+                K.resample(x, 16000, 48000)
+            for r in _hip.profile_end():
+                t = r["total_ms"] / r["launches"]
+                if r["name"] not in best or t < best[r["name"]][0]:
+                    best[r["name"]] = (t, r["bytes"] / r["launches"])
+        for name, (t, nbytes) in best.items():
+            print(f"loudness B={B} N={N} {name:30s}: {t * 1e3:7.1f} us by events  {nbytes / 1e6:7.2f} MB  "
+                  f"{nbytes / t / 1e9:6.3f} TB/s", flush=True)
+        total = sum(t for n, (t, _) in best.items() if "resample" not in n)
+        print(f"loudness B={B} N={N} the five loudness launches together: {total * 1e3:7.1f} us", flush=True)
+
+
 def bench_editlong(L=936, reps=5):
     """edit_long on a 30 s clip (936 frames, B = 1, mixed policy, one 2 s span) from a waveform: keep_original=True
     (decode of the span's region + one paste) against keep_original=False (decode of the whole clip); alternating,
@@ -643,4 +671,4 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["op", "conv", "act"]
     spin(float(os.environ.get("SPIN", "3")))
     for w in which:
-        {"resample": bench_resample, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()
+        {"resample": bench_resample, "loudness": bench_loudness, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()

@@ -62,6 +62,11 @@ class ConvPlanInfo(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class GemmPlanInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 128), ("family", C.c_int), ("bm", C.c_int), ("bn", C.c_int), ("wm", C.c_int),
+                ("wn", C.c_int), ("grid", C.c_int * 3), ("flops", C.c_double), ("bytes", C.c_double)]
+
+
 VOC_MAX_RB, VOC_MAX_DIL = 8, 8
 
 
@@ -137,6 +142,7 @@ _SIGS = [
     ("alcm_debug_tconv_wg_times", C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     ("alcm_debug_conv_plan", C.c_int, [C.POINTER(OpConvArgs), C.c_int, C.c_int, C.c_int, C.POINTER(ConvPlanInfo),
                                        C.POINTER(C.c_int)]),
+    ("alcm_debug_gemm_plan", C.c_int, [C.POINTER(GemmArgs), C.POINTER(GemmPlanInfo)]),
     ("alcm_debug_voc_plan", C.c_int, [C.POINTER(VocStageShape), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(VocStagePlan)]),
     ("alcm_debug_ksplit_parts", C.c_int, [i64, i64, C.c_int, C.c_double, C.c_double]),
@@ -255,6 +261,19 @@ def debug_conv_plan(args, n: int = 1, form: int = PLAN_OPCONV, ncu: int = 0) -> 
                  tiles_per_batch=out[i].tiles_per_batch, tiles=int(out[i].tiles), flops=out[i].flops,
                  bytes=out[i].bytes)
             for i in range(nl.value)]
+
+
+GEMM_FAMILIES = ("none", "window_conv", "skinny", "gemm")
+
+
+def debug_gemm_plan(args) -> dict:
+    """Diagnostics: the launch alcm_gemm would make for a GemmArgs under the current ALCM_* switches (name = its profile
+    row, family, bm, bn, wm, wn, grid, flops, bytes); raises HipError with the call's own error.  Host only: nothing is
+    launched or dereferenced and no device is needed (alcm_debug_gemm_plan)."""
+    out = GemmPlanInfo()
+    check(lib().alcm_debug_gemm_plan(C.byref(args), C.byref(out)), "alcm_debug_gemm_plan")
+    return dict(name=out.name.decode(), family=GEMM_FAMILIES[out.family], bm=out.bm, bn=out.bn, wm=out.wm, wn=out.wn,
+                grid=list(out.grid), flops=out.flops, bytes=out.bytes)
 
 
 VOC_UPS = ("planes", "ups2", "phases")

@@ -26,10 +26,10 @@
 #include "alcm_common.h"
 #include "audiolcm_hip.h"
 #include "alcm_internal.h"
+#include "alcm_gemmplan.h"
 
 namespace alcm {
 
-constexpr int BK = 32;
 // GEMM tiles in LDS: rows of BK=32 bf16 (64 B, unpadded); the 16-B chunk kq of row r sits at chunk
 // slot kq ^ ((r >> 2) & 2).  A ds_read_b128 fragment read (lane l: row l&15 of an aligned 16-row
 // block, chunk l>>4) then hits 16 distinct 16-B bank slots in each of its four 16-lane groups
@@ -88,8 +88,6 @@ struct GemmDev {
   WDev w;
   EpiDev e;
 };
-
-enum { BK_W = 0, BK_ACT = 1, BK_ACTT = 2 };
 
 __device__ __forceinline__ int64_t zoff(const FastDiv& zd, int z, int64_t s1, int64_t s2) {
   uint32_t q, r;
@@ -412,7 +410,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmDev P) {
 // slice order, then the MFMA kernels' epilogue (acc_scale, bias, act, residual, out_scale, accumulate).
 // Rows in blocks of SK_M (grid.y), so which rows share a launch never changes a row's arithmetic: the result is
 // invariant to how a batch is split (eligibility depends on K and the layer, not on M up to SK_MAXM rows).
-constexpr int SK_N = 32, SK_M = 32, SK_KMAX = 768, SK_MAXM = 1024;  // columns / rows per workgroup, K and M limits
+// (SK_N columns x SK_M rows per workgroup, K <= SK_KMAX: alcm_gemmplan.h)
 template <int PREC>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmDev P) {
   __shared__ __attribute__((aligned(16))) float sm[SK_M * SK_KMAX];
@@ -527,8 +525,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const GemmDev P) {
 // are loaded, normalised/activated (prologue) and split to bf16 hi/lo ONCE into LDS, and the k
 // taps then read it at row offset tap*dil.  Compared with the tap-by-tap loader this cuts the A
 // global loads, the fp32->bf16 conversions and the A LDS writes by k (k = 3..11 on the path).
-// Tiles never straddle a batch (grid.x = B * ceil(T_out / BM)); K order = (chunk, tap).
-constexpr int HALO_MAX = 64;
+// Tiles never straddle a batch (grid.x = B * ceil(T_out / BM)); K order = (chunk, tap); (k-1)*dil <= HALO_MAX.
 
 template <int BM, int BN, int WM, int WN, int PREC, bool PRO>
 __global__ __launch_bounds__(256) void conv_kernel(const GemmDev P, int tiles_per_batch, int T_out) {
@@ -714,7 +711,9 @@ __global__ __launch_bounds__(256) void conv_kernel(const GemmDev P, int tiles_pe
 }
 
 // ---------------------------------------------------------------- host side
-static bool fill_act(const alcm_operand& o, int M, ActDev& d, std::string& err) {
+// Every check and the kernel choice are gemm_plan's (alcm_gemmplan.cpp); what follows fills the kernels' argument
+// struct and launches the instantiation the plan names.
+static void fill_act(const alcm_operand& o, int M, ActDev& d) {
   d.p = (const float*)o.ptr;
   d.sb = o.sb; d.st = o.st; d.sc = o.sc;
   d.T_in = o.T_in; d.C_in = o.C_in; d.Cpad = o.Cpad; d.ksize = o.ksize; d.dil = o.dil;
@@ -726,115 +725,22 @@ static bool fill_act(const alcm_operand& o, int M, ActDev& d, std::string& err) 
   d.zs1 = o.zs1; d.zs2 = o.zs2;
   d.ps = o.pro_scale; d.ph = o.pro_shift; d.psb = o.pro_sb;
   d.pm = o.pro_mean; d.pr = o.pro_rstd; d.pact = o.pro_act;
-  if (!o.ptr || o.Cpad <= 0 || o.Cpad % 8 || o.C_in > o.Cpad || o.ksize <= 0 || o.T_in <= 0 ||
-      (d.up != 1 && d.up != 2) || o.rows_per_batch <= 0) {
-    err = "bad ACT operand geometry";
-    return false;
-  }
-  if (o.pro_act != ACT_NONE && o.pro_act != ACT_SILU) {
-    err = "prologue activation must be NONE or SILU";
-    return false;
-  }
-  if ((o.pro_scale == nullptr) != (o.pro_shift == nullptr) || (o.pro_mean == nullptr) != (o.pro_rstd == nullptr)) {
-    err = "prologue scale/shift and mean/rstd must come in pairs";
-    return false;
-  }
-  return true;
 }
 
-static bool act_vec_ok(const alcm_operand& o) {
-  const bool al = (((uintptr_t)o.ptr) & 15) == 0;
-  return al && o.sc == 1 && o.C_in == o.Cpad && o.Cpad % 8 == 0 && o.st % 4 == 0 && o.sb % 4 == 0 &&
-         o.zs1 % 4 == 0 && o.zs2 % 4 == 0;
-}
-
-struct LaunchCost {
-  double flops, bytes;
-};
-static thread_local LaunchCost g_cost;
-
-template <int BM, int BN, int WM, int WN, bool AVEC, int BKIND, int PREC>
-static void launch_one(const GemmDev& P, int batch, int ncols, hipStream_t s) {
-  dim3 grid((P.M + BM - 1) / BM, (ncols + BN - 1) / BN, batch);
-  void* tok = prof_start(s);
-  hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, AVEC, BKIND, PREC>), grid, dim3(256), 0, s, P);
-  if (tok) {
-    // the demangled name rocprofv3 prints for this instantiation
-    char name[128];
-    std::snprintf(name, sizeof(name), "alcm::gemm_kernel<%d, %d, %d, %d, %s, %d, %d>", BM, BN, WM, WN,
-                  AVEC ? "true" : "false", BKIND, PREC);
-    if (knobs().prof_shapes)  // diagnostics: split the statistics per problem shape
-      std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " M%d N%d K%d x%d", P.M, ncols,
-                    P.Kpad, batch);
-    prof_stop(tok, s, name, g_cost.flops, g_cost.bytes);
-  }
-}
-
-template <int BM, int BN, int WM, int WN, bool AVEC, int BKIND>
-static void launch_split(const GemmDev& P, int batch, int ncols, int prec, hipStream_t s) {
-  if (prec == PREC_SPLIT) launch_one<BM, BN, WM, WN, AVEC, BKIND, PREC_SPLIT>(P, batch, ncols, s);
-  else if (prec == PREC_F16) launch_one<BM, BN, WM, WN, AVEC, BKIND, PREC_F16>(P, batch, ncols, s);
-  else launch_one<BM, BN, WM, WN, AVEC, BKIND, PREC_BF16>(P, batch, ncols, s);
-}
-
-template <int BM, int BN, int WM, int WN, int PREC, bool PRO>
-static void launch_conv(const GemmDev& P, int nbatch, int T_out, hipStream_t s) {
-  const int tpb = (T_out + BM - 1) / BM;
-  dim3 grid(nbatch * tpb, (P.N + BN - 1) / BN, 1);
-  void* tok = prof_start(s);
-  hipLaunchKernelGGL((conv_kernel<BM, BN, WM, WN, PREC, PRO>), grid, dim3(256), 0, s, P, tpb, T_out);
-  if (tok) {
-    char name[128];
-    std::snprintf(name, sizeof(name), "alcm::conv_kernel<%d, %d, %d, %d, %d, %s>", BM, BN, WM, WN, PREC,
-                  PRO ? "true" : "false");
-    if (knobs().prof_shapes)
-      std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " T%d N%d K%d k%d up%d x%d", T_out,
-                    P.N, P.Kpad, P.a.ksize, P.a.up, nbatch);
-    prof_stop(tok, s, name, g_cost.flops, g_cost.bytes);
-  }
-}
-
-template <int BM, int BN, int WM, int WN, bool PRO>
-static void launch_conv_sp(const GemmDev& P, int nbatch, int T_out, int prec, hipStream_t s) {
-  if (prec == PREC_SPLIT) launch_conv<BM, BN, WM, WN, PREC_SPLIT, PRO>(P, nbatch, T_out, s);
-  else if (prec == PREC_F16) launch_conv<BM, BN, WM, WN, PREC_F16, PRO>(P, nbatch, T_out, s);
-  else launch_conv<BM, BN, WM, WN, PREC_BF16, PRO>(P, nbatch, T_out, s);
-}
-
-int gemm(const alcm_gemm_args& g, hipStream_t s) {
-  std::string err;
-  if (g.M <= 0 || g.N <= 0) return 0;
-  if (g.Kpad <= 0 || g.Kpad % BK) return set_error(ALCM_E_INVALID, "Kpad must be a positive multiple of 32");
-  if (g.a.kind != ALCM_OPND_ACT) return set_error(ALCM_E_INVALID, "A operand must be ACT");
-  if (!g.out) return set_error(ALCM_E_INVALID, "null output");
-  if (g.geglu && (g.N % 2)) return set_error(ALCM_E_INVALID, "geglu needs even N");
+static GemmDev fill_dev(const GemmPlan& pl, const alcm_gemm_args& g) {
   GemmDev P{};
   P.M = g.M; P.N = g.N; P.Kpad = g.Kpad;
-  const int batch = g.batch > 0 ? g.batch : 1;
   P.zdiv = FastDiv((uint32_t)(g.zdiv > 0 ? g.zdiv : 1));
-  if (!fill_act(g.a, g.M, P.a, err)) return set_error(ALCM_E_INVALID, "A: " + err);
-  if (P.a.Kreal > g.Kpad) return set_error(ALCM_E_INVALID, "Kpad smaller than ksize*Cpad of A");
-  int bkind;
-  if (g.b.kind == ALCM_OPND_WEIGHT) {
-    bkind = BK_W;
+  fill_act(g.a, g.M, P.a);
+  if (pl.bkind == BK_W) {
     // PREC_F16 reads the fp16 plane (third plane of the packed weight) in place of bf16 hi
     P.w.p = (const u16*)g.b.ptr + (g.prec == PREC_F16 ? 2 * g.b.w_lo_off : 0);
     P.w.lo = g.b.w_lo_off; P.w.rows = g.b.rows; P.w.Kpad = g.Kpad;
-    if (!g.b.ptr || g.b.rows < g.N) return set_error(ALCM_E_INVALID, "weight operand rows < N");
-    if ((((uintptr_t)g.b.ptr) & 15) || (g.b.w_lo_off % 8)) return set_error(ALCM_E_INVALID, "weight alignment");
-  } else if (g.b.kind == ALCM_OPND_ACT) {
-    bkind = BK_ACT;
-    if (!fill_act(g.b, g.N, P.bact, err)) return set_error(ALCM_E_INVALID, "B: " + err);
-    if (!act_vec_ok(g.b) || g.b.ksize != 1 || g.b.pro_scale || g.b.pro_mean)
-      return set_error(ALCM_E_INVALID, "B ACT operand must be channel-contiguous, 16B aligned, k=1, no prologue");
-    if (P.bact.Kreal > g.Kpad) return set_error(ALCM_E_INVALID, "Kpad smaller than B K");
-  } else if (g.b.kind == ALCM_OPND_ACT_T) {
-    bkind = BK_ACTT;
+  } else if (pl.bkind == BK_ACT) {
+    fill_act(g.b, g.N, P.bact);
+  } else {
     P.bT.p = (const float*)g.b.ptr; P.bT.st = g.b.st; P.bT.sc = g.b.sc; P.bT.Kext = g.b.T_in;
     P.bT.rows = g.b.rows; P.bT.zs1 = g.b.zs1; P.bT.zs2 = g.b.zs2;
-    if (!g.b.ptr || g.b.rows < g.N) return set_error(ALCM_E_INVALID, "ACT_T operand rows < N");
-  } else {
-    return set_error(ALCM_E_INVALID, "unknown B operand kind");
   }
   EpiDev& E = P.e;
   E.bias = g.bias; E.acc_scale = g.acc_scale; E.out_scale = g.out_scale; E.act = g.act;
@@ -844,87 +750,80 @@ int gemm(const alcm_gemm_args& g, hipStream_t s) {
   E.orpb = FastDiv((uint32_t)(g.out_rows_per_batch > 0 ? g.out_rows_per_batch : 1));
   E.out_step = g.out_step ? g.out_step : 1;
   E.out_off = g.out_off;
+  return P;
+}
 
-  const bool avec = act_vec_ok(g.a);
-  if (g.prec < PREC_BF16 || g.prec > PREC_F16) return set_error(ALCM_E_INVALID, "prec must be 0 (bf16), 1 (split) or 2 (f16)");
-  const int split = g.prec;  // precision code passed down to the launchers
-  const int N = g.N;
-  if (prof_enabled()) {
-    // algorithmic work of this launch: 2*M*N*K_real MACs; unique A rows, B operand, output (+residual/acc)
-    const double Kr = (double)g.a.ksize * g.a.C_in;
-    const double nb = (double)batch;
-    const double a_rows = (double)g.a.T_in * ((double)g.M / std::max(1, g.a.rows_per_batch));
-    double bbytes;
-    if (bkind == BK_W) bbytes = (double)N * g.Kpad * 2.0 * (split == PREC_SPLIT ? 2 : 1);
-    else if (bkind == BK_ACT) bbytes = nb * (double)g.b.T_in * g.b.C_in * 4.0;
-    else bbytes = nb * (double)g.b.rows * g.b.T_in * 4.0;
-    const double nout = g.geglu ? N / 2 : N;
-    const double obytes = nb * (double)g.M * nout * 4.0 * (1 + (g.res ? 1 : 0) + (g.accumulate ? 1 : 0));
-    g_cost.flops = 2.0 * nb * (double)g.M * N * Kr;
-    g_cost.bytes = nb * a_rows * g.a.C_in * 4.0 + bbytes + obytes;
+// The built instantiations: a plan that names none of them gets no kernel (an error, never another kernel).
+using GemmKern = void (*)(const GemmDev);
+using ConvKern = void (*)(const GemmDev, int, int);
+
+template <int BM, int BN, int WM, int WN, bool AVEC, int BKIND>
+static GemmKern gemm_prec(int prec) {
+  if (prec == PREC_SPLIT) return gemm_kernel<BM, BN, WM, WN, AVEC, BKIND, PREC_SPLIT>;
+  if (prec == PREC_F16) return gemm_kernel<BM, BN, WM, WN, AVEC, BKIND, PREC_F16>;
+  return gemm_kernel<BM, BN, WM, WN, AVEC, BKIND, PREC_BF16>;
+}
+template <int BM, int BN, int WM, int WN>
+static GemmKern gemm_w(const GemmPlan& pl) {
+  return pl.avec ? gemm_prec<BM, BN, WM, WN, true, BK_W>(pl.prec) : gemm_prec<BM, BN, WM, WN, false, BK_W>(pl.prec);
+}
+static GemmKern gemm_built(const GemmPlan& pl) {
+  const int bm = pl.BM, bn = pl.BN;
+  if (pl.family == GF_SKINNY) {
+    if (pl.prec == PREC_SPLIT) return gemm_skinny_kernel<PREC_SPLIT>;
+    if (pl.prec == PREC_F16) return gemm_skinny_kernel<PREC_F16>;
+    return gemm_skinny_kernel<PREC_BF16>;
   }
-  const bool window_conv = bkind == BK_W && avec && batch == 1 && g.a.ksize > 1 && g.a.Cpad % 32 == 0 &&
-                           g.a.C_in == g.a.Cpad && (g.a.ksize - 1) * g.a.dil <= HALO_MAX &&
-                           g.out_rows_per_batch == g.a.rows_per_batch && g.M % g.a.rows_per_batch == 0 &&
-                           !g.disable_window;
-  if (window_conv) {
-    const int nb = g.M / g.a.rows_per_batch, T_out = g.a.rows_per_batch;
-    // 64-wide N tiles when 128-wide tiles would waste a third of the MFMA work (N = 192, 320, ...)
-    const bool narrow = g.tile_n == 64 || (g.tile_n == 0 && (N <= 64 || (N % 128 != 0 && N % 64 == 0)));
-    const bool pro = g.a.pro_scale || g.a.pro_mean || g.a.pro_act;
-    if (narrow) {
-      if (pro) launch_conv_sp<128, 64, 4, 1, true>(P, nb, T_out, split, s);
-      else launch_conv_sp<128, 64, 4, 1, false>(P, nb, T_out, split, s);
-    } else {
-      if (pro) launch_conv_sp<128, 128, 2, 2, true>(P, nb, T_out, split, s);
-      else launch_conv_sp<128, 128, 2, 2, false>(P, nb, T_out, split, s);
-    }
-  } else if (bkind == BK_W && batch == 1 && g.M <= SK_MAXM && g.a.ksize == 1 && P.a.pad == 0 && P.a.up != 2 &&
-             !P.a.pm && !P.a.ps && !P.a.pact && !g.geglu && g.Kpad <= SK_KMAX && g.Kpad % 8 == 0 &&
-             g.a.sc == 1 && g.a.C_in % 4 == 0 && g.a.st % 4 == 0 && g.a.sb % 4 == 0 && (((uintptr_t)g.a.ptr) & 15) == 0 &&
-             knobs().gemm_skinny) {
-    // the embedder MLPs' M = B rows (gemm_skinny_kernel)
-    const dim3 grid((unsigned)((N + SK_N - 1) / SK_N), (unsigned)((g.M + SK_M - 1) / SK_M));
-    void* tok = prof_start(s);
-    if (split == PREC_SPLIT) hipLaunchKernelGGL((gemm_skinny_kernel<PREC_SPLIT>), grid, dim3(256), 0, s, P);
-    else if (split == PREC_F16) hipLaunchKernelGGL((gemm_skinny_kernel<PREC_F16>), grid, dim3(256), 0, s, P);
-    else hipLaunchKernelGGL((gemm_skinny_kernel<PREC_BF16>), grid, dim3(256), 0, s, P);
-    if (tok) {
-      char name[96];
-      std::snprintf(name, sizeof(name), "alcm::gemm_skinny_kernel<%d>", split);
-      if (knobs().prof_shapes)
-        std::snprintf(name + std::strlen(name), sizeof(name) - std::strlen(name), " M%d N%d K%d", g.M, N, g.Kpad);
-      prof_stop(tok, s, name, g_cost.flops, g_cost.bytes);
-    }
-  } else if (bkind == BK_W) {
-    // (N <= 32 on fewer than 128 tiles of 256 rows: 64-row tiles, 4x the workgroups — the DiT final layer, M = B T rows
-    // x N = 20: 39 -> 156 workgroups; the same K order per output, bit-identical)
-    if (N <= 32 && (int64_t)((g.M + 255) / 256) * batch < 128 && knobs().gemm_skinny) {
-      if (avec) launch_split<64, 32, 4, 1, true, BK_W>(P, batch, N, split, s);
-      else launch_split<64, 32, 4, 1, false, BK_W>(P, batch, N, split, s);
-    } else if (N <= 32) {
-      if (avec) launch_split<256, 32, 4, 1, true, BK_W>(P, batch, N, split, s);
-      else launch_split<256, 32, 4, 1, false, BK_W>(P, batch, N, split, s);
-    } else if (N <= 64) {
-      if (avec) launch_split<256, 64, 4, 1, true, BK_W>(P, batch, N, split, s);
-      else launch_split<256, 64, 4, 1, false, BK_W>(P, batch, N, split, s);
-    } else {
-      if (avec) launch_split<128, 128, 2, 2, true, BK_W>(P, batch, N, split, s);
-      else launch_split<128, 128, 2, 2, false, BK_W>(P, batch, N, split, s);
-    }
-  } else {
-    if (!avec) return set_error(ALCM_E_INVALID, "attention GEMM A operand must be vectorisable");
-    if (bkind == BK_ACT) {
-      if (N <= 64) launch_split<256, 64, 4, 1, true, BK_ACT>(P, batch, N, split, s);
-      else launch_split<128, 128, 2, 2, true, BK_ACT>(P, batch, N, split, s);
-    } else {
-      if (N <= 64) launch_split<256, 64, 4, 1, true, BK_ACTT>(P, batch, N, split, s);
-      else launch_split<128, 128, 2, 2, true, BK_ACTT>(P, batch, N, split, s);
-    }
+  if (pl.bkind == BK_W) {  //                                 BM   BN  WM WN
+    if (bm == 64 && bn == 32) return gemm_w<64, 32, 4, 1>(pl);
+    if (bm == 256 && bn == 32) return gemm_w<256, 32, 4, 1>(pl);
+    if (bm == 256 && bn == 64) return gemm_w<256, 64, 4, 1>(pl);
+    if (bm == 128 && bn == 128) return gemm_w<128, 128, 2, 2>(pl);
+  } else if (pl.avec && pl.bkind == BK_ACT) {
+    if (bm == 256 && bn == 64) return gemm_prec<256, 64, 4, 1, true, BK_ACT>(pl.prec);
+    if (bm == 128 && bn == 128) return gemm_prec<128, 128, 2, 2, true, BK_ACT>(pl.prec);
+  } else if (pl.avec) {
+    if (bm == 256 && bn == 64) return gemm_prec<256, 64, 4, 1, true, BK_ACTT>(pl.prec);
+    if (bm == 128 && bn == 128) return gemm_prec<128, 128, 2, 2, true, BK_ACTT>(pl.prec);
   }
+  return nullptr;
+}
+
+template <int BM, int BN, int WM, int WN, bool PRO>
+static ConvKern conv_prec(int prec) {
+  if (prec == PREC_SPLIT) return conv_kernel<BM, BN, WM, WN, PREC_SPLIT, PRO>;
+  if (prec == PREC_F16) return conv_kernel<BM, BN, WM, WN, PREC_F16, PRO>;
+  return conv_kernel<BM, BN, WM, WN, PREC_BF16, PRO>;
+}
+static ConvKern conv_built(const GemmPlan& pl) {
+  if (pl.BM == 128 && pl.BN == 64)
+    return pl.pro ? conv_prec<128, 64, 4, 1, true>(pl.prec) : conv_prec<128, 64, 4, 1, false>(pl.prec);
+  if (pl.BM == 128 && pl.BN == 128)
+    return pl.pro ? conv_prec<128, 128, 2, 2, true>(pl.prec) : conv_prec<128, 128, 2, 2, false>(pl.prec);
+  return nullptr;
+}
+
+static int launch_gemm(const GemmPlan& pl, const alcm_gemm_args& g, hipStream_t s) {
+  if (pl.family == GF_NONE) return 0;
+  const bool window = pl.family == GF_WINDOW_CONV;
+  const ConvKern ck = window ? conv_built(pl) : nullptr;
+  const GemmKern gk = window ? nullptr : gemm_built(pl);
+  if (!ck && !gk) return set_error(ALCM_E_INVALID, "gemm: the plan names no built instantiation");
+  const GemmDev P = fill_dev(pl, g);
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  void* tok = pl.name[0] ? prof_start(s) : nullptr;
+  if (window) hipLaunchKernelGGL(ck, grid, dim3(256), 0, s, P, pl.tpb, pl.T_out);
+  else hipLaunchKernelGGL(gk, grid, dim3(256), 0, s, P);
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(ALCM_E_HIP, std::string("gemm launch: ") + hipGetErrorString(e));
   return 0;
+}
+
+int gemm(const alcm_gemm_args& g, hipStream_t s) {
+  GemmPlan pl;
+  if (gemm_plan(g, knobs(), prof_enabled(), &pl)) return set_error(ALCM_E_INVALID, pl.err);
+  return launch_gemm(pl, g, s);
 }
 
 // ---------------------------------------------------------------- weight packing (device)
@@ -979,6 +878,19 @@ int pack_conv_weight(const float* w, int c_out, int c_in, int k, int cpad, int k
 extern "C" int alcm_gemm(const alcm_gemm_args* args, alcm_stream_t stream) {
   if (!args) return alcm::set_error(ALCM_E_INVALID, "null args");
   return alcm::gemm(*args, (hipStream_t)stream);
+}
+
+extern "C" int alcm_debug_gemm_plan(const alcm_gemm_args* args, alcm_gemm_plan_info* out) {
+  if (!args || !out) return alcm::set_error(ALCM_E_INVALID, "debug_gemm_plan: bad arguments");
+  alcm::GemmPlan pl;
+  if (alcm::gemm_plan(*args, alcm::knobs(), true, &pl)) return alcm::set_error(ALCM_E_INVALID, pl.err);
+  std::snprintf(out->name, sizeof(out->name), "%s", pl.name);
+  out->family = pl.family;
+  out->bm = pl.BM; out->bn = pl.BN; out->wm = pl.WM; out->wn = pl.WN;
+  out->grid[0] = pl.gx; out->grid[1] = pl.gy; out->grid[2] = pl.gz;
+  out->flops = pl.flops;
+  out->bytes = pl.bytes;
+  return 0;
 }
 
 extern "C" int alcm_pack_conv_weight(const float* w, int c_out, int c_in, int k, int cpad, int kpad, int transposed,

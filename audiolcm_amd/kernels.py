@@ -619,6 +619,12 @@ def conv_plan(args, ncu: int = 0, dense: bool = False) -> list:
     return _hip.debug_conv_plan(arr, len(args), _hip.PLAN_SUM, ncu)
 
 
+def gemm_plan(args: _hip.GemmArgs) -> dict:
+    """Which kernel an alcm_gemm call would launch: name = its profile row, family ("none" for M or N <= 0,
+    "window_conv", "skinny", "gemm"), bm, bn, wm, wn, grid, flops, bytes.  Launches nothing and needs no GPU."""
+    return _hip.debug_gemm_plan(args)
+
+
 def voc_stage_shapes(cfg) -> list:
     """The BigVGAN stages of a recipe.BigVGANConfig as the stage planner reads them (_hip.VocStageShape), as the
     library's loader derives them from the packed weights: phase weights of one shape, the tail convs' dense packing

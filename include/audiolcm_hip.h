@@ -455,6 +455,19 @@ typedef struct alcm_conv_plan_info {
 } alcm_conv_plan_info;
 int alcm_debug_conv_plan(const alcm_opconv_args* args, int n, int form, int ncu, alcm_conv_plan_info* out,
                          int* launches);
+/* diagnostics: what alcm_gemm would launch for these arguments under the current ALCM_* switches (alcm_gemmplan.h), or
+ * the ALCM_E* code the call itself would return (message in alcm_last_error()).  Host only: pointers are tested for
+ * null-ness and alignment, never dereferenced, nothing is launched and no device is needed.
+ * family: 0 nothing (M or N <= 0), 1 conv_kernel (window conv), 2 gemm_skinny_kernel, 3 gemm_kernel; name: the profile
+ * row; bm, bn, wm, wn: tile and wave grid (skinny: rows / columns per workgroup); grid: workgroups in x, y, z. */
+typedef struct alcm_gemm_plan_info {
+  char name[128];
+  int family;
+  int bm, bn, wm, wn;
+  int grid[3];
+  double flops, bytes; /* the cost the profile row is charged */
+} alcm_gemm_plan_info;
+int alcm_debug_gemm_plan(const alcm_gemm_args* args, alcm_gemm_plan_info* out);
 /* The BigVGAN stage planner (alcm_vocplan.h).  A stage's static shape: the upsampler ConvTranspose1d cin -> cout
  * at `rate` as `rate` phase convs of `taps` taps on input rows padded to `cpad` channels, and nrb AMPBlock1 resblocks of
  * kernel size rb_k[j] with the ndil dilations dil[] (one set for the stage's resblocks). */

@@ -20,6 +20,7 @@ static Knobs read_knobs() {
   k.wconv = env_int("ALCM_WCONV", 8);
   k.wconv3 = env_int("ALCM_WCONV3", -1);
   k.wconv3_grid = env_int("ALCM_WCONV3_GRID", 0);
+  k.ups2_grid = env_int("ALCM_UPS2_GRID", 0);
   k.nconv = env_int("ALCM_NCONV", -1);
   k.opconv_tile = env_int("ALCM_OPCONV_TILE", 0);
   k.serial_resblocks = env_set("ALCM_SERIAL_RESBLOCKS");

@@ -1265,7 +1265,9 @@ struct VocWs {
   VocChain ch[3];
 };
 static size_t voc_elems(const VocW& G, int M) {
-  size_t big = (size_t)M * G.c0;
+  // (conv_pre stages the channels-last mel, rows of its padded input channels, in a chain buffer: wider than c0
+  // only in a config cut down below 96 channels)
+  size_t big = (size_t)M * std::max(G.c0, G.pre.w.cpad);
   int T = M;
   for (const StageW& S : G.st) {
     T *= S.rate;

@@ -207,7 +207,10 @@ int ups2(const float* x, float* out, int B, int T, int cin, int cout, const u16*
   const int64_t nt = (int64_t)B * P.tiles_per_batch;
   if (nt >= (1ll << 30)) return set_error(ALCM_E_INVALID, "ups2: problem too large");
   P.ntiles = (int)nt;
-  const int grid = (int)std::min<int64_t>(nt, (int64_t)device_cus() * (cin == 96 ? UpsGeo<96, 48>::OCC : UpsGeo<48, 32>::OCC));
+  int grid = (int)std::min<int64_t>(nt, (int64_t)device_cus() * (cin == 96 ? UpsGeo<96, 48>::OCC : UpsGeo<48, 32>::OCC));
+  // tests: fewer workgroups, so each walks several tiles (workgroup g takes tiles g, g + grid, ...: the same tiles,
+  // each computed the same way, so the output is bit-identical at any cap)
+  if (knobs().ups2_grid > 0) grid = std::min(grid, knobs().ups2_grid);
   void* tok = prof_start(s);
   if (cin == 96) hipLaunchKernelGGL((ups2_kernel<96, 48, 96>), dim3(grid), dim3(512), 0, s, P);
   else hipLaunchKernelGGL((ups2_kernel<48, 32, 48>), dim3(grid), dim3(512), 0, s, P);

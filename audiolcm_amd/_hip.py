@@ -121,6 +121,9 @@ _SIGS = [
                                      C.c_int, vp]),
     ("alcm_lcm_step_joint", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, fp,
                                       fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_lcm_step_ring", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, fp,
+                                     fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_wave_loop", C.c_int, [fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, vp]),
     ("alcm_latent_init", C.c_int, [fp, fp, fp, C.c_float, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp,
                                    C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_paste", C.c_int, [fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp]),

@@ -76,6 +76,24 @@ def frame_samples_of(rate: int) -> int:
     return F
 
 
+def loop_multiple(rate: int) -> int:
+    """The latent frames a loop's period and halo are a multiple of at ``rate``, so that both are whole numbers of
+    output samples: a frame is 512 * rate / 16000 = 4 * rate / 125 samples, hence 125 / gcd(125, rate) frames (1 at
+    16, 32, 48 and 96 kHz, 5 at 44.1 and 22.05 kHz)."""
+    return 125 // math.gcd(125, int(rate))
+
+
+def loop_frames(duration_s: float, out_sample_rate: Optional[int] = None) -> int:
+    """The period of a loop of ``duration_s`` seconds in latent frames: the smallest L >= ceil(duration_s * 16000 /
+    512) (at least 2: a ring has two windows) that is a multiple of ``loop_multiple(out_sample_rate or 16000)``.  The
+    period is never cropped to ``duration_s``: a crop would cut the seam."""
+    if not duration_s > 0:
+        raise ValueError("duration_s must be positive")
+    m = loop_multiple(SAMPLE_RATE if out_sample_rate is None else out_sample_rate)
+    need = max(2, math.ceil(duration_s * SAMPLE_RATE / FRAME_SAMPLES))
+    return -(-need // m) * m
+
+
 def check_native_keep_original(path: str, rate: int, channels: int, out_sample_rate: Optional[int]) -> int:
     """What a keep-original edit of a file needs; returns the samples F of one latent frame at the file's rate."""
     if channels != 1:

@@ -44,8 +44,8 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .audio_in import (FRAME_SAMPLES, SAMPLE_RATE, EditPlan, check_level, check_out_rate, finish_output, parse_spans,
-                       plan_edit)
+from .audio_in import (FRAME_SAMPLES, SAMPLE_RATE, EditPlan, check_level, check_out_rate, fade_samples_of,
+                       finish_output, loop_frames, loop_multiple, parse_spans, plan_edit)
 from .config import instantiate_from_config, load_config
 from .infer_api import build_models, struct_caption
 from .lcm import LCMSampler
@@ -103,6 +103,11 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--long-joint", action="store_true",
                    help="with --duration: denoise the windows jointly, one DiT call per clip and LCM step (DESIGN.md §5)")
+    p.add_argument("--loop", action="store_true",
+                   help="write clips that loop without a seam: one period of --duration seconds (rounded up to whole "
+                        "latent frames), or of --W frames without --duration (DESIGN.md §5)")
+    p.add_argument("--loop-fade-ms", type=float, default=32.0,
+                   help="with --loop: the fade that closes the seam at the start of the period")
     p.add_argument("--test-dataset-tsv", type=str, default=None, help="override the config's test_dataset tsv_path")
     return p.parse_args(argv)
 
@@ -137,6 +142,12 @@ class GenSamples:
         if self.plan is not None:
             wav, rate, mel = self.pipeline.run_edit(self.plan, c, seeds, self.opt.strength)
             return mel, wav, self.opt.sample_rate if label and not self.plan.native else rate, self.plan.pcm_scale
+        if self.opt.loop:
+            out = self.pipeline.generate_loop(c, seeds, loop_period(self.opt), out_sample_rate=self.opt.out_sample_rate,
+                                              fade_samples=fade_samples_of(self.opt.loop_fade_ms,
+                                                                           self.opt.out_sample_rate or SAMPLE_RATE),
+                                              level=self.level)
+            return out["mel"], out["wav"], self.opt.sample_rate if label else out["rate"], 32767.0
         if self.opt.duration is not None:
             out = self.pipeline.generate_long(c, seeds, math.ceil(self.opt.duration * SAMPLE_RATE / FRAME_SAMPLES),
                                               joint=self.opt.long_joint)
@@ -189,7 +200,24 @@ class GenSamples:
         return [r for rs in records for r in rs]
 
 
+def loop_period(opt) -> int:
+    """The period of ``--loop`` in latent frames: ``--duration`` rounded up (``audio_in.loop_frames``), else ``--W``."""
+    if opt.duration is not None:
+        return loop_frames(opt.duration, opt.out_sample_rate)
+    return opt.W
+
+
 def build(opt):
+    if opt.loop:
+        if opt.init_audio or opt.inpaint or opt.keep_original:
+            raise ValueError("--loop generates from text: it does not combine with --init-audio, --inpaint or "
+                             "--keep-original")
+        if opt.loop_fade_ms < 0:
+            raise ValueError("--loop-fade-ms must not be negative")
+        mult = loop_multiple(check_out_rate(opt.out_sample_rate) or SAMPLE_RATE)
+        if loop_period(opt) < 2 or loop_period(opt) % mult:
+            raise ValueError(f"--loop without --duration: the period of --W {opt.W} frames must be at least 2 and, at "
+                             f"this output rate, a multiple of {mult}")
     if opt.plms:
         raise NotImplementedError("--plms: the teacher PLMS sampler is outside the LCM hot path (and calls the 3-arg "
                                   "apply_model, plms.py:185, which LCM_audio does not have)")
@@ -202,7 +230,7 @@ def build(opt):
         raise ValueError("--mask-spans is used with --inpaint")
     if opt.init_audio and opt.duration is not None:
         raise ValueError("--init-audio and --duration do not combine")
-    if opt.long_joint and opt.duration is None:
+    if opt.long_joint and opt.duration is None and not opt.loop:
         raise ValueError("--long-joint is used with --duration")
     if opt.resample and not opt.init_audio:
         raise ValueError("--resample is used with --init-audio")

@@ -53,6 +53,11 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
 int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
                    const float* coeffs, const int* starts, int K, const float* wn, float* prev, float* den, float* xw,
                    int B, int C, int L, int W, hipStream_t s);
+int lcm_step_ring(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                  const float* coeffs, const int* starts, int K, const float* wn, float* prev, float* den, float* xw,
+                  int B, int C, int L, int W, hipStream_t s);
+int wave_loop(const float* ext, const float* ramp, float* out, int B, int64_t Next, int64_t start, int64_t N, int R,
+              hipStream_t s);
 int latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
                 const float* mask, float sa, float sb, float sa_r, float sb_r, float* z0_out, float* x_out, int B,
                 int C, int T, hipStream_t s);

@@ -583,6 +583,10 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
 // frames of one access share their covering windows.  The starts travel by value in the kernel's arguments (the window
 // index is uniform, so each is a scalar load).  No atomics: an element's value is one fixed chain, whatever B, the grid
 // or V.
+// Ring = true (lcm_step_ring) closes the line into a ring of L frames: window k covers frame t at the offset
+// t - s_k, plus L when that is negative, if it is below W (W <= L: a window covers a frame at most once).  The chain
+// is the same one in ascending k, and with V = 4 an access never straddles the wrap (L, W and the starts are multiples
+// of 4).
 constexpr int kJointMaxWin = 32;
 struct JointStarts {
   int s[kJointMaxWin];
@@ -592,8 +596,14 @@ __device__ __forceinline__ float joint_first(float w, float d) {
   const float a = w * d;
   return a;
 }
+// the offset of frame t in a window that starts at s: negative or >= W when the window does not cover t
+template <bool Ring>
+__device__ __forceinline__ int window_offset(int t, int s, int L) {
+  const int o = t - s;
+  return Ring && o < 0 ? o + L : o;
+}
 
-template <int V>
+template <int V, bool Ring>
 __global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
     const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg,
     const float* __restrict__ noise, StepCoeffs k, JointStarts st, int K, const float* __restrict__ wn,
@@ -612,7 +622,7 @@ __global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
     }
     int cover = 0;
     for (int kk = 0; kk < K; ++kk) {
-      const int o = w.t - st.s[kk];
+      const int o = window_offset<Ring>(w.t, st.s[kk], L);
       if (o < 0 || o >= W) continue;
       const FVec<V> wv = FVec<V>::ld(wn + (int64_t)kk * W + o);
       const int64_t e0 = (((int64_t)kk * B + w.b) * C + w.c0) * W + o;
@@ -650,7 +660,7 @@ __global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
     }
     if (xw) {
       for (int kk = 0; kk < K; ++kk) {
-        const int o = w.t - st.s[kk];
+        const int o = window_offset<Ring>(w.t, st.s[kk], L);
         if (o < 0 || o >= W) continue;
         const int64_t e0 = (((int64_t)kk * B + w.b) * C + w.c0) * W + o;
 #pragma unroll
@@ -662,7 +672,7 @@ __global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
 }
 
 // the windows of the first step, cut from x: xw[k * B + b, c, t - s_k] = x[b, c, t] for every covering k
-template <int V>
+template <int V, bool Ring>
 __global__ __launch_bounds__(kEditBlock) void joint_gather_kernel(const float* __restrict__ x, JointStarts st, int K,
                                                                   float* __restrict__ xw, int B, int C, int L, int W,
                                                                   int64_t items) {
@@ -675,7 +685,7 @@ __global__ __launch_bounds__(kEditBlock) void joint_gather_kernel(const float* _
     for (int j = 0; j < kEditCh; ++j)
       if (j < nch) xv[j] = FVec<V>::ld(x + o0 + (int64_t)j * L);
     for (int kk = 0; kk < K; ++kk) {
-      const int o = w.t - st.s[kk];
+      const int o = window_offset<Ring>(w.t, st.s[kk], L);
       if (o < 0 || o >= W) continue;
       const int64_t e0 = (((int64_t)kk * B + w.b) * C + w.c0) * W + o;
 #pragma unroll
@@ -685,29 +695,39 @@ __global__ __launch_bounds__(kEditBlock) void joint_gather_kernel(const float* _
   }
 }
 
-int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
-                   const int* starts, int K, const float* wn, float* prev, float* den, float* xw, int B, int C, int L,
-                   int W, hipStream_t s) {
-  if (!x || !wn || !c || !starts) return set_error(ALCM_E_INVALID, "lcm_step_joint: null x, wn, coeffs or starts");
-  if (!prev && !den && !xw) return set_error(ALCM_E_INVALID, "lcm_step_joint: no output");
+// The host side of both forms.  `fn` names the entry in the errors; the open form's plan rules are those of
+// pipeline.joint_weights and the ring's those of pipeline.ring_weights, checked before any launch.
+template <bool Ring>
+static int step_windows(const char* fn, const float* x, const float* eps, const float* eps_u, float cfg,
+                        const float* noise, const float* c, const int* starts, int K, const float* wn, float* prev,
+                        float* den, float* xw, int B, int C, int L, int W, hipStream_t s) {
+  const std::string f = std::string(fn) + ": ";
+  if (!x || !wn || !c || !starts) return set_error(ALCM_E_INVALID, f + "null x, wn, coeffs or starts");
+  if (!prev && !den && !xw) return set_error(ALCM_E_INVALID, f + "no output");
   if (!eps && (eps_u || noise || prev || den || !xw))
-    return set_error(ALCM_E_INVALID, "lcm_step_joint: without eps only x is gathered into xw");
-  if (B < 0 || C < 0 || L < 0 || W < 0) return set_error(ALCM_E_INVALID, "lcm_step_joint: negative B, C, L or W");
-  if (K < 1 || K > kJointMaxWin) return set_error(ALCM_E_INVALID, "lcm_step_joint: K outside 1 .. 32");
+    return set_error(ALCM_E_INVALID, f + "without eps only x is gathered into xw");
+  if (B < 0 || C < 0 || L < 0 || W < 0) return set_error(ALCM_E_INVALID, f + "negative B, C, L or W");
+  if (K < (Ring ? 2 : 1) || K > kJointMaxWin)
+    return set_error(ALCM_E_INVALID, f + (Ring ? "K outside 2 .. 32" : "K outside 1 .. 32"));
   if (B == 0 || C == 0 || L == 0 || W == 0) return 0;
-  // the window plan: the same conditions as pipeline.joint_weights
+  if (Ring && W > L) return set_error(ALCM_E_INVALID, f + "a window longer than the ring");
   JointStarts st = {};
   bool mult4 = true;
   for (int i = 0; i < K; ++i) {
     st.s[i] = starts[i];
     mult4 = mult4 && starts[i] % 4 == 0;
     if (i == 0 ? starts[0] != 0 : starts[i] <= starts[i - 1])
-      return set_error(ALCM_E_INVALID, "lcm_step_joint: starts must begin at 0 and ascend strictly");
+      return set_error(ALCM_E_INVALID, f + "starts must begin at 0 and ascend strictly");
     if (i > 0 && (int64_t)starts[i] > (int64_t)starts[i - 1] + W)
-      return set_error(ALCM_E_INVALID, "lcm_step_joint: a gap between two windows");
+      return set_error(ALCM_E_INVALID, f + "a gap between two windows");
   }
-  if ((int64_t)starts[K - 1] + W != L)
-    return set_error(ALCM_E_INVALID, "lcm_step_joint: the last window must end at L");
+  if (Ring) {
+    if (starts[K - 1] >= L) return set_error(ALCM_E_INVALID, f + "a window starts past the ring");
+    if ((int64_t)starts[K - 1] + W < L)
+      return set_error(ALCM_E_INVALID, f + "a gap between the last window and the first");
+  } else if ((int64_t)starts[K - 1] + W != L) {
+    return set_error(ALCM_E_INVALID, f + "the last window must end at L");
+  }
   StepCoeffs k{c[0], c[1], c[2], c[3], c[4], c[5]};
   const bool vec = mult4 && L % 4 == 0 && W % 4 == 0 && aligned16({x, eps, eps_u, noise, wn, prev, den, xw});
   const int64_t items = edit_items(B, C, L, vec);
@@ -715,26 +735,43 @@ int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float c
   const double nl = (double)B * C * L, nw = (double)K * B * C * W;
   void* tok = prof_start(s);
   if (!eps) {
-    if (vec) hipLaunchKernelGGL(joint_gather_kernel<4>, grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
-    else hipLaunchKernelGGL(joint_gather_kernel<1>, grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
-    prof_stop(tok, s, vec ? "alcm::joint_gather_kernel<4>" : "alcm::joint_gather_kernel<1>", 0.0, 4.0 * (nl + nw));
+    if (vec) hipLaunchKernelGGL((joint_gather_kernel<4, Ring>), grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
+    else hipLaunchKernelGGL((joint_gather_kernel<1, Ring>), grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
+    prof_stop(tok, s,
+              Ring ? (vec ? "alcm::ring_gather_kernel<4>" : "alcm::ring_gather_kernel<1>")
+                   : (vec ? "alcm::joint_gather_kernel<4>" : "alcm::joint_gather_kernel<1>"),
+              0.0, 4.0 * (nl + nw));
     ALCM_HIP(hipGetLastError());
     return 0;
   }
   if (vec)
-    hipLaunchKernelGGL(lcm_step_joint_kernel<4>, grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev, den, xw,
-                       B, C, L, W, items);
+    hipLaunchKernelGGL((lcm_step_joint_kernel<4, Ring>), grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev,
+                       den, xw, B, C, L, W, items);
   else
-    hipLaunchKernelGGL(lcm_step_joint_kernel<1>, grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev, den, xw,
-                       B, C, L, W, items);
+    hipLaunchKernelGGL((lcm_step_joint_kernel<1, Ring>), grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev,
+                       den, xw, B, C, L, W, items);
   // the window tensors (eps, eps_u, xw) count K * B * C * W elements and the long ones (x, noise, prev, den) B * C * L; the
   // weights once per window, frame and channel group; per window element the step (8) and one multiply-add
-  prof_stop(tok, s, vec ? "alcm::lcm_step_joint_kernel<4>" : "alcm::lcm_step_joint_kernel<1>",
+  prof_stop(tok, s,
+            Ring ? (vec ? "alcm::lcm_step_ring_kernel<4>" : "alcm::lcm_step_ring_kernel<1>")
+                 : (vec ? "alcm::lcm_step_joint_kernel<4>" : "alcm::lcm_step_joint_kernel<1>"),
             10.0 * nw + (noise ? 3.0 * nl : 0.0),
             4.0 * (nl * (1 + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0)) +
                    nw * (1 + (eps_u ? 1 : 0) + (xw ? 1 : 0)) + (double)K * W * B * ((C + kEditCh - 1) / kEditCh)));
   ALCM_HIP(hipGetLastError());
   return 0;
+}
+
+int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
+                   const int* starts, int K, const float* wn, float* prev, float* den, float* xw, int B, int C, int L,
+                   int W, hipStream_t s) {
+  return step_windows<false>("lcm_step_joint", x, eps, eps_u, cfg, noise, c, starts, K, wn, prev, den, xw, B, C, L, W, s);
+}
+
+int lcm_step_ring(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
+                  const int* starts, int K, const float* wn, float* prev, float* den, float* xw, int B, int C, int L,
+                  int W, hipStream_t s) {
+  return step_windows<true>("lcm_step_ring", x, eps, eps_u, cfg, noise, c, starts, K, wn, prev, den, xw, B, C, L, W, s);
 }
 
 // z0 = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0) from the encoder's (B, 2C, T) moments (the posterior mode
@@ -955,6 +992,65 @@ int wave_paste(const float* orig, const float* gen, const float* mask, const flo
   return 0;
 }
 
+// ---------------------------------------------------------------- loop crop and seam close
+// One period of N samples cut from a longer decode ext (B, Next) of the same ring, which goes on past the period's end
+// with the period's start rendered once more: out[n] = ext[start + n] from n = R on, out[0] = ext[start + N] (the sample
+// that follows out[N - 1] in ext, so the wrap is an adjacent pair of one waveform), and for 0 < n < R the fade
+// a + ramp[n] * (b - a) from the continuation b = ext[start + N + n] to the clip's own a = ext[start + n], in
+// wave_paste's fma form on wave_paste's table.  R = 0: a plain crop.  One item is V samples of one clip (V = 4 with
+// 16-byte accesses when start, N, Next and the pointers allow, else 1); the ramp is read by element, so R is free.
+constexpr int kLoopBlock = 256;
+constexpr int kLoopMaxBlocks = 4096;
+
+template <int V>
+__global__ __launch_bounds__(kLoopBlock) void wave_loop_kernel(const float* __restrict__ ext,
+                                                               const float* __restrict__ ramp, float* __restrict__ out,
+                                                               int64_t Next, int64_t start, int64_t N, int R,
+                                                               int64_t items) {
+  const int64_t per = N / V;
+  for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = it / per, n = (it - b * per) * V;
+    const float* row = ext + b * Next + start;
+    FVec<V> a = FVec<V>::ld(row + n);
+    if (n < R) {  // n + N + V - 1 < Next: start + N + R <= Next, and with V = 4 all three are multiples of 4
+      const FVec<V> c = FVec<V>::ld(row + N + n);
+#pragma unroll
+      for (int i = 0; i < V; ++i) {
+        const int64_t m = n + i;
+        if (m == 0) a.v[i] = c.v[i];
+        else if (m < R) a.v[i] = fmaf(ramp[m], c.v[i] - a.v[i], a.v[i]);
+      }
+    }
+    a.st(out + b * N + n);
+  }
+}
+
+int wave_loop(const float* ext, const float* ramp, float* out, int B, int64_t Next, int64_t start, int64_t N, int R,
+              hipStream_t s) {
+  if (!ext || !out) return set_error(ALCM_E_INVALID, "wave_loop: null ext or out");
+  if (B < 0 || Next < 0 || N < 0 || R < 0) return set_error(ALCM_E_INVALID, "wave_loop: negative B, row length, N or R");
+  if (start < 0) return set_error(ALCM_E_INVALID, "wave_loop: negative start");
+  if (R > N) return set_error(ALCM_E_INVALID, "wave_loop: R exceeds N");
+  if (start > Next || N > Next - start || R > Next - start - N)
+    return set_error(ALCM_E_INVALID, "wave_loop: start + N + R reaches past the row");
+  if (R > 1 && !ramp) return set_error(ALCM_E_INVALID, "wave_loop: null ramp");
+  if (B == 0 || N == 0) return 0;
+  const bool vec = start % 4 == 0 && N % 4 == 0 && Next % 4 == 0 && aligned16({ext, out});
+  const int64_t items = (int64_t)B * (vec ? N / 4 : N);
+  const int blocks = (int)std::min<int64_t>((items + kLoopBlock - 1) / kLoopBlock, kLoopMaxBlocks);
+  void* tok = prof_start(s);
+  if (vec)
+    hipLaunchKernelGGL(wave_loop_kernel<4>, dim3(blocks), dim3(kLoopBlock), 0, s, ext, ramp, out, Next, start, N, R, items);
+  else
+    hipLaunchKernelGGL(wave_loop_kernel<1>, dim3(blocks), dim3(kLoopBlock), 0, s, ext, ramp, out, Next, start, N, R, items);
+  // per sample one read and one write; per sample of the fade the continuation and the ramp too, and 3 FLOPs
+  const double fade = (double)B * (R > 0 ? R - 1 : 0);
+  prof_stop(tok, s, vec ? "alcm::wave_loop_kernel<4>" : "alcm::wave_loop_kernel<1>", 3.0 * fade,
+            4.0 * (2.0 * B * N + 2.0 * fade + (R > 0 ? B : 0)));
+  ALCM_HIP(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------- sinusoidal embeddings
 // freqs[] is the reference's own fp32 frequency table (computed on the host exactly as
 // scheduling_lcm.py:103-105 / concatDiT.py:60-62 do), so the only device math is t*f and sin/cos.
@@ -1081,6 +1177,17 @@ extern "C" int alcm_lcm_step_joint(const float* x, const float* eps_cond, const 
                                    alcm_stream_t stream) {
   return alcm::lcm_step_joint(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, prev_out, denoised_out,
                               xw_out, B, C, L, W, (hipStream_t)stream);
+}
+extern "C" int alcm_lcm_step_ring(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                                  const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
+                                  float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
+                                  alcm_stream_t stream) {
+  return alcm::lcm_step_ring(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, prev_out, denoised_out,
+                             xw_out, B, C, L, W, (hipStream_t)stream);
+}
+extern "C" int alcm_wave_loop(const float* ext, const float* ramp, float* out, int B, int64_t row_len, int64_t start,
+                              int64_t N, int R, alcm_stream_t stream) {
+  return alcm::wave_loop(ext, ramp, out, B, row_len, start, N, R, (hipStream_t)stream);
 }
 extern "C" int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, float scale,
                                 const float* noise, const float* mask, float sa, float sb, float sa_r, float sb_r,

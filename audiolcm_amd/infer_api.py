@@ -19,8 +19,8 @@ import torch
 from . import recipe
 from .audio_in import (FRAME_SAMPLES, SAMPLE_RATE, EditPlan, Level, check_level,  # noqa: F401
                        check_native_keep_original, check_out_rate, fade_samples_of, finish_output, keep_original_mask,
-                       load_init_audio, load_init_audio_whole, load_native_audio, parse_spans, plan_edit, spans_to_mask,
-                       to_out_rate)
+                       load_init_audio, load_init_audio_whole, load_native_audio, loop_frames, parse_spans, plan_edit,
+                       spans_to_mask, to_out_rate)
 from .ckpt import load_checkpoint, state_dict_of
 from .config import instantiate_from_config, load_config
 from .lcm import LCM_audio, LCMSampler
@@ -221,17 +221,25 @@ def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: st
                       synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
                       seed: Optional[int] = None, out_sample_rate: Optional[int] = None, joint: bool = False,
                       loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-                      true_peak: bool = False) -> str:
+                      true_peak: bool = False, loop: bool = False, loop_fade_ms: float = 32.0) -> str:
     """A clip of ceil(duration_s * 16000 / 512) latent frames by long-form continuation
     (``AudioLCMPipeline.generate_long``).  ``seed`` None draws the clip's base seed from the global RNG.
     ``joint``: the windows are denoised jointly, one DiT call per LCM step (``generate_long(joint=True)``).
     ``out_sample_rate``: the clip is resampled from 16 kHz to that rate on the GPU, cropped to
     round(duration_s * out_sample_rate) samples and written under that rate (without it the file keeps every sample
     of the last latent frame, as before).  ``loudness``, ``peak_dbfs``, ``true_peak``: the level of the output, as
-    ``AudioLCMBatchInfer``, measured at the output rate on the cropped clip.  Returns the WAV path."""
+    ``AudioLCMBatchInfer``, measured at the output rate on the cropped clip.
+    ``loop``: the clip loops without a seam (``AudioLCMPipeline.generate_loop``): the latent is denoised on a ring and
+    decoded with a circular halo, and a fade of ``loop_fade_ms`` at the start of the period closes what is left.  The
+    period is ``audio_in.loop_frames(duration_s, out_sample_rate)`` latent frames: ``duration_s`` rounded up to whole
+    frames, and to a multiple of 5 frames at 44.1 and 22.05 kHz.  The file holds exactly one period at the output rate
+    and is never cropped to ``duration_s``: a crop would cut the seam.  ``joint`` is then redundant.
+    Returns the WAV path."""
     from .pipeline import AudioLCMPipeline
     check_out_rate(out_sample_rate)
     level = check_level(loudness, peak_dbfs, true_peak)
+    if loop and loop_fade_ms < 0:
+        raise ValueError("loop_fade_ms must not be negative")
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split)
     latent_len = math.ceil(duration_s * SAMPLE_RATE / FRAME_SAMPLES)
     if latent_len < 1:
@@ -242,9 +250,15 @@ def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: st
     os.makedirs(outpath, exist_ok=True)
     with torch.no_grad():
         c = model.get_learned_conditioning({"ori_caption": [ori_prompt], "struct_caption": [struct_caption(ori_prompt)]})
-        n_out = None if out_sample_rate is None else int(round(duration_s * out_sample_rate))
-        wav, rate = finish_output(pipe.generate_long(c, [base], latent_len, joint=joint)["wav"], out_sample_rate, level,
-                                  n_out)
+        if loop:
+            out = pipe.generate_loop(c, [base], loop_frames(duration_s, out_sample_rate), level=level,
+                                     out_sample_rate=out_sample_rate,
+                                     fade_samples=fade_samples_of(loop_fade_ms, out_sample_rate or SAMPLE_RATE))
+            wav, rate = out["wav"], out["rate"]
+        else:
+            n_out = None if out_sample_rate is None else int(round(duration_s * out_sample_rate))
+            wav, rate = finish_output(pipe.generate_long(c, [base], latent_len, joint=joint)["wav"], out_sample_rate,
+                                      level, n_out)
         wav = wav.cpu().numpy()
     path = os.path.join(outpath, wav_name_for(ori_prompt) + "_0.wav")
     write_pcm16(path, wav[0], rate)

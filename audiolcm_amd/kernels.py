@@ -343,13 +343,15 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
                    wn: torch.Tensor, eps_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
                    want_prev: bool = True, want_den: bool = True, want_xw: bool = True,
                    prev: Optional[torch.Tensor] = None, den: Optional[torch.Tensor] = None,
-                   xw: Optional[torch.Tensor] = None):
+                   xw: Optional[torch.Tensor] = None, ring: bool = False):
     """``lcm_step`` on one long latent ``x`` (B, C, L) whose K overlapping windows of W frames at ``starts`` went through
     the DiT as one batch: ``eps`` (K * B, C, W), row k * B + b.  Where windows overlap their denoised estimates are
     averaged with the normalised weights ``wn`` (K, W) (``pipeline.joint_weights``); a frame under one window is the
     plain step bit for bit (alcm_lcm_step_joint).  Returns (prev, denoised, xw): the two (B, C, L) results and prev
     gathered back into window layout (K * B, C, W), the next DiT input; a result not wanted is None, ``prev`` / ``den``
-    / ``xw`` give the tensors to write.  ``eps`` None: only x itself is gathered into xw.  One launch."""
+    / ``xw`` give the tensors to write.  ``eps`` None: only x itself is gathered into xw.  One launch.
+    ``ring``: the L frames are a ring (alcm_lcm_step_ring): window k covers frame t at the offset (t - starts[k]) mod L
+    when that is below W, and ``wn`` is ``pipeline.ring_weights``."""
     B, Cc, L = x.shape
     K, W = wn.shape
     assert len(starts) == K and x.is_contiguous() and wn.is_contiguous()
@@ -367,8 +369,9 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
         xw = torch.empty((K * B, Cc, W), device=x.device, dtype=torch.float32)
     arr = (C.c_float * 6)(*[float(c) for c in coeffs])
     st = (C.c_int * K)(*[int(s) for s in starts])
-    check(lib().alcm_lcm_step_joint(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K, ptr(wn),
-                                    ptr(prev), ptr(den), ptr(xw), B, Cc, L, W, stream_handle()), "lcm_step_joint")
+    entry = lib().alcm_lcm_step_ring if ring else lib().alcm_lcm_step_joint
+    check(entry(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K, ptr(wn), ptr(prev), ptr(den),
+                ptr(xw), B, Cc, L, W, stream_handle()), "lcm_step_ring" if ring else "lcm_step_joint")
     return prev, den, xw
 
 
@@ -426,6 +429,25 @@ def wave_paste(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_st
     check(lib().alcm_wave_paste(ptr(orig), ptr(gen), ptr(mask), ptr(ramp), ptr(out), B, N, int(gen_start),
                                 gen.shape[1], mask.shape[1], int(frame_samples), int(fade_samples), stream_handle()),
           "wave_paste")
+    return out
+
+
+def wave_loop(ext: torch.Tensor, start: int, N: int, fade_samples: int = 0) -> torch.Tensor:
+    """One period of a looping clip from ``ext`` (B, Next), the decode of the ring's latent padded circularly: the N
+    samples from ``start`` on, with the seam closed over the first R = ``fade_samples`` of them (alcm_wave_loop).
+    out[n] = ext[start + n] bit for bit from n = R on; out[0] = ext[start + N] bit for bit, the sample that follows the
+    period's last one in ``ext``; for 0 < n < R a fade from that continuation to the period's own start,
+    fmaf(ramp[n], ext[start + N + n] - ext[start + n], ext[start + n]) with ``paste_ramp(R)``.  R = 0 is a plain crop.
+    ValueError unless start >= 0, R <= N and start + N + R <= Next.  One launch."""
+    start, N, R = int(start), int(N), int(fade_samples)
+    assert ext.dim() == 2 and ext.is_cuda and ext.dtype == torch.float32 and ext.is_contiguous()
+    B, Next = ext.shape
+    if start < 0 or N < 0 or not 0 <= R <= N or start + N + R > Next:
+        raise ValueError(f"wave_loop: need start >= 0, 0 <= fade_samples <= N and start + N + fade_samples <= {Next}, "
+                         f"got start {start}, N {N}, fade_samples {R}")
+    out = torch.empty((B, N), device=ext.device, dtype=torch.float32)
+    ramp = paste_ramp(R, ext.device) if R > 0 else None
+    check(lib().alcm_wave_loop(ptr(ext), ptr(ramp), ptr(out), B, Next, start, N, R, stream_handle()), "wave_loop")
     return out
 
 

@@ -281,7 +281,7 @@ class LCMSampler:
                      noise: Optional[torch.Tensor] = None, guidance_scale=5., original_inference_steps=50,
                      unconditional_conditioning: Optional[torch.Tensor] = None,
                      unconditional_guidance_scale: float = 1.0,
-                     clips_per_call: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+                     clips_per_call: int = 1, ring: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """Joint long-form sampling: S LCM steps on one latent of ``length`` frames covered by the K windows of
         ``window`` frames at ``starts`` (``AudioLCMPipeline.long_windows``).  Every step runs the DiT on all windows of
         all clips (K * B rows, row k * B + b; [uc; c] doubled with guidance as in ``sample``) and then one
@@ -299,15 +299,20 @@ class LCMSampler:
         RNG: with ``seeds`` ``recipe.prompt_noise(seeds, S, C, length)``, per prompt at the clip's whole length (a clip
         does not depend on its batch; with one window these are ``sample``'s draws and the result is ``sample``'s bit
         for bit); ``x_T`` / ``noise`` replace the respective draw; without seeds the global device RNG.
+
+        ``ring``: the ``length`` frames are a ring (seamless loops): window k covers the frames (starts[k] + j) mod
+        length, the plan is ``pipeline.ring_weights`` (at least two windows: ``AudioLCMPipeline.loop_windows``) and the
+        step alcm_lcm_step_ring.  Each window is still an ordinary DiT call on ``window`` frames, and everything else is
+        as above; rotating ``x_T`` and ``noise`` by a multiple of the windows' spacing rotates the result.
         Returns (denoised, last sample) like ``sample``."""
-        from .pipeline import joint_weights_device
+        from .pipeline import joint_weights_device, ring_weights_device
         self.make_schedule(verbose=False)
         dev = torch.device("cuda")
         dit: ConcatDiT2MLP = self.model.unet.diffusion_model
         W, L, K = int(window), int(length), len(starts)
         if W > dit.cfg.max_latent_len:
             raise ValueError(f"window {W} exceeds the DiT's {dit.cfg.max_latent_len} frames")
-        wn = joint_weights_device(starts, W, L, overlap, dev)  # validates the window plan
+        wn = (ring_weights_device if ring else joint_weights_device)(starts, W, L, overlap, dev)  # validates the plan
         cond = conditioning
         if isinstance(cond, dict):
             cond = cond[list(cond.keys())[0]]
@@ -353,7 +358,7 @@ class LCMSampler:
         xw = torch.empty((KB, Cc, W), device=dev, dtype=torch.float32)
         ec = torch.empty_like(xw)
         eu = torch.empty_like(xw) if cfg else None
-        kernels.lcm_step_joint(img, None, None, plan[0]["coeffs"], starts, wn, xw=xw)   # the first windows, cut from x_T
+        kernels.lcm_step_joint(img, None, None, plan[0]["coeffs"], starts, wn, xw=xw, ring=ring)   # the first windows
         outs = [torch.empty_like(img), torch.empty_like(img)]   # never write into the caller's x_T
         denoised = torch.empty_like(img)
         for i, p in enumerate(plan):
@@ -372,7 +377,8 @@ class LCMSampler:
             last = i + 1 == len(plan)
             kernels.lcm_step_joint(img, ec, noise[i] if p["add_noise"] else None, p["coeffs"], starts, wn,
                                    eps_uncond=eu, cfg_scale=float(unconditional_guidance_scale),
-                                   prev=outs[i % 2], den=denoised, xw=None if last else xw, want_xw=not last)
+                                   prev=outs[i % 2], den=denoised, xw=None if last else xw, want_xw=not last,
+                                   ring=ring)
             img = outs[i % 2]
         return denoised, img
 

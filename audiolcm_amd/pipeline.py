@@ -114,6 +114,56 @@ def joint_weights_device(starts, W: int, L: int, overlap: int, device) -> torch.
     return _joint_dev[key]
 
 
+@functools.lru_cache(maxsize=None)
+def _ring_weights(starts: tuple, W: int, L: int, overlap: int) -> np.ndarray:
+    K = len(starts)
+    if not 2 <= K <= JOINT_MAX_WINDOWS:
+        raise ValueError(f"a ring needs 2 to {JOINT_MAX_WINDOWS} windows, got {K}")
+    if not 1 <= W <= L or overlap < 0:
+        raise ValueError(f"need 1 <= window <= the ring's {L} frames and overlap >= 0")
+    if starts[0] != 0:
+        raise ValueError("the first window must start at frame 0")
+    for a, b in zip(starts, starts[1:]):
+        if b <= a:
+            raise ValueError(f"window starts must ascend strictly, got {list(starts)}")
+        if b > a + W:
+            raise ValueError(f"frames {a + W} .. {b - 1} are under no window")
+    if starts[-1] >= L:
+        raise ValueError(f"the last window starts at {starts[-1]}, past the ring's {L} frames")
+    if starts[-1] + W < L:
+        raise ValueError(f"frames {starts[-1] + W} .. {L - 1} are under no window")
+    j = np.arange(W, dtype=np.float64)
+    w = np.minimum(1.0, (np.minimum(j, W - 1 - j) + 1.0) / (overlap + 1.0))
+    frames = [(s + np.arange(W)) % L for s in starts]
+    total = np.zeros(L, dtype=np.float64)
+    for f in frames:
+        total[f] += w     # W <= L: a window covers a frame at most once
+    wn = np.stack([w / total[f] for f in frames], 0).astype(np.float32)
+    wn.setflags(write=False)
+    return wn
+
+
+def ring_weights(starts, W: int, L: int, overlap: int) -> np.ndarray:
+    """``joint_weights`` on a ring of L frames (``sample_joint(ring=True)``, alcm_lcm_step_ring): window k covers the
+    frames (starts[k] + j) mod L, j = 0 .. W - 1.  The same raw profile w[j] = min(1, (min(j, W - 1 - j) + 1) /
+    (overlap + 1)), normalised in float64 over the windows that cover frame (starts[k] + j) mod L and rounded to fp32
+    once.  ValueError unless there are 2 to 32 windows, 1 <= W <= L, the starts begin at 0, ascend strictly and stay
+    below L, and no frame is uncovered (starts[k] <= starts[k - 1] + W, and starts[-1] + W >= L for the gap across the
+    wrap).  Built once per argument tuple; the array is read-only."""
+    return _ring_weights(tuple(int(s) for s in starts), int(W), int(L), int(overlap))
+
+
+_ring_dev = {}
+
+
+def ring_weights_device(starts, W: int, L: int, overlap: int, device) -> torch.Tensor:
+    """``ring_weights(...)`` on ``device``, uploaded once per argument tuple and device."""
+    key = (tuple(int(s) for s in starts), int(W), int(L), int(overlap), torch.device(device))
+    if key not in _ring_dev:
+        _ring_dev[key] = torch.from_numpy(ring_weights(*key[:4]).copy()).to(device)
+    return _ring_dev[key]
+
+
 class AudioLCMPipeline:
     def __init__(self, model: LCM_audio, vocoder: BigVGAN, steps: int = 2, guidance_scale: float = 5.0,
                  original_inference_steps: int = 50, latent_shape=(20, 312)):
@@ -402,6 +452,88 @@ class AudioLCMPipeline:
                                              seeds=[recipe.window_seed(s, k) for s in seeds], **kw)
             z = torch.cat([z, zk[:, :, known:]], 2)
         return dict(latent=z, **self.decode(z))
+
+    def loop_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
+        """(window starts, window length W, overlap) of ``generate_loop``: the plan of a ring of L = ``latent_len``
+        frames.  W = min(window or latent_shape[1], L); ``overlap`` defaults to W // 2, 0 < overlap < W.  K = max(2,
+        ceil(L / (W - overlap))) windows start at floor(k * L / K): every gap between cyclic neighbours is at most
+        W - overlap, so they share at least ``overlap`` frames.  One window cannot close a ring, so K is never 1: a ring
+        of one window's length is covered by two windows with different cut points.  When L and W are multiples of 4
+        the starts are rounded down to multiples of 4 (the step kernel's 16-byte path), provided they stay strictly
+        ascending and no cyclic gap exceeds W - overlap.  ValueError for more than 32 windows."""
+        L = int(latent_len)
+        W = min(int(window or self.latent_shape[1]), L)
+        overlap = W // 2 if overlap is None else int(overlap)
+        if not 0 < overlap < W:
+            raise ValueError("need 0 < overlap < window")
+        stride = W - overlap
+        K = max(2, -(-L // stride))
+        if K > JOINT_MAX_WINDOWS:
+            raise ValueError(f"{K} windows of {W} frames for a ring of {L}: at most {JOINT_MAX_WINDOWS}")
+        starts = [k * L // K for k in range(K)]
+        if L % 4 == 0 and W % 4 == 0:
+            r = [s - s % 4 for s in starts]
+            gaps = [b - a for a, b in zip(r, r[1:] + [L])]
+            if min(gaps) > 0 and max(gaps) <= stride:
+                starts = r
+        return starts, W, overlap
+
+    @torch.no_grad()
+    def generate_loop(self, cond: torch.Tensor, seeds: Optional[Sequence[int]], latent_len: int,
+                      window: Optional[int] = None, overlap: Optional[int] = None, steps: Optional[int] = None,
+                      halo_frames: Optional[int] = None, fade_samples: Optional[int] = None,
+                      out_sample_rate: Optional[int] = None, level=None, joint_clips_per_call: int = 1,
+                      x_T: Optional[torch.Tensor] = None,
+                      noise: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """A clip that loops: played end to start it has no seam.  The period is L = ``latent_len`` frames.
+
+        The latent is denoised on a ring (``sample_joint(ring=True)`` on ``loop_windows``' plan): no frame is an end,
+        and rotating the noise rotates the latent.  The decoders zero-pad at a clip's edges, so the ring is decoded with
+        a circular halo: z_ext = z[:, :, (arange(L + 2h) - h) mod L], h = ``halo_frames`` (default min(32, L), 1 <= h <=
+        L), in one ``decode`` call.  With ``out_sample_rate`` the whole extended waveform is resampled, as the one
+        continuous signal it is.  ``kernels.wave_loop`` then cuts the period of N samples that starts h frames in: its
+        first sample is the one that follows its last in the extended waveform, and what the halo leaves of a
+        difference between that continuation and the period's own start is faded out over ``fade_samples`` (default
+        32 ms at the output rate, at most h frames).  With ``level`` (``audio_in.check_level``) the N samples are
+        brought to that level by one static gain (``kernels.normalize_loudness``), which keeps the period.
+
+        The period is a whole number of frames and of output samples: L, and h after rounding up, are multiples of
+        125 / gcd(125, rate) (``audio_in.loop_multiple``; ValueError for L otherwise).  ``x_T`` (B, C, L) and ``noise``
+        (S - 1, B, C, L) replace ``recipe.prompt_noise(seeds, S, C, L)``.  Returns latent (B, C, L), mel (the centre 2L
+        frames), wav (B, N), rate, and ext, the extended waveform at that rate that wav was cut from."""
+        from . import kernels
+        from .audio_in import fade_samples_of, loop_multiple
+        L = int(latent_len)
+        rate = SAMPLE_RATE if out_sample_rate is None else int(out_sample_rate)
+        mult = loop_multiple(rate)
+        if L < 2 or L % mult:
+            raise ValueError(f"a loop at {rate} Hz is a multiple of {mult} latent frames and at least 2, got {L} "
+                             "(audio_in.loop_frames)")
+        per_frame = lambda n: n * FRAME_SAMPLES * rate // SAMPLE_RATE   # noqa: E731  (whole for multiples of mult)
+        h = min(32, L) if halo_frames is None else int(halo_frames)
+        if not 1 <= h <= L:
+            raise ValueError(f"halo_frames must be in 1 .. {L}, got {h}")
+        h = -(-h // mult) * mult
+        fade = fade_samples_of(32.0, rate) if fade_samples is None else int(fade_samples)
+        if not 0 <= fade <= min(per_frame(h), per_frame(L)):
+            raise ValueError(f"fade_samples must be in 0 .. {min(per_frame(h), per_frame(L))}: the halo's {h} frames")
+        starts, W, ov = self.loop_windows(L, window, overlap)
+        z, _ = self.sampler.sample_joint(S=steps or self.steps, conditioning=cond, length=L, starts=starts, window=W,
+                                         overlap=ov, seeds=seeds, x_T=x_T, noise=noise,
+                                         guidance_scale=self.guidance_scale,
+                                         original_inference_steps=self.original_inference_steps,
+                                         clips_per_call=joint_clips_per_call, ring=True)
+        idx = (torch.arange(L + 2 * h, device=z.device) - h) % L
+        dec = self.decode(z[:, :, idx].contiguous())
+        ext = dec["wav"].contiguous()
+        if rate != SAMPLE_RATE:
+            ext = kernels.resample(ext, SAMPLE_RATE, rate)
+        if ext.shape[1] != per_frame(L + 2 * h):
+            raise RuntimeError(f"the extended waveform has {ext.shape[1]} samples, not {per_frame(L + 2 * h)}")
+        wav = kernels.wave_loop(ext, per_frame(h), per_frame(L), fade)
+        if level is not None:
+            wav = kernels.normalize_loudness(wav, rate, level.loudness, level.peak_dbfs, level.true_peak)["wav"]
+        return dict(latent=z, mel=dec["mel"][..., 2 * h:2 * (h + L)], wav=wav, rate=rate, ext=ext)
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> Dict[str, torch.Tensor]:

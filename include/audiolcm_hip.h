@@ -311,6 +311,32 @@ int alcm_lcm_step_joint(const float* x, const float* eps_cond, const float* eps_
                         const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
                         float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
                         alcm_stream_t stream);
+/* alcm_lcm_step_ring: alcm_lcm_step_joint on a ring of L frames instead of a line (seamless loops; the same kernel
+ * body).  Arguments, outputs and the eps-less gather form are alcm_lcm_step_joint's.  Window k covers frame t at the
+ * offset o = t - starts[k], plus L when that is negative, if o < W; eps and xw_out are read and written at that offset,
+ * and wn is audiolcm_amd/pipeline.py ring_weights.  Per element the chain over the covering windows in ascending k is
+ * the open entry's: one covering window gives alcm_lcm_step's bits, several the first product rounded alone and fmaf
+ * for the further ones.  16-byte accesses under the open entry's conditions; an access then never straddles the wrap.
+ * ALCM_E_INVALID as for alcm_lcm_step_joint, except for the plan: K outside 2 .. 32, W > L, starts that do not begin at
+ * 0, do not ascend strictly, reach L (starts[K - 1] >= L) or leave a gap (starts[k] > starts[k - 1] + W, or
+ * starts[K - 1] + W < L). */
+int alcm_lcm_step_ring(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                       const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
+                       float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
+                       alcm_stream_t stream);
+/* alcm_wave_loop: one period of a looping clip cut from a longer decode of the same ring, with the seam closed, one
+ * launch (no reference counterpart).
+ *   ext (B, row_len): the decode of the ring's latent padded circularly; out (B, N); ramp (R entries, device):
+ *   alcm_wave_paste's fade table, ramp[0] = 1.
+ *   out[n] = ext[start + n] for n >= R, bit for bit;
+ *   out[0] = ext[start + N] bit for bit (R >= 1): the sample that follows out[N - 1] in ext;
+ *   out[n] = fmaf(ramp[n], ext[start + N + n] - ext[start + n], ext[start + n]) for 0 < n < R.
+ * R = 0 is a plain crop.  out must not overlap ext.  16-byte accesses when start, N and row_len are multiples of 4 and
+ * ext and out are 16-byte aligned, element accesses otherwise.
+ * ALCM_E_INVALID for a null ext or out (ramp with R > 1), a negative size or start, R > N, or start + N + R > row_len.
+ * B or N of 0: no launch. */
+int alcm_wave_loop(const float* ext, const float* ramp, float* out, int B, int64_t row_len, int64_t start, int64_t N,
+                   int R, alcm_stream_t stream);
 /* alcm_latent_init: the encoder output (or a given latent) -> the edit sampler's starting point, one launch.
  *   exactly one of moments (B, 2C, T: mean | logvar, AutoencoderKL.encode) and z0_in (B, C, T);
  *   z0 = z0_in, or scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0); e0 (B, C, T) NULL: the posterior mode

@@ -121,6 +121,8 @@ _SIGS = [
                                      C.c_int, vp]),
     ("alcm_lcm_step_joint", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, fp,
                                       fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_lcm_step_joint_edit", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int,
+                                           fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_lcm_step_ring", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, fp,
                                      fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_loop", C.c_int, [fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, vp]),

@@ -1,8 +1,8 @@
 """The audio-input half of the front end: reading ``--init-audio`` / ``init_audio`` and planning the request.
 
 ``plan_edit`` is the one place that decides what an audio-conditioned request is (a variation, an inpainting of the
-cropped clip, or a keep-original inpainting at 16 kHz or at the recording's own rate) and the one place that refuses
-one; ``AudioLCMPipeline.run_edit`` turns its ``EditPlan`` into audio.  The command line and ``AudioLCMEditInfer`` are
+cropped clip or, jointly denoised, of the whole one, a keep-original inpainting at 16 kHz or at the recording's own
+rate, or an extension of the recording) and the one place that refuses one; ``AudioLCMPipeline.run_edit`` turns its ``EditPlan`` into audio.  The command line and ``AudioLCMEditInfer`` are
 callers of the two.  Importing this module does not touch the GPU (``kernels`` is imported where a file has to be
 resampled).
 """
@@ -223,7 +223,7 @@ def finish_output(wav16: torch.Tensor, out_sample_rate: Optional[int], level: Op
 @dataclass(frozen=True, eq=False)
 class EditPlan:
     """What ``plan_edit`` decided about one audio-conditioned request; ``AudioLCMPipeline.run_edit`` runs it."""
-    mode: str                                           # "variation", "inpaint" or "keep_original"
+    mode: str                                           # "variation", "inpaint", "keep_original" or "extend"
     samples: np.ndarray                                 # mono float32 at `rate`, zero-padded to whole latent frames
     n_samples: int                                      # the sample count before padding
     rate: int                                           # the rate the edit runs at
@@ -237,17 +237,55 @@ class EditPlan:
     native: bool                                        # keep_original with resample: the file's own rate was read,
     #                                                     so the header rate is no label on 16 kHz samples
     level: Optional[Level] = None                       # the level of the output (`check_level`), None: as generated
+    joint: bool = False                                 # denoise jointly (`edit_long(joint=True)`), the whole recording
+    extend_frames: int = 0                              # extend: the latent frames generated after `samples`
+    n_out: int = 0                                      # extend: the samples written
+
+
+def extend_counts(n_samples: int, extend_s: float) -> Tuple[int, int, int]:
+    """The arithmetic of an extension of a recording of ``n_samples`` samples at 16 kHz by ``extend_s`` seconds:
+    (J, the new latent frames, the samples written).  The junction is frame J = n_samples // 512: the samples of a last
+    partial frame are regenerated, so nothing of a zero padding is ever kept as audio.  n_samples +
+    round(extend_s * 16000) samples are written, which takes ceil of that / 512 frames in all.  ValueError for a
+    recording shorter than one frame or an extension of less than one sample."""
+    J = n_samples // FRAME_SAMPLES
+    if J < 1:
+        raise ValueError(f"the recording has {n_samples} samples at {SAMPLE_RATE} Hz: an extension needs at least one "
+                         f"latent frame of {FRAME_SAMPLES} to continue")
+    extra = int(round(extend_s * SAMPLE_RATE)) if extend_s == extend_s else 0   # NaN: refused below
+    if extra < 1:
+        raise ValueError(f"extend_s must add at least one sample, got {extend_s!r}")
+    n_out = n_samples + extra
+    return J, -(-n_out // FRAME_SAMPLES) - J, n_out
 
 
 def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]]] = None, keep_original: bool = False,
               fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
               max_frames: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-              true_peak: bool = False) -> EditPlan:
+              true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None) -> EditPlan:
     """Reads ``init_audio`` once and decides the request, or refuses it with ValueError.  No ``mask_spans``: a
     variation; with them: an inpainting of the clip (both crop to ``max_frames`` latent frames here when given;
     ``run_edit`` crops to the DiT's limit in any case); ``keep_original``: the whole frames inside the spans are
     regenerated in a clip of any length, at 16 kHz or, with ``resample``, at the recording's own rate.  ``loudness``,
-    ``peak_dbfs``, ``true_peak``: the level of the output (``check_level``); refused with ``keep_original``."""
+    ``peak_dbfs``, ``true_peak``: the level of the output (``check_level``); refused with ``keep_original``.
+    ``joint``: the frames to regenerate are denoised jointly (``edit_long(joint=True)``); a variation or an inpainting
+    is then made from the whole recording instead of a crop to the DiT's limit.  ``extend_s``: the recording is
+    continued by that many seconds (``AudioLCMPipeline.extend``, ``extend_counts``) at 16 kHz; with ``resample`` any
+    input is brought to 16 kHz first and the kept part is the resampled recording.  Refused with ``mask_spans`` and
+    ``keep_original``, with a level (it would scale the kept samples) and with ``out_sample_rate``."""
+    if extend_s is not None:
+        if mask_spans or keep_original:
+            raise ValueError("extend_s continues the recording: it does not combine with mask_spans or keep_original")
+        if loudness is not None or peak_dbfs is not None or true_peak:
+            raise ValueError("extend_s keeps the recording's samples bit for bit; loudness, peak_dbfs and true_peak "
+                             "would scale them")
+        if out_sample_rate is not None:
+            raise ValueError(f"extend_s writes {SAMPLE_RATE} Hz, the rate it keeps the recording at, not "
+                             f"out_sample_rate {out_sample_rate}")
+        x, rate, F = _read_mono(init_audio, resample)
+        J, frames, n_out = extend_counts(x.size, extend_s)
+        return EditPlan("extend", np.ascontiguousarray(x[:J * F]), x.size, rate, F, None, None,
+                        fade_samples_of(fade_ms, rate), rate, False, 32768.0, False, None, True, frames, n_out)
     if keep_original and not mask_spans:
         raise ValueError("keep_original needs mask_spans: the time spans to regenerate")
     level = check_level(loudness, peak_dbfs, true_peak)
@@ -266,4 +304,5 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
         samples = samples if max_frames is None else samples[:max_frames * F]
     out_rate = rate if keep_original else out_sample_rate or SAMPLE_RATE
     return EditPlan(mode, samples, x.size, rate, F, spans, mask, fade_samples_of(fade_ms, rate), out_rate,
-                    out_rate != rate, 32768.0 if keep_original else 32767.0, keep_original and resample, level)
+                    out_rate != rate, 32768.0 if keep_original else 32767.0, keep_original and resample, level,
+                    bool(joint))

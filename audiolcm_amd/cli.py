@@ -18,7 +18,13 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
     ``--keep-original`` (with ``--inpaint``) takes a recording of any length, regenerates only the
     whole latent frames inside the spans window by window and fades them into the input over ``--fade-ms F`` (default
     32) either side: every sample further than F ms from a span is written back as it was read, and each output has
-    the input's sample count.  Without it the clip is cropped to the DiT's 845 frames and synthesised again as a whole;
+    the input's sample count.  Without it the clip is cropped to the DiT's 845 frames and synthesised again as a whole.
+    ``--long-joint`` with ``--init-audio`` denoises the frames to regenerate jointly (S DiT calls per region instead
+    of S per window), and a variation or a plain ``--inpaint`` then works on the whole recording instead of a crop;
+  * ``--extend SECONDS`` (with ``--init-audio``) continues the recording at 16 kHz: the file holds the recording,
+    as it was read up to ``--fade-ms`` before the junction, and SECONDS of generated continuation.  It does not combine
+    with ``--inpaint``, ``--mask-spans``, ``--keep-original``, ``--loop``, ``--duration``, the level options or
+    ``--out-sample-rate``;
   * ``--resample``: ``--init-audio`` may have any sample rate, 1 to 8 channels and PCM16, PCM24 or float32 samples; it
     is downmixed and resampled to 16 kHz on the GPU (alcm_resample; without the flag only 16 kHz mono PCM16 is read).
     With ``--keep-original`` the edit is done at the recording's own rate: mono, and a rate at which a latent frame is a
@@ -102,7 +108,10 @@ def parse_args(argv: Optional[Sequence[str]] = None):
     p.add_argument("--duration", type=float, default=None,
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--long-joint", action="store_true",
-                   help="with --duration: denoise the windows jointly, one DiT call per clip and LCM step (DESIGN.md §5)")
+                   help="with --duration: denoise the windows jointly, one DiT call per clip and LCM step; with "
+                        "--init-audio: denoise the frames to regenerate jointly, on the whole recording (DESIGN.md §5)")
+    p.add_argument("--extend", type=float, default=None, metavar="SECONDS",
+                   help="with --init-audio: continue the recording by this many seconds (DESIGN.md §5)")
     p.add_argument("--loop", action="store_true",
                    help="write clips that loop without a seam: one period of --duration seconds (rounded up to whole "
                         "latent frames), or of --W frames without --duration (DESIGN.md §5)")
@@ -208,6 +217,22 @@ def loop_period(opt) -> int:
 
 
 def build(opt):
+    if opt.extend is not None:
+        if not opt.init_audio:
+            raise ValueError("--extend continues a recording: it needs --init-audio PATH")
+        if opt.inpaint or opt.mask_spans or opt.keep_original:
+            raise ValueError("--extend does not combine with --inpaint, --mask-spans or --keep-original: it regenerates "
+                             "nothing of the recording")
+        if opt.loop:
+            raise ValueError("--extend does not combine with --loop: a continued recording does not loop")
+        if opt.duration is not None:
+            raise ValueError("--extend does not combine with --duration: the length is the recording's plus --extend")
+        if opt.loudness is not None or opt.peak is not None or opt.true_peak:
+            raise ValueError("--extend keeps the recording's samples bit for bit; --loudness, --peak and --true-peak "
+                             "would scale them")
+        if opt.out_sample_rate is not None:
+            raise ValueError("--extend writes 16 kHz, the rate it keeps the recording at: it does not combine with "
+                             "--out-sample-rate")
     if opt.loop:
         if opt.init_audio or opt.inpaint or opt.keep_original:
             raise ValueError("--loop generates from text: it does not combine with --init-audio, --inpaint or "
@@ -230,8 +255,8 @@ def build(opt):
         raise ValueError("--mask-spans is used with --inpaint")
     if opt.init_audio and opt.duration is not None:
         raise ValueError("--init-audio and --duration do not combine")
-    if opt.long_joint and opt.duration is None and not opt.loop:
-        raise ValueError("--long-joint is used with --duration")
+    if opt.long_joint and opt.duration is None and not opt.loop and not opt.init_audio:
+        raise ValueError("--long-joint is used with --duration or with --init-audio")
     if opt.resample and not opt.init_audio:
         raise ValueError("--resample is used with --init-audio")
     check_out_rate(opt.out_sample_rate)
@@ -239,7 +264,7 @@ def build(opt):
     # the file and the flags decide: a refused request fails before the models are built
     plan = plan_edit(opt.init_audio, parse_spans(opt.mask_spans) if opt.inpaint else None, opt.keep_original,
                      opt.fade_ms, opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
-                     true_peak=opt.true_peak) if opt.init_audio else None
+                     true_peak=opt.true_peak, joint=opt.long_joint, extend_s=opt.extend) if opt.init_audio else None
     config = load_config(opt.base)
     split = {"split": True, "bf16": "bf16", "mixed": "mixed"}[opt.precision]
     if opt.synthetic_seed is None:

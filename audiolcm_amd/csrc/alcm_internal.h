@@ -53,6 +53,10 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
 int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
                    const float* coeffs, const int* starts, int K, const float* wn, float* prev, float* den, float* xw,
                    int B, int C, int L, int W, hipStream_t s);
+int lcm_step_joint_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                        const float* coeffs, const int* starts, int K, const float* wn, const float* z0,
+                        const float* mask, float* prev, float* den, float* xw, int B, int C, int L, int W,
+                        hipStream_t s);
 int lcm_step_ring(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
                   const float* coeffs, const int* starts, int K, const float* wn, float* prev, float* den, float* xw,
                   int B, int C, int L, int W, hipStream_t s);

@@ -587,6 +587,9 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
 // t - s_k, plus L when that is negative, if it is below W (W <= L: a window covers a frame at most once).  The chain
 // is the same one in ascending k, and with V = 4 an access never straddles the wrap (L, W and the starts are multiples
 // of 4).
+// Edit = true (lcm_step_joint_edit) blends the joint estimate with a known latent before the re-noise, as the edit step
+// does: d' = mask_blend(mask[b, t], d, z0[b, c, t]), den = d', prev = the re-noised d'.  The mask is read once per item
+// and the z0 rows with x and noise, ahead of the windows' loads; the other forms load nothing more than before.
 constexpr int kJointMaxWin = 32;
 struct JointStarts {
   int s[kJointMaxWin];
@@ -603,22 +606,24 @@ __device__ __forceinline__ int window_offset(int t, int s, int L) {
   return Ring && o < 0 ? o + L : o;
 }
 
-template <int V, bool Ring>
+template <int V, bool Ring, bool Edit>
 __global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
     const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg,
     const float* __restrict__ noise, StepCoeffs k, JointStarts st, int K, const float* __restrict__ wn,
-    float* __restrict__ prev, float* __restrict__ den, float* __restrict__ xw, int B, int C, int L, int W,
-    int64_t items) {
+    const float* __restrict__ z0, const float* __restrict__ mask, float* __restrict__ prev, float* __restrict__ den,
+    float* __restrict__ xw, int B, int C, int L, int W, int64_t items) {
   for (int64_t it = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; it < items; it += (int64_t)gridDim.x * blockDim.x) {
     const EditItem w = edit_item<V>(it, C, L);
     const int64_t o0 = (w.b * C + w.c0) * L + w.t;
     const int nch = C - w.c0 < kEditCh ? C - w.c0 : kEditCh;
-    FVec<V> xv[kEditCh], nv[kEditCh], acc[kEditCh], one[kEditCh];
+    FVec<V> xv[kEditCh], nv[kEditCh], acc[kEditCh], one[kEditCh], zv[Edit ? kEditCh : 1], m;
+    if constexpr (Edit) m = FVec<V>::ld(mask + w.b * L + w.t);
 #pragma unroll
     for (int j = 0; j < kEditCh; ++j) {
       if (j >= nch) break;
       xv[j] = FVec<V>::ld(x + o0 + (int64_t)j * L);
       if (noise) nv[j] = FVec<V>::ld(noise + o0 + (int64_t)j * L);  // in flight with x, ahead of the windows' loads
+      if constexpr (Edit) zv[j] = FVec<V>::ld(z0 + o0 + (int64_t)j * L);
     }
     int cover = 0;
     for (int kk = 0; kk < K; ++kk) {
@@ -652,7 +657,10 @@ __global__ __launch_bounds__(kEditBlock) void lcm_step_joint_kernel(
       const int64_t o = o0 + (int64_t)j * L;
       FVec<V> dv;
 #pragma unroll
-      for (int i = 0; i < V; ++i) dv.v[i] = cover == 1 ? one[j].v[i] : acc[j].v[i];
+      for (int i = 0; i < V; ++i) {
+        dv.v[i] = cover == 1 ? one[j].v[i] : acc[j].v[i];
+        if constexpr (Edit) dv.v[i] = mask_blend(m.v[i], dv.v[i], zv[j].v[i]);
+      }
 #pragma unroll
       for (int i = 0; i < V; ++i) xv[j].v[i] = noise ? lcm_renoise(dv.v[i], nv[j].v[i], k) : dv.v[i];
       if (den) dv.st(den + o);
@@ -695,14 +703,18 @@ __global__ __launch_bounds__(kEditBlock) void joint_gather_kernel(const float* _
   }
 }
 
-// The host side of both forms.  `fn` names the entry in the errors; the open form's plan rules are those of
-// pipeline.joint_weights and the ring's those of pipeline.ring_weights, checked before any launch.
-template <bool Ring>
+// The host side of all forms.  `fn` names the entry in the errors; the open form's plan rules are those of
+// pipeline.joint_weights and the ring's those of pipeline.ring_weights, checked before any launch.  Edit: the open form
+// with z0 and mask; it has no gather-only form.
+template <bool Ring, bool Edit = false>
 static int step_windows(const char* fn, const float* x, const float* eps, const float* eps_u, float cfg,
-                        const float* noise, const float* c, const int* starts, int K, const float* wn, float* prev,
-                        float* den, float* xw, int B, int C, int L, int W, hipStream_t s) {
+                        const float* noise, const float* c, const int* starts, int K, const float* wn, const float* z0,
+                        const float* mask, float* prev, float* den, float* xw, int B, int C, int L, int W,
+                        hipStream_t s) {
+  static_assert(!(Ring && Edit), "the ring has no edit form yet");
   const std::string f = std::string(fn) + ": ";
   if (!x || !wn || !c || !starts) return set_error(ALCM_E_INVALID, f + "null x, wn, coeffs or starts");
+  if (Edit && (!eps || !z0 || !mask)) return set_error(ALCM_E_INVALID, f + "null eps_cond, z0 or mask");
   if (!prev && !den && !xw) return set_error(ALCM_E_INVALID, f + "no output");
   if (!eps && (eps_u || noise || prev || den || !xw))
     return set_error(ALCM_E_INVALID, f + "without eps only x is gathered into xw");
@@ -729,12 +741,12 @@ static int step_windows(const char* fn, const float* x, const float* eps, const 
     return set_error(ALCM_E_INVALID, f + "the last window must end at L");
   }
   StepCoeffs k{c[0], c[1], c[2], c[3], c[4], c[5]};
-  const bool vec = mult4 && L % 4 == 0 && W % 4 == 0 && aligned16({x, eps, eps_u, noise, wn, prev, den, xw});
+  const bool vec = mult4 && L % 4 == 0 && W % 4 == 0 && aligned16({x, eps, eps_u, noise, wn, z0, mask, prev, den, xw});
   const int64_t items = edit_items(B, C, L, vec);
   const dim3 grid(edit_blocks(items)), blk(kEditBlock);
   const double nl = (double)B * C * L, nw = (double)K * B * C * W;
   void* tok = prof_start(s);
-  if (!eps) {
+  if (!Edit && !eps) {
     if (vec) hipLaunchKernelGGL((joint_gather_kernel<4, Ring>), grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
     else hipLaunchKernelGGL((joint_gather_kernel<1, Ring>), grid, blk, 0, s, x, st, K, xw, B, C, L, W, items);
     prof_stop(tok, s,
@@ -745,19 +757,23 @@ static int step_windows(const char* fn, const float* x, const float* eps, const 
     return 0;
   }
   if (vec)
-    hipLaunchKernelGGL((lcm_step_joint_kernel<4, Ring>), grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev,
-                       den, xw, B, C, L, W, items);
+    hipLaunchKernelGGL((lcm_step_joint_kernel<4, Ring, Edit>), grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn,
+                       z0, mask, prev, den, xw, B, C, L, W, items);
   else
-    hipLaunchKernelGGL((lcm_step_joint_kernel<1, Ring>), grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn, prev,
-                       den, xw, B, C, L, W, items);
-  // the window tensors (eps, eps_u, xw) count K * B * C * W elements and the long ones (x, noise, prev, den) B * C * L; the
-  // weights once per window, frame and channel group; per window element the step (8) and one multiply-add
+    hipLaunchKernelGGL((lcm_step_joint_kernel<1, Ring, Edit>), grid, blk, 0, s, x, eps, eps_u, cfg, noise, k, st, K, wn,
+                       z0, mask, prev, den, xw, B, C, L, W, items);
+  // the window tensors (eps, eps_u, xw) count K * B * C * W elements and the long ones (x, noise, prev, den, and z0 of
+  // the edit form) B * C * L; the weights once per window, frame and channel group, and so the edit form's mask per
+  // frame and channel group; per window element the step (8) and one multiply-add
+  const int cg = (C + kEditCh - 1) / kEditCh;
   prof_stop(tok, s,
-            Ring ? (vec ? "alcm::lcm_step_ring_kernel<4>" : "alcm::lcm_step_ring_kernel<1>")
-                 : (vec ? "alcm::lcm_step_joint_kernel<4>" : "alcm::lcm_step_joint_kernel<1>"),
+            Edit   ? (vec ? "alcm::lcm_step_joint_edit_kernel<4>" : "alcm::lcm_step_joint_edit_kernel<1>")
+            : Ring ? (vec ? "alcm::lcm_step_ring_kernel<4>" : "alcm::lcm_step_ring_kernel<1>")
+                   : (vec ? "alcm::lcm_step_joint_kernel<4>" : "alcm::lcm_step_joint_kernel<1>"),
             10.0 * nw + (noise ? 3.0 * nl : 0.0),
-            4.0 * (nl * (1 + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0)) +
-                   nw * (1 + (eps_u ? 1 : 0) + (xw ? 1 : 0)) + (double)K * W * B * ((C + kEditCh - 1) / kEditCh)));
+            4.0 * (nl * (1 + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0) + (Edit ? 1 : 0)) +
+                   nw * (1 + (eps_u ? 1 : 0) + (xw ? 1 : 0)) + (double)K * W * B * cg +
+                   (Edit ? (double)B * L * cg : 0.0)));
   ALCM_HIP(hipGetLastError());
   return 0;
 }
@@ -765,13 +781,22 @@ static int step_windows(const char* fn, const float* x, const float* eps, const 
 int lcm_step_joint(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
                    const int* starts, int K, const float* wn, float* prev, float* den, float* xw, int B, int C, int L,
                    int W, hipStream_t s) {
-  return step_windows<false>("lcm_step_joint", x, eps, eps_u, cfg, noise, c, starts, K, wn, prev, den, xw, B, C, L, W, s);
+  return step_windows<false>("lcm_step_joint", x, eps, eps_u, cfg, noise, c, starts, K, wn, nullptr, nullptr, prev, den,
+                             xw, B, C, L, W, s);
+}
+
+int lcm_step_joint_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                        const float* c, const int* starts, int K, const float* wn, const float* z0, const float* mask,
+                        float* prev, float* den, float* xw, int B, int C, int L, int W, hipStream_t s) {
+  return step_windows<false, true>("lcm_step_joint_edit", x, eps, eps_u, cfg, noise, c, starts, K, wn, z0, mask, prev,
+                                   den, xw, B, C, L, W, s);
 }
 
 int lcm_step_ring(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise, const float* c,
                   const int* starts, int K, const float* wn, float* prev, float* den, float* xw, int B, int C, int L,
                   int W, hipStream_t s) {
-  return step_windows<true>("lcm_step_ring", x, eps, eps_u, cfg, noise, c, starts, K, wn, prev, den, xw, B, C, L, W, s);
+  return step_windows<true>("lcm_step_ring", x, eps, eps_u, cfg, noise, c, starts, K, wn, nullptr, nullptr, prev, den, xw,
+                            B, C, L, W, s);
 }
 
 // z0 = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0) from the encoder's (B, 2C, T) moments (the posterior mode
@@ -1177,6 +1202,14 @@ extern "C" int alcm_lcm_step_joint(const float* x, const float* eps_cond, const 
                                    alcm_stream_t stream) {
   return alcm::lcm_step_joint(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, prev_out, denoised_out,
                               xw_out, B, C, L, W, (hipStream_t)stream);
+}
+extern "C" int alcm_lcm_step_joint_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                                        const float* noise, const float* coeffs, const int* starts, int K,
+                                        const float* wn, const float* z0, const float* mask, float* prev_out,
+                                        float* denoised_out, float* xw_out, int B, int C, int L, int W,
+                                        alcm_stream_t stream) {
+  return alcm::lcm_step_joint_edit(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, z0, mask, prev_out,
+                                   denoised_out, xw_out, B, C, L, W, (hipStream_t)stream);
 }
 extern "C" int alcm_lcm_step_ring(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
                                   const float* noise, const float* coeffs, const int* starts, int K, const float* wn,

@@ -185,7 +185,7 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
                       outpath: str = "results/test", seed: Optional[int] = None, keep_original: bool = False,
                       fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
                       loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-                      true_peak: bool = False) -> str:
+                      true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None) -> str:
     """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength``, or, with ``mask_spans``
     ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
     clip is synthesised again from the latent, cropped to the DiT's 845 frames.  ``keep_original`` (needs
@@ -198,11 +198,19 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
     frame is a whole number of samples: 48000, 32000, 8000, ...) and the output has the input's rate and sample count.
     ``out_sample_rate``: the output is resampled from 16 kHz to that rate on the GPU and written under it (with
     ``keep_original`` it may only name the input's rate).  ``loudness``, ``peak_dbfs``, ``true_peak``: the level of the
-    output, as ``AudioLCMBatchInfer``; refused with ``keep_original``, whose kept samples they would scale.  Returns the
+    output, as ``AudioLCMBatchInfer``; refused with ``keep_original``, whose kept samples they would scale.
+    ``joint``: the frames to regenerate are denoised jointly (``edit_long(joint=True)``: S DiT calls per region of
+    regenerated frames instead of S per window); a variation or an inpainting without ``keep_original`` is then made
+    from the whole recording, not from a crop to 845 frames.
+    ``extend_s``: the recording is continued by that many seconds (``AudioLCMPipeline.extend``) at 16 kHz.  The file
+    holds n + round(extend_s * 16000) samples, n the recording's; the recording comes back as it was read up to
+    ``fade_ms`` before the junction at frame n // 512 (the samples of a last partial frame are generated again).
+    ``resample`` brings any input to 16 kHz first.  Refused with ``mask_spans``, ``keep_original``, a level and
+    ``out_sample_rate``, and for a recording shorter than one latent frame.  Returns the
     WAV path (``<prompt-with-dashes>_0.wav``)."""
     from .pipeline import AudioLCMPipeline
     plan = plan_edit(init_audio, mask_spans, keep_original, fade_ms, resample, out_sample_rate, loudness=loudness,
-                     peak_dbfs=peak_dbfs, true_peak=true_peak)  # before any model
+                     peak_dbfs=peak_dbfs, true_peak=true_peak, joint=joint, extend_s=extend_s)  # before any model
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  encoder=True)
     pipe = AudioLCMPipeline(model, vocoder.generator, steps=2, original_inference_steps=orig_steps,

@@ -375,6 +375,36 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
     return prev, den, xw
 
 
+def lcm_step_joint_edit(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tensor], coeffs, starts,
+                        wn: torch.Tensor, z0: torch.Tensor, mask: torch.Tensor,
+                        eps_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, want_prev: bool = True,
+                        want_den: bool = True, want_xw: bool = True, prev: Optional[torch.Tensor] = None,
+                        den: Optional[torch.Tensor] = None, xw: Optional[torch.Tensor] = None):
+    """``lcm_step_joint`` with the known latent ``z0`` (B, C, L) blended into the joint estimate per frame, as
+    ``lcm_step_edit`` does for one window: ``mask`` (B, L) in [0, 1], 1 = take the joint step's value, 0 = keep z0
+    (alcm_lcm_step_joint_edit).  Returns (prev, denoised, xw) as ``lcm_step_joint``; ``eps`` is required (the first
+    windows are gathered by ``lcm_step_joint(x, None, ...)``).  One launch."""
+    B, Cc, L = x.shape
+    K, W = wn.shape
+    assert len(starts) == K and x.is_contiguous() and wn.is_contiguous()
+    assert tuple(eps.shape) == (K * B, Cc, W) and eps.is_contiguous()
+    assert eps_uncond is None or (eps_uncond.shape == eps.shape and eps_uncond.is_contiguous())
+    assert noise is None or (noise.shape == x.shape and noise.is_contiguous())
+    assert z0.shape == x.shape and z0.is_contiguous() and tuple(mask.shape) == (B, L) and mask.is_contiguous()
+    if want_prev and prev is None:
+        prev = torch.empty_like(x)
+    if want_den and den is None:
+        den = torch.empty_like(x)
+    if want_xw and xw is None:
+        xw = torch.empty((K * B, Cc, W), device=x.device, dtype=torch.float32)
+    arr = (C.c_float * 6)(*[float(c) for c in coeffs])
+    st = (C.c_int * K)(*[int(s) for s in starts])
+    check(lib().alcm_lcm_step_joint_edit(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K,
+                                         ptr(wn), ptr(z0), ptr(mask), ptr(prev), ptr(den), ptr(xw), B, Cc, L, W,
+                                         stream_handle()), "lcm_step_joint_edit")
+    return prev, den, xw
+
+
 def latent_init(noise: Optional[torch.Tensor], keep=(1.0, 0.0), regen=(0.0, 1.0), moments: Optional[torch.Tensor] = None,
                 z0: Optional[torch.Tensor] = None, e0: Optional[torch.Tensor] = None, scale: float = 1.0,
                 mask: Optional[torch.Tensor] = None, want_z0: bool = True,

@@ -281,7 +281,9 @@ class LCMSampler:
                      noise: Optional[torch.Tensor] = None, guidance_scale=5., original_inference_steps=50,
                      unconditional_conditioning: Optional[torch.Tensor] = None,
                      unconditional_guidance_scale: float = 1.0,
-                     clips_per_call: int = 1, ring: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                     clips_per_call: int = 1, ring: bool = False, init=None, mask=None, strength: float = 1.0,
+                     init_noise: Optional[torch.Tensor] = None, posterior_noise: Optional[torch.Tensor] = None,
+                     sample_posterior: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
         """Joint long-form sampling: S LCM steps on one latent of ``length`` frames covered by the K windows of
         ``window`` frames at ``starts`` (``AudioLCMPipeline.long_windows``).  Every step runs the DiT on all windows of
         all clips (K * B rows, row k * B + b; [uc; c] doubled with guidance as in ``sample``) and then one
@@ -304,6 +306,16 @@ class LCMSampler:
         length, the plan is ``pipeline.ring_weights`` (at least two windows: ``AudioLCMPipeline.loop_windows``) and the
         step alcm_lcm_step_ring.  Each window is still an ordinary DiT call on ``window`` frames, and everything else is
         as above; rotating ``x_T`` and ``noise`` by a multiple of the windows' spacing rotates the result.
+
+        ``init``: joint denoising from a known latent, ``sample_edit`` on the long latent.  ``init`` (the encoder's
+        ``DiagonalGaussianDistribution`` or a scaled (B, C, length) latent), ``mask`` (B, length) or None, ``strength``,
+        ``init_noise``, ``posterior_noise`` and ``sample_posterior`` mean what they mean there: the plan is
+        ``schedule.sample_plan(S, ..., strength=strength)``, the draws with ``seeds`` are ``recipe.edit_noise(seeds, S',
+        C, length)`` at the clip's whole length, the start is one alcm_latent_init on the long latent, and every step is
+        one alcm_lcm_step_joint_edit, which blends the joint estimate with z0 per frame: frames of mask 0 keep z0
+        exactly.  Without a mask every frame is regenerated and the step is the open entry, as ``sample_edit``'s is the
+        plain one.  With one window the result is ``sample_edit``'s bit for bit.  ``x_T`` is not used, and a ring
+        cannot take ``init`` (ValueError): that kernel form does not exist yet.
         Returns (denoised, last sample) like ``sample``."""
         from .pipeline import joint_weights_device, ring_weights_device
         self.make_schedule(verbose=False)
@@ -319,20 +331,32 @@ class LCMSampler:
             while isinstance(cond, list):
                 cond = cond[0]
         B, Cc = cond.shape[0], dit.cfg.in_channels
-        plan = schedule.sample_plan(S, original_inference_steps)
-        self.num_inference_steps = len(plan)
-        self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
-        n_noise = sum(1 for p in plan if p["add_noise"])
-        if seeds is not None:
-            xT_h, noise_h = recipe.prompt_noise(seeds, len(plan), Cc, L)
-            img = _h2d(xT_h, dev) if x_T is None else x_T.to(dev)
-            noise = _h2d(noise_h, dev) if noise is None else noise
+        z0 = None
+        if init is not None:
+            if ring:
+                raise ValueError("a ring cannot take `init`: joint editing exists on a line only")
+            if x_T is not None:
+                raise ValueError("`x_T` is not used with `init`: pass `init_noise`")
+            plan, img, z0, noise, mask = self._edit_start(S, init, mask, strength, seeds, noise, init_noise,
+                                                          posterior_noise, sample_posterior,
+                                                          original_inference_steps, one_window=False)
+            if mask is None:
+                z0 = None
         else:
-            img = x_T.to(dev) if x_T is not None else torch.randn((B, Cc, L), device=dev)
-            if noise is None and n_noise:
-                noise = torch.randn((n_noise, B, Cc, L), device=dev)
-        img = img.float().contiguous()
-        noise = noise.to(dev).float().contiguous() if noise is not None else None
+            plan = schedule.sample_plan(S, original_inference_steps)
+            self.num_inference_steps = len(plan)
+            self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
+            n_noise = sum(1 for p in plan if p["add_noise"])
+            if seeds is not None:
+                xT_h, noise_h = recipe.prompt_noise(seeds, len(plan), Cc, L)
+                img = _h2d(xT_h, dev) if x_T is None else x_T.to(dev)
+                noise = _h2d(noise_h, dev) if noise is None else noise
+            else:
+                img = x_T.to(dev) if x_T is not None else torch.randn((B, Cc, L), device=dev)
+                if noise is None and n_noise:
+                    noise = torch.randn((n_noise, B, Cc, L), device=dev)
+            img = img.float().contiguous()
+            noise = noise.to(dev).float().contiguous() if noise is not None else None
         if tuple(img.shape) != (B, Cc, L):
             raise ValueError(f"x_T must be (B, C, length) = {(B, Cc, L)}, got {tuple(img.shape)}")
 
@@ -375,10 +399,13 @@ class LCMSampler:
                 if cfg or not whole:
                     ec.view(K, B, Cc, W)[:, b0:b1] = e[-n:].view(K, b1 - b0, Cc, W)
             last = i + 1 == len(plan)
-            kernels.lcm_step_joint(img, ec, noise[i] if p["add_noise"] else None, p["coeffs"], starts, wn,
-                                   eps_uncond=eu, cfg_scale=float(unconditional_guidance_scale),
-                                   prev=outs[i % 2], den=denoised, xw=None if last else xw, want_xw=not last,
-                                   ring=ring)
+            kw = dict(eps_uncond=eu, cfg_scale=float(unconditional_guidance_scale), prev=outs[i % 2], den=denoised,
+                      xw=None if last else xw, want_xw=not last)
+            nz = noise[i] if p["add_noise"] else None
+            if z0 is not None:
+                kernels.lcm_step_joint_edit(img, ec, nz, p["coeffs"], starts, wn, z0, mask, **kw)
+            else:
+                kernels.lcm_step_joint(img, ec, nz, p["coeffs"], starts, wn, ring=ring, **kw)
             img = outs[i % 2]
         return denoised, img
 
@@ -401,6 +428,21 @@ class LCMSampler:
         RNG: with ``seeds``, per prompt n0, the step noise and e0 from ``recipe.edit_noise``; ``init_noise``, ``noise``
         and ``posterior_noise`` replace the respective draw; without seeds the global device RNG.
         Returns (denoised, last sample) like ``sample``."""
+        cond = conditioning
+        if isinstance(cond, dict):
+            cond = cond[list(cond.keys())[0]]
+            while isinstance(cond, list):
+                cond = cond[0]
+        plan, img, z0, noise, mask = self._edit_start(S, init, mask, strength, seeds, noise, init_noise,
+                                                      posterior_noise, sample_posterior, original_inference_steps)
+        return self._run(plan, img, noise, cond, img.shape[0], guidance_scale, unconditional_conditioning,
+                         unconditional_guidance_scale, z0=z0 if mask is not None else None, mask=mask)
+
+    def _edit_start(self, S, init, mask, strength, seeds, noise, init_noise, posterior_noise, sample_posterior,
+                    original_inference_steps, one_window: bool = True):
+        """The start of ``sample_edit`` and of ``sample_joint(init=...)``: (plan, x at plan[0]'s noise level, z0, the
+        step noise, the mask on the device or None) from their arguments, with one alcm_latent_init on the whole
+        latent.  ``one_window``: the latent must fit the DiT."""
         self.make_schedule(verbose=False)
         if not 0.0 < strength <= 1.0:
             raise ValueError(f"`strength` must be in (0, 1], got {strength}")
@@ -417,7 +459,7 @@ class LCMSampler:
             B, Cc, T = z_in.shape
             moments = None
         dit: ConcatDiT2MLP = self.model.unet.diffusion_model
-        if T > dit.cfg.max_latent_len:
+        if one_window and T > dit.cfg.max_latent_len:
             raise ValueError(f"latent length {T} exceeds the DiT's {dit.cfg.max_latent_len} frames")
         if mask is not None:
             mask = torch.as_tensor(mask, dtype=torch.float32)
@@ -426,11 +468,6 @@ class LCMSampler:
             if tuple(mask.shape) != (B, T):
                 raise ValueError(f"mask must be (B, T) = {(B, T)}, got {tuple(mask.shape)}")
             mask = mask.to(dev).contiguous()
-        cond = conditioning
-        if isinstance(cond, dict):
-            cond = cond[list(cond.keys())[0]]
-            while isinstance(cond, list):
-                cond = cond[0]
         plan = schedule.sample_plan(S, original_inference_steps, strength=strength)
         self.num_inference_steps = len(plan)
         self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
@@ -460,5 +497,4 @@ class LCMSampler:
         check(lib().alcm_latent_init(ptr(moments), ptr(z_in), ptr(e0), float(self.model.scale_factor), ptr(n0),
                                      ptr(mask), sk[0], sk[1], regen[0], regen[1], ptr(z0), ptr(img), B, Cc, T,
                                      stream_handle()), "latent_init")
-        return self._run(plan, img, noise, cond, B, guidance_scale, unconditional_conditioning,
-                         unconditional_guidance_scale, z0=z0 if mask is not None else None, mask=mask)
+        return plan, img, z0, noise, mask

@@ -103,6 +103,43 @@ def joint_weights(starts, W: int, L: int, overlap: int) -> np.ndarray:
     return _joint_weights(tuple(int(s) for s in starts), int(W), int(L), int(overlap))
 
 
+def _long_windows(latent_len: int, window: int, overlap: Optional[int] = None):
+    """``AudioLCMPipeline.long_windows`` for a given window length."""
+    overlap = window // 2 if overlap is None else overlap
+    if not 0 < overlap < window:
+        raise ValueError("need 0 < overlap < window")
+    if latent_len <= window:
+        return [(0, 0)], latent_len
+    spans, end = [(0, 0)], window
+    while end < latent_len:
+        start = min(end - overlap, latent_len - window)
+        spans.append((start, end - start))
+        end = start + window
+    return spans, window
+
+
+def joint_edit_regions(union, window: int, overlap: Optional[int] = None):
+    """The host plan of ``edit_long(joint=True)`` for a clip of L = len(union) latent frames, ``union[t]`` true where
+    any clip of the batch regenerates frame t: a list of (a, b, starts, W).  Every maximal run of regenerated frames
+    is widened by ``overlap`` frames of known context either side and clamped to the clip, and touching or overlapping
+    ranges are merged (``paste_regions(union, overlap)``); region [a, b) of R = b - a frames is denoised jointly on
+    ``long_windows(R, window, overlap)``'s plan: K windows of W = min(window, R) frames at ``starts``, relative to a.
+    ``overlap`` defaults to min(window, L) // 2.  ValueError for a region of more than ``JOINT_MAX_WINDOWS``
+    windows."""
+    L = len(union)
+    overlap = min(window, L) // 2 if overlap is None else overlap
+    if not 0 < overlap < window:
+        raise ValueError("need 0 < overlap < window")
+    plan = []
+    for a, b in paste_regions(union, overlap):
+        spans, W = _long_windows(b - a, window, overlap)
+        if len(spans) > JOINT_MAX_WINDOWS:
+            raise ValueError(f"the region of frames {a} .. {b} needs {len(spans)} windows of {W} frames: at most "
+                             f"{JOINT_MAX_WINDOWS} are denoised jointly")
+        plan.append((a, b, [s for s, _ in spans], W))
+    return plan
+
+
 _joint_dev = {}
 
 
@@ -245,7 +282,8 @@ class AudioLCMPipeline:
                   sample_posterior: bool = True, steps: Optional[int] = None,
                   unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, keep_original: bool = False,
                   fade_samples: Optional[int] = None, halo_frames: int = 32,
-                  rate: int = SAMPLE_RATE) -> Dict[str, torch.Tensor]:
+                  rate: int = SAMPLE_RATE, joint: bool = False,
+                  joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
         """``edit`` for a clip of any length, optionally keeping the input waveform outside the regenerated frames.
 
         The input is exactly one of ``wav`` (B, N), N a multiple of 512, encoded once as a whole (z = the scaled
@@ -256,6 +294,14 @@ class AudioLCMPipeline:
         call on its W frames with the mask still to do and the seeds ``recipe.window_seed(seed, k)``; what it
         produces is known context to the next window.  Frames of mask 0 keep the input latent exactly; an empty mask
         runs no DiT call.
+
+        ``joint=True``: the regenerated frames are denoised jointly instead (``joint_edit_regions`` on the union mask
+        with the same W and overlap): region r of regenerated frames and their context is one
+        ``sample_joint(init=z[:, :, a:b], mask=mask[:, a:b], ...)`` call with the seeds ``recipe.window_seed(seed, r)``:
+        S DiT calls per region and clip whatever its length, and every window sees both neighbours.  It is another
+        sampler, not another route to the same clip; a region of one window is ``sample_edit`` on that slice.
+        ``joint_clips_per_call`` is ``sample_joint``'s ``clips_per_call``.  ValueError for a region of more than 32
+        windows.  Everything after the latent (``keep_original``, ``rate``, halo and fade) is the same for both forms.
 
         ``keep_original=False``: the whole clip is decoded; returns latent, mel, wav.  ``keep_original=True`` (needs
         ``wav``): only ``paste_regions(union, halo_frames)`` are decoded, each blended into a copy of ``wav`` by one
@@ -313,7 +359,7 @@ class AudioLCMPipeline:
         wav16 = kernels.resample(wav, rate, SAMPLE_RATE) if native else wav     # for the encoder only
         assert wav16 is None or wav16.shape[1] == L * FRAME_SAMPLES
         z = self._edit_long_latent(cond, seeds, wav16, latent, mask, union, W, overlap, strength, sample_posterior,
-                                   steps, unconditional, cfg_scale)
+                                   steps, unconditional, cfg_scale, joint, joint_clips_per_call)
         if not keep_original:
             return dict(latent=z, **self.decode(z))
         out = wav.clone()
@@ -322,9 +368,10 @@ class AudioLCMPipeline:
         return dict(latent=z, wav=out, regions=regions)
 
     def _edit_long_latent(self, cond, seeds, wav, latent, mask, union, W, overlap, strength, sample_posterior, steps,
-                          unconditional, cfg_scale):
+                          unconditional, cfg_scale, joint=False, joint_clips_per_call=1):
         """The latent of ``edit_long``: ``wav`` (B, L * 512) on the device or ``latent`` (B, C, L), ``mask`` (B, L) on
-        the host or None, ``union`` its per-frame any over the batch, W the window length."""
+        the host or None, ``union`` its per-frame any over the batch, W the window length.  ``joint``: one
+        ``sample_joint`` call per region of ``joint_edit_regions`` instead of one ``sample_edit`` call per window."""
         from . import kernels
         dev = torch.device("cuda")
         S = steps or self.steps
@@ -344,16 +391,24 @@ class AudioLCMPipeline:
                                     scale=float(self.model.scale_factor), want_x=False)[0]
         else:
             z = latent.to(dev).float().clone()
-        if any(union):
+        kw = dict(guidance_scale=self.guidance_scale, original_inference_steps=self.original_inference_steps,
+                  unconditional_conditioning=unconditional, unconditional_guidance_scale=cfg_scale)
+        if joint:
+            m = torch.ones((B, L)) if mask is None else mask.cpu()
+            ov = W // 2 if overlap is None else overlap
+            for r, (a, b, starts, Wr) in enumerate(joint_edit_regions(union, W, ov)):
+                rseeds = None if seeds is None else [recipe.window_seed(sd, r) for sd in seeds]
+                zr, _ = self.sampler.sample_joint(S=S, conditioning=cond, length=b - a, starts=starts, window=Wr,
+                                                  overlap=ov, seeds=rseeds, clips_per_call=joint_clips_per_call,
+                                                  init=z[:, :, a:b].contiguous(), mask=m[:, a:b], strength=strength,
+                                                  **kw)
+                z[:, :, a:b] = zr
+        elif any(union):
             m = torch.ones((B, L)) if mask is None else mask.cpu().clone()
             for k, s in enumerate(edit_windows(union, W, overlap)[0]):
                 wseeds = None if seeds is None else [recipe.window_seed(sd, k) for sd in seeds]
                 zk, _ = self.sampler.sample_edit(S=S, conditioning=cond, init=z[:, :, s:s + W].contiguous(),
-                                                 mask=m[:, s:s + W], strength=strength, seeds=wseeds,
-                                                 guidance_scale=self.guidance_scale,
-                                                 original_inference_steps=self.original_inference_steps,
-                                                 unconditional_conditioning=unconditional,
-                                                 unconditional_guidance_scale=cfg_scale)
+                                                 mask=m[:, s:s + W], strength=strength, seeds=wseeds, **kw)
                 z[:, :, s:s + W] = zk
                 m[:, s:s + W] = 0.0
         return z
@@ -379,14 +434,27 @@ class AudioLCMPipeline:
         cropped to the DiT's length limit and encoded once, the posterior is expanded to the batch, and ``edit`` makes
         the whole clip again, resampled to the plan's output rate and brought to the plan's level
         (``audio_in.finish_output``).  Keep-original: ``edit_long`` at the plan's rate on the whole recording, cropped
-        to the input's sample count; no whole-clip mel is decoded."""
+        to the input's sample count; no whole-clip mel is decoded.  With ``plan.joint`` the frames to regenerate are
+        denoised jointly, and a variation or an inpainting is ``edit_long(joint=True)`` on the whole recording instead
+        of a crop.  Extend: ``extend`` on the recording's whole frames, cropped to the plan's sample count."""
         B = cond.shape[0]
+        if plan.mode == "extend":
+            wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
+            out = self.extend(cond, seeds, wav, plan.extend_frames, fade_samples=plan.fade)
+            return out["wav"][:, :plan.n_out], plan.out_rate, None
         if plan.mode == "keep_original":
             wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
             mask = np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
             out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, keep_original=True, rate=plan.rate,
-                                 fade_samples=plan.fade)
+                                 fade_samples=plan.fade, joint=plan.joint)
             return out["wav"][:, :plan.n_samples], plan.out_rate, None
+        if plan.joint:
+            T = plan.samples.size // plan.frame_samples
+            wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
+            mask = None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
+            out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, joint=True)
+            wav, rate = finish_output(out["wav"], plan.out_rate, plan.level)
+            return wav, rate, out["mel"]
         from .models import DiagonalGaussianDistribution
         crop = self.model.unet.diffusion_model.cfg.max_latent_len * plan.frame_samples
         post = self._encode(plan.samples[:crop])
@@ -397,22 +465,84 @@ class AudioLCMPipeline:
         wav, rate = finish_output(out["wav"], plan.out_rate, plan.level)
         return wav, rate, out["mel"]
 
+    @torch.no_grad()
+    def extend(self, cond: torch.Tensor, seeds: Optional[Sequence[int]], wav, extra_frames: int,
+               context_frames: Optional[int] = None, window: Optional[int] = None, overlap: Optional[int] = None,
+               fade_samples: Optional[int] = None, halo_frames: int = 32, steps: Optional[int] = None,
+               joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
+        """Continues a recording: ``wav`` (B, N) at 16 kHz, N = L0 * 512, comes back followed by ``extra_frames`` new
+        latent frames that continue it.
+
+        The recording is encoded alone (z_rec = the scaled posterior sample with e0 =
+        ``recipe.edit_noise(seeds, S, C, L0)[2]``, as in ``edit_long``) and followed by ``extra_frames`` frames of mask
+        1.  One ``sample_joint(init=..., mask=..., strength=1.0)`` call denoises the region [max(L0 - context, 0),
+        L0 + extra) jointly on ``long_windows``' plan (W = ``window`` or latent_shape[1], ``overlap`` = W // 2 by
+        default, ``context_frames`` = ``overlap`` by default; seeds ``recipe.window_seed(seed, 0)``): the last
+        ``context`` frames of the recording are known context to every window that covers them, the new frames start
+        from pure noise, and a continuation of any length costs S DiT calls per clip.  The frames [max(L0 -
+        ``halo_frames``, 0), L0 + extra) are decoded and blended into ``cat(wav, zeros)`` by one
+        ``kernels.wave_paste``: the recording's samples are its own bit for bit up to ``fade_samples`` (default 512)
+        before the junction at sample N, the raised-cosine fade closes the junction, and from the junction on
+        everything is generated.  ``halo_frames`` * 512 >= ``fade_samples`` is required unless the decode starts at
+        frame 0.
+
+        Returns latent (B, C, L0 + extra; the first L0 frames are z_rec), wav (B, (L0 + extra) * 512) and region
+        (a, L0 + extra).  ValueError for ``extra_frames`` < 1, an empty recording, or a region of more than 32
+        windows."""
+        from . import kernels
+        dev = torch.device("cuda")
+        S = steps or self.steps
+        wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
+        if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES or wav.shape[1] < FRAME_SAMPLES:
+            raise ValueError(f"`wav` is (B, N) with N a multiple of {FRAME_SAMPLES} and at least one frame")
+        extra = int(extra_frames)
+        if extra < 1:
+            raise ValueError(f"extra_frames must be at least 1, got {extra_frames}")
+        B, L0 = wav.shape[0], wav.shape[1] // FRAME_SAMPLES
+        L = L0 + extra
+        W = window or self.latent_shape[1]
+        ov = W // 2 if overlap is None else overlap
+        context = ov if context_frames is None else int(context_frames)
+        if context < 0:
+            raise ValueError("context_frames must not be negative")
+        a = max(L0 - context, 0)
+        spans, Wr = _long_windows(L - a, W, ov)
+        if len(spans) > JOINT_MAX_WINDOWS:
+            raise ValueError(f"the region of frames {a} .. {L} needs {len(spans)} windows of {Wr} frames: at most "
+                             f"{JOINT_MAX_WINDOWS} are denoised jointly")
+        fade = FRAME_SAMPLES if fade_samples is None else int(fade_samples)
+        if not 0 <= fade <= kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES:
+            raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES}")
+        h0 = max(L0 - int(halo_frames), 0)
+        if h0 > 0 and halo_frames * FRAME_SAMPLES < fade:
+            raise ValueError(f"halo_frames * 512 must be at least the fade's {fade} samples: the fade must end inside "
+                             "the decoded region")
+        post = self._encode(wav)
+        Cc = post.parameters.shape[1] // 2
+        e0 = (recipe.edit_noise(seeds, S, Cc, L0)[2].to(dev) if seeds is not None
+              else torch.randn((B, Cc, L0), device=dev))
+        z_rec = kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
+                                    scale=float(self.model.scale_factor), want_x=False)[0]
+        z = torch.cat([z_rec, torch.zeros((B, Cc, extra), device=dev)], 2)
+        m = torch.zeros((B, L), device=dev)
+        m[:, L0:] = 1.0
+        rseeds = None if seeds is None else [recipe.window_seed(sd, 0) for sd in seeds]
+        zr, _ = self.sampler.sample_joint(S=S, conditioning=cond, length=L - a, starts=[s for s, _ in spans],
+                                          window=Wr, overlap=ov, seeds=rseeds, clips_per_call=joint_clips_per_call,
+                                          init=z[:, :, a:].contiguous(), mask=m[:, a:].contiguous(), strength=1.0,
+                                          guidance_scale=self.guidance_scale,
+                                          original_inference_steps=self.original_inference_steps)
+        z[:, :, a:] = zr
+        gen = self.decode(z[:, :, h0:].contiguous())["wav"].contiguous()
+        out = torch.cat([wav, torch.zeros((B, extra * FRAME_SAMPLES), device=dev)], 1)
+        kernels.wave_paste(out, gen, m, gen_start=h0 * FRAME_SAMPLES, fade_samples=fade, out=out)
+        return dict(latent=z, wav=out, region=(a, L))
+
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
         """([(start, known)], window length) of ``generate_long``: window k covers frames start .. start + window, of
         which the first ``known`` are already generated.  The stride is window - overlap; the last window is shifted
         back to end at latent_len when the stride does not divide; a clip no longer than one window is that one window."""
-        window = window or self.latent_shape[1]
-        overlap = window // 2 if overlap is None else overlap
-        if not 0 < overlap < window:
-            raise ValueError("need 0 < overlap < window")
-        if latent_len <= window:
-            return [(0, 0)], latent_len
-        spans, end = [(0, 0)], window
-        while end < latent_len:
-            start = min(end - overlap, latent_len - window)
-            spans.append((start, end - start))
-            end = start + window
-        return spans, window
+        return _long_windows(latent_len, window or self.latent_shape[1], overlap)
 
     @torch.no_grad()
     def generate_long(self, cond: torch.Tensor, seeds: Sequence[int], latent_len: int, window: Optional[int] = None,

@@ -311,6 +311,24 @@ int alcm_lcm_step_joint(const float* x, const float* eps_cond, const float* eps_
                         const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
                         float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
                         alcm_stream_t stream);
+/* alcm_lcm_step_joint_edit: alcm_lcm_step_joint with a known latent blended in, as alcm_lcm_step_edit does for one
+ * window (joint inpainting, variation and extension of a recording; the same kernel body).  The arguments are
+ * alcm_lcm_step_joint's plus z0 (B, C, L) and mask (B, L) in [0, 1], 1 = regenerate.  Per element (b, c, t):
+ *   d  = alcm_lcm_step_joint's value, bit for bit (one covering window: alcm_lcm_step's bits; several: the first
+ *        product rounded alone, fmaf for the further ones in ascending k);
+ *   d' = m * d + (1 - m) * z0[b, c, t] with m = mask[b, t]  (m = 1 gives d and m = 0 gives z0, bit for bit);
+ *   denoised_out = d',  prev_out = noise ? sqrt_a_prev * d' + sqrt_b_prev * noise : d',
+ *   xw_out[k * B + b, c, t - starts[k]] = prev for every covering k.
+ * With one window (K = 1) prev_out and denoised_out are alcm_lcm_step_edit's bits.  Any output may be NULL, not all
+ * three.  There is no gather-only form: the first DiT input comes from alcm_lcm_step_joint with eps_cond = NULL.  No
+ * atomics: an element's bits do not depend on B, the grid or the access width.  16-byte accesses under
+ * alcm_lcm_step_joint's conditions with z0 and mask 16-byte aligned too, element accesses otherwise.
+ * ALCM_E_INVALID for everything alcm_lcm_step_joint refuses and for a null eps_cond, z0 or mask.  B, C, L or W of 0: no
+ * launch.  A ring form does not exist yet. */
+int alcm_lcm_step_joint_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                             const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
+                             const float* z0, const float* mask, float* prev_out, float* denoised_out,
+                             float* xw_out, int B, int C, int L, int W, alcm_stream_t stream);
 /* alcm_lcm_step_ring: alcm_lcm_step_joint on a ring of L frames instead of a line (seamless loops; the same kernel
  * body).  Arguments, outputs and the eps-less gather form are alcm_lcm_step_joint's.  Window k covers frame t at the
  * offset o = t - starts[k], plus L when that is negative, if o < W; eps and xw_out are read and written at that offset,

@@ -10,6 +10,7 @@ Used to A/B kernel variants in one process and as the target of 
     python scripts/microbench.py loudness   # the loudness launches beside alcm_resample 16 -> 48 kHz
     python scripts/microbench.py editlong   # 30 s keep-original edit: region decode + paste vs whole-clip decode
     python scripts/microbench.py longjoint  # 30 s long-form clip: chained windows vs windows denoised jointly
+    python scripts/microbench.py editjoint  # 30 s recording: edit_long window by window vs jointly; extend
     python scripts/microbench.py loop       # 10 s and 30 s seamless loops vs open clips of the same length
 """
 import os
@@ -667,6 +668,52 @@ def bench_longjoint(L=936, reps=7):
                       f"({r['launches']} launches)  {r['bytes'] / r['launches'] / 1e6:6.2f} MB per launch", flush=True)
 
 
+def bench_editjoint(L=936, reps=7):
+    """edit_long on a 30 s recording (936 frames, B = 1, mixed policy) window by window against joint=True: a 2 s span
+    and a 12 s span with keep_original, and a variation of the whole clip; then extend of a 10 s recording by 20 s
+    beside generate_long(joint=True) of the same 30 s.  The forms alternate in one process, median of 7 calls after 2
+    warm-ups, host clock around a device synchronise; then the joint edit step kernel by the library's per-launch
+    events beside the open one's"""
+    from audiolcm_amd import recipe
+    from audiolcm_amd.pipeline import AudioLCMPipeline
+    pipe = AudioLCMPipeline.from_recipe(0, split=True, encoder=True)
+    pipe.set_split("mixed")
+    ctx, seeds = recipe.synthetic_context(1).cuda(), [0]
+    wav = torch.rand((1, L * 512), device="cuda") - 0.5
+    rec = wav[:, :312 * 512].contiguous()
+    cases = {"2 s span, keep_original": dict(mask=_span_mask(1, L, 14.0, 16.0), keep_original=True),
+             "12 s span, keep_original": dict(mask=_span_mask(1, L, 9.0, 21.0), keep_original=True),
+             "variation of the whole clip": dict()}
+    forms = {}
+    for name, kw in cases.items():
+        for joint in (False, True):
+            forms[f"{name}, joint={joint!s}"] = (
+                lambda kw=kw, joint=joint: pipe.edit_long(ctx, seeds, wav=wav, joint=joint, **kw))
+    forms["extend 10 s by 20 s"] = lambda: pipe.extend(ctx, seeds, rec, L - 312)
+    forms["generate_long(joint=True), 30 s"] = lambda: pipe.generate_long(ctx, seeds, L, joint=True)
+    times = {k: [] for k in forms}
+    for i in range(2 + reps):
+        for k, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if i >= 2:
+                times[k].append((time.perf_counter() - t0) * 1e3)
+    for k in forms:
+        t = sorted(times[k])
+        print(f"editjoint L={L} B=1 {k:42s}: median {t[len(t) // 2]:7.2f} ms  min {t[0]:7.2f}  max {t[-1]:7.2f} "
+              f"({len(t)} calls)", flush=True)
+    _hip.profile_begin()
+    for _ in range(reps):
+        pipe.edit_long(ctx, seeds, wav=wav, joint=True)
+        pipe.generate_long(ctx, seeds, L, joint=True)
+    for r in _hip.profile_end():
+        if "lcm_step_joint" in r["name"]:
+            print(f"editjoint L={L} B=1 {r['name']}: {r['total_ms'] / r['launches'] * 1e3:6.1f} us by events "
+                  f"({r['launches']} launches)  {r['bytes'] / r['launches'] / 1e6:6.2f} MB per launch", flush=True)
+
+
 def bench_loop(reps=7):
     """generate_loop on a 10 s and a 30 s loop (312 and 936 frames, mixed policy) at B = 1 against the open clip of the
     same length: ``generate`` (one window; 10 s only, the DiT's length limit) and ``generate_long(joint=True)``,
@@ -710,4 +757,4 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["op", "conv", "act"]
     spin(float(os.environ.get("SPIN", "3")))
     for w in which:
-        {"resample": bench_resample, "loudness": bench_loudness, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "loop": bench_loop, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()
+        {"resample": bench_resample, "loudness": bench_loudness, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "editjoint": bench_editjoint, "loop": bench_loop, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()

@@ -343,24 +343,34 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
                    wn: torch.Tensor, eps_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
                    want_prev: bool = True, want_den: bool = True, want_xw: bool = True,
                    prev: Optional[torch.Tensor] = None, den: Optional[torch.Tensor] = None,
-                   xw: Optional[torch.Tensor] = None, ring: bool = False):
+                   xw: Optional[torch.Tensor] = None, ring: bool = False, z0: Optional[torch.Tensor] = None,
+                   mask: Optional[torch.Tensor] = None):
     """``lcm_step`` on one long latent ``x`` (B, C, L) whose K overlapping windows of W frames at ``starts`` went through
     the DiT as one batch: ``eps`` (K * B, C, W), row k * B + b.  Where windows overlap their denoised estimates are
-    averaged with the normalised weights ``wn`` (K, W) (``pipeline.joint_weights``); a frame under one window is the
+    averaged with the normalised weights ``wn`` (K, W) (``windows.window_weights``); a frame under one window is the
     plain step bit for bit (alcm_lcm_step_joint).  Returns (prev, denoised, xw): the two (B, C, L) results and prev
     gathered back into window layout (K * B, C, W), the next DiT input; a result not wanted is None, ``prev`` / ``den``
     / ``xw`` give the tensors to write.  ``eps`` None: only x itself is gathered into xw.  One launch.
     ``ring``: the L frames are a ring (alcm_lcm_step_ring): window k covers frame t at the offset (t - starts[k]) mod L
-    when that is below W, and ``wn`` is ``pipeline.ring_weights``."""
+    when that is below W, and ``wn`` is the ring's table.
+    ``z0`` and ``mask``: the known latent ``z0`` (B, C, L) is blended into the joint estimate per frame, as
+    ``lcm_step_edit`` does for one window: ``mask`` (B, L) in [0, 1], 1 = take the joint step's value, 0 = keep z0
+    (alcm_lcm_step_joint_edit).  ``eps`` is required then, and a ring cannot take them (ValueError)."""
     B, Cc, L = x.shape
     K, W = wn.shape
+    edit = z0 is not None
+    if ring and edit:
+        raise ValueError("a ring cannot take `z0`: joint editing exists on a line only")
     assert len(starts) == K and x.is_contiguous() and wn.is_contiguous()
+    assert edit == (mask is not None) and not (edit and eps is None)
     if eps is None:
         want_prev = want_den = False
     else:
         assert tuple(eps.shape) == (K * B, Cc, W) and eps.is_contiguous()
         assert eps_uncond is None or (eps_uncond.shape == eps.shape and eps_uncond.is_contiguous())
         assert noise is None or (noise.shape == x.shape and noise.is_contiguous())
+    if edit:
+        assert z0.shape == x.shape and z0.is_contiguous() and tuple(mask.shape) == (B, L) and mask.is_contiguous()
     if want_prev and prev is None:
         prev = torch.empty_like(x)
     if want_den and den is None:
@@ -369,40 +379,17 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
         xw = torch.empty((K * B, Cc, W), device=x.device, dtype=torch.float32)
     arr = (C.c_float * 6)(*[float(c) for c in coeffs])
     st = (C.c_int * K)(*[int(s) for s in starts])
-    entry = lib().alcm_lcm_step_ring if ring else lib().alcm_lcm_step_joint
-    check(entry(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K, ptr(wn), ptr(prev), ptr(den),
-                ptr(xw), B, Cc, L, W, stream_handle()), "lcm_step_ring" if ring else "lcm_step_joint")
+    name = "lcm_step_joint_edit" if edit else "lcm_step_ring" if ring else "lcm_step_joint"
+    known = (ptr(z0), ptr(mask)) if edit else ()
+    check(getattr(lib(), "alcm_" + name)(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K,
+                                         ptr(wn), *known, ptr(prev), ptr(den), ptr(xw), B, Cc, L, W, stream_handle()),
+          name)
     return prev, den, xw
 
 
-def lcm_step_joint_edit(x: torch.Tensor, eps: torch.Tensor, noise: Optional[torch.Tensor], coeffs, starts,
-                        wn: torch.Tensor, z0: torch.Tensor, mask: torch.Tensor,
-                        eps_uncond: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, want_prev: bool = True,
-                        want_den: bool = True, want_xw: bool = True, prev: Optional[torch.Tensor] = None,
-                        den: Optional[torch.Tensor] = None, xw: Optional[torch.Tensor] = None):
-    """``lcm_step_joint`` with the known latent ``z0`` (B, C, L) blended into the joint estimate per frame, as
-    ``lcm_step_edit`` does for one window: ``mask`` (B, L) in [0, 1], 1 = take the joint step's value, 0 = keep z0
-    (alcm_lcm_step_joint_edit).  Returns (prev, denoised, xw) as ``lcm_step_joint``; ``eps`` is required (the first
-    windows are gathered by ``lcm_step_joint(x, None, ...)``).  One launch."""
-    B, Cc, L = x.shape
-    K, W = wn.shape
-    assert len(starts) == K and x.is_contiguous() and wn.is_contiguous()
-    assert tuple(eps.shape) == (K * B, Cc, W) and eps.is_contiguous()
-    assert eps_uncond is None or (eps_uncond.shape == eps.shape and eps_uncond.is_contiguous())
-    assert noise is None or (noise.shape == x.shape and noise.is_contiguous())
-    assert z0.shape == x.shape and z0.is_contiguous() and tuple(mask.shape) == (B, L) and mask.is_contiguous()
-    if want_prev and prev is None:
-        prev = torch.empty_like(x)
-    if want_den and den is None:
-        den = torch.empty_like(x)
-    if want_xw and xw is None:
-        xw = torch.empty((K * B, Cc, W), device=x.device, dtype=torch.float32)
-    arr = (C.c_float * 6)(*[float(c) for c in coeffs])
-    st = (C.c_int * K)(*[int(s) for s in starts])
-    check(lib().alcm_lcm_step_joint_edit(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K,
-                                         ptr(wn), ptr(z0), ptr(mask), ptr(prev), ptr(den), ptr(xw), B, Cc, L, W,
-                                         stream_handle()), "lcm_step_joint_edit")
-    return prev, den, xw
+def lcm_step_joint_edit(x, eps, noise, coeffs, starts, wn, z0: torch.Tensor, mask: torch.Tensor, **kw):
+    """``lcm_step_joint`` in its edit form, ``z0`` and ``mask`` required."""
+    return lcm_step_joint(x, eps, noise, coeffs, starts, wn, z0=z0, mask=mask, **kw)
 
 
 def latent_init(noise: Optional[torch.Tensor], keep=(1.0, 0.0), regen=(0.0, 1.0), moments: Optional[torch.Tensor] = None,

@@ -20,7 +20,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import _hip, kernels, recipe, schedule
+from . import _hip, kernels, recipe, schedule, windows
 from ._hip import check, lib, ptr, stream_handle
 from .config import instantiate_from_config
 from .models import AutoencoderKL, ConcatDiT2MLP, DiagonalGaussianDistribution
@@ -150,6 +150,17 @@ def _h2d(t: torch.Tensor, dev) -> torch.Tensor:
     return t.pin_memory().to(dev, non_blocking=True)
 
 
+_weights_dev = {}
+
+
+def window_weights_device(starts, W: int, L: int, overlap: int, ring: bool, device) -> torch.Tensor:
+    """``windows.window_weights(...)`` on ``device``, uploaded once per argument tuple and device."""
+    key = (tuple(int(s) for s in starts), int(W), int(L), int(overlap), bool(ring), torch.device(device))
+    if key not in _weights_dev:
+        _weights_dev[key] = torch.from_numpy(windows.window_weights(*key[:5]).copy()).to(device)
+    return _weights_dev[key]
+
+
 class LCMSampler:
     """LCM multistep sampler (scheduling_lcm.py) over the HIP DiT and the fused step kernel."""
 
@@ -196,6 +207,57 @@ class LCMSampler:
             out = torch.nn.functional.pad(out, (0, 1))
         return out
 
+    @staticmethod
+    def _cond(conditioning):
+        """The conditioning tensor of a call: the reference passes it bare, or as the first entry of a dict of lists."""
+        cond = conditioning
+        if isinstance(cond, dict):
+            cond = cond[list(cond.keys())[0]]
+            while isinstance(cond, list):
+                cond = cond[0]
+        return cond
+
+    def _set_plan(self, plan) -> int:
+        """Takes the timesteps of ``plan`` (``schedule.sample_plan``); returns how many of its steps add noise."""
+        self.num_inference_steps = len(plan)
+        self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
+        return sum(1 for p in plan if p["add_noise"])
+
+    def _noise_start(self, plan, seeds, x_T, noise, B, Cc, T):
+        """The start of ``sample`` and of ``sample_joint`` from pure noise: takes ``plan`` (``_set_plan``) and returns
+        (x_T (B, C, T), the step noise or None), fp32 and contiguous on the device: per prompt from
+        ``recipe.prompt_noise`` with ``seeds``, else from the global device RNG; ``x_T`` / ``noise`` replace the
+        respective draw."""
+        dev = torch.device("cuda")
+        n_noise = self._set_plan(plan)
+        if seeds is not None:
+            # host draws (per-prompt generators), copied from pinned memory without blocking the host: a pageable
+            # copy waits for everything already queued on the stream, so each call used to start only after the
+            # previous call's vocoder had drained, with the GPU idle meanwhile (2.4 ms per bench step, rocprofv3
+            # kernel trace of profiles/r4v6)
+            xT_h, noise_h = recipe.prompt_noise(seeds, len(plan), Cc, T)
+            img = _h2d(xT_h, dev) if x_T is None else x_T
+            noise = _h2d(noise_h, dev) if noise is None else noise
+        else:
+            img = torch.randn((B, Cc, T), device=dev) if x_T is None else x_T
+            if noise is None and n_noise:
+                noise = torch.randn((n_noise, B, Cc, T), device=dev)
+        img = img.to(dev).float().contiguous()
+        noise = noise.to(dev).float().contiguous() if noise is not None else None
+        return img, noise
+
+    def _context(self, cond, guidance_scale, unconditional_conditioning, unconditional_guidance_scale):
+        """(cfg, cemb, w_emb): whether the DiT runs batch-doubled on [uc; c], the embedded context of those rows and
+        their guidance-scale embedding.  Step-invariant: once per call."""
+        dev = torch.device("cuda")
+        cfg = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
+        c = cond.to(dev).float()
+        if cfg:
+            c = torch.cat([unconditional_conditioning.to(dev).float(), c], 0)
+        cemb = self.model.unet.diffusion_model.embed_context(c)
+        w = torch.full((c.shape[0],), float(guidance_scale - 1), device=dev, dtype=torch.float32)  # (no host copy)
+        return cfg, cemb, self.get_guidance_scale_embedding(w, embedding_dim=256)
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None,
                img_callback=None, verbose=True, x_T=None, guidance_scale=5., original_inference_steps=50,
@@ -207,49 +269,24 @@ class LCMSampler:
         if len(shape) != 2:
             raise ValueError("audio latents are (C, T)")
         Cc, T = shape
-        dev = torch.device("cuda")
-        cond = conditioning
-        if isinstance(cond, dict):
-            cond = cond[list(cond.keys())[0]]
-            while isinstance(cond, list):
-                cond = cond[0]
+        cond = self._cond(conditioning)
         if cond.shape[0] != batch_size:
             print(f"Warning: Got {cond.shape[0]} conditionings but batch-size is {batch_size}")
         plan = schedule.sample_plan(S, original_inference_steps, timesteps)
-        self.num_inference_steps = len(plan)
-        self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
-        n_noise = sum(1 for p in plan if p["add_noise"])
-        if seeds is not None:
-            # host draws (per-prompt generators), copied from pinned memory without blocking the host: a pageable
-            # copy waits for everything already queued on the stream, so each call used to start only after the
-            # previous call's vocoder had drained, with the GPU idle meanwhile (2.4 ms per bench step, rocprofv3
-            # kernel trace of profiles/r4v6)
-            xT_h, noise_h = recipe.prompt_noise(seeds, len(plan), Cc, T)
-            img = _h2d(xT_h, dev) if x_T is None else x_T.to(dev)
-            noise = _h2d(noise_h, dev) if noise is None else noise
-        else:
-            img = x_T.to(dev).float() if x_T is not None else torch.randn((batch_size, Cc, T), device=dev)
-        if noise is None:
-            noise = torch.randn((n_noise, batch_size, Cc, T), device=dev) if n_noise else None
-        noise = noise.to(dev).float().contiguous() if noise is not None else None
+        img, noise = self._noise_start(plan, seeds, x_T, noise, batch_size, Cc, T)
         return self._run(plan, img, noise, cond, batch_size, guidance_scale, unconditional_conditioning,
                          unconditional_guidance_scale)
 
     def _run(self, plan, img, noise, cond, batch_size, guidance_scale, unconditional_conditioning,
              unconditional_guidance_scale, z0=None, mask=None):
-        """The step loop of ``sample`` and ``sample_edit``: img (B, C, T) at plan[0]'s noise level, noise[i] the noise of
-        step i.  With z0 / mask every step blends the denoised estimate with the known latent (alcm_lcm_step_edit)."""
+        """The step loop of ``sample`` and ``sample_edit``: img (B, C, T), fp32 and contiguous, at plan[0]'s noise level,
+        noise[i] the noise of step i.  With z0 / mask every step blends the denoised estimate with the known latent
+        (alcm_lcm_step_edit)."""
         dev = img.device
         dit: ConcatDiT2MLP = self.model.unet.diffusion_model
-        cfg = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
-        c = cond.to(dev).float()
-        if cfg:
-            c = torch.cat([unconditional_conditioning.to(dev).float(), c], 0)
-        cemb = dit.embed_context(c)
-        B2 = c.shape[0]
-        w = torch.full((B2,), float(guidance_scale - 1), device=dev, dtype=torch.float32)  # (no host copy)
-        w_emb = self.get_guidance_scale_embedding(w, embedding_dim=256)
-        img = img.contiguous().float().clone()  # never write into the caller's x_T
+        cfg, cemb, w_emb = self._context(cond, guidance_scale, unconditional_conditioning, unconditional_guidance_scale)
+        B2 = cemb.shape[0]
+        img = img.clone()  # never write into the caller's x_T
         n = img.numel()
         prev = torch.empty_like(img)
         denoised = torch.empty_like(img)
@@ -288,7 +325,7 @@ class LCMSampler:
         ``window`` frames at ``starts`` (``AudioLCMPipeline.long_windows``).  Every step runs the DiT on all windows of
         all clips (K * B rows, row k * B + b; [uc; c] doubled with guidance as in ``sample``) and then one
         alcm_lcm_step_joint: where windows overlap their denoised estimates are averaged with
-        ``pipeline.joint_weights(starts, window, length, overlap)``, the long latent is re-noised once, and the windows
+        ``windows.window_weights(starts, window, length, overlap, ring)``, the long latent is re-noised once, and the windows
         of the next step are cut from it.  No window waits for another one, and every window sees both neighbours.
 
         The DiT is called on the windows of ``clips_per_call`` clips at a time (at most ``JOINT_DIT_ROWS`` rows).  The
@@ -303,7 +340,7 @@ class LCMSampler:
         for bit); ``x_T`` / ``noise`` replace the respective draw; without seeds the global device RNG.
 
         ``ring``: the ``length`` frames are a ring (seamless loops): window k covers the frames (starts[k] + j) mod
-        length, the plan is ``pipeline.ring_weights`` (at least two windows: ``AudioLCMPipeline.loop_windows``) and the
+        length, the plan is the ring's table (at least two windows: ``AudioLCMPipeline.loop_windows``) and the
         step alcm_lcm_step_ring.  Each window is still an ordinary DiT call on ``window`` frames, and everything else is
         as above; rotating ``x_T`` and ``noise`` by a multiple of the windows' spacing rotates the result.
 
@@ -317,19 +354,14 @@ class LCMSampler:
         plain one.  With one window the result is ``sample_edit``'s bit for bit.  ``x_T`` is not used, and a ring
         cannot take ``init`` (ValueError): that kernel form does not exist yet.
         Returns (denoised, last sample) like ``sample``."""
-        from .pipeline import joint_weights_device, ring_weights_device
         self.make_schedule(verbose=False)
         dev = torch.device("cuda")
         dit: ConcatDiT2MLP = self.model.unet.diffusion_model
         W, L, K = int(window), int(length), len(starts)
         if W > dit.cfg.max_latent_len:
             raise ValueError(f"window {W} exceeds the DiT's {dit.cfg.max_latent_len} frames")
-        wn = (ring_weights_device if ring else joint_weights_device)(starts, W, L, overlap, dev)  # validates the plan
-        cond = conditioning
-        if isinstance(cond, dict):
-            cond = cond[list(cond.keys())[0]]
-            while isinstance(cond, list):
-                cond = cond[0]
+        wn = window_weights_device(starts, W, L, overlap, ring, dev)  # validates the plan
+        cond = self._cond(conditioning)
         B, Cc = cond.shape[0], dit.cfg.in_channels
         z0 = None
         if init is not None:
@@ -341,32 +373,14 @@ class LCMSampler:
                                                           posterior_noise, sample_posterior,
                                                           original_inference_steps, one_window=False)
             if mask is None:
-                z0 = None
+                z0 = None       # every frame is regenerated: the open step
         else:
             plan = schedule.sample_plan(S, original_inference_steps)
-            self.num_inference_steps = len(plan)
-            self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
-            n_noise = sum(1 for p in plan if p["add_noise"])
-            if seeds is not None:
-                xT_h, noise_h = recipe.prompt_noise(seeds, len(plan), Cc, L)
-                img = _h2d(xT_h, dev) if x_T is None else x_T.to(dev)
-                noise = _h2d(noise_h, dev) if noise is None else noise
-            else:
-                img = x_T.to(dev) if x_T is not None else torch.randn((B, Cc, L), device=dev)
-                if noise is None and n_noise:
-                    noise = torch.randn((n_noise, B, Cc, L), device=dev)
-            img = img.float().contiguous()
-            noise = noise.to(dev).float().contiguous() if noise is not None else None
+            img, noise = self._noise_start(plan, seeds, x_T, noise, B, Cc, L)
         if tuple(img.shape) != (B, Cc, L):
             raise ValueError(f"x_T must be (B, C, length) = {(B, Cc, L)}, got {tuple(img.shape)}")
 
-        cfg = unconditional_conditioning is not None and unconditional_guidance_scale != 1.0
-        c = cond.to(dev).float()
-        if cfg:
-            c = torch.cat([unconditional_conditioning.to(dev).float(), c], 0)
-        cemb = dit.embed_context(c)
-        w = torch.full((c.shape[0],), float(guidance_scale - 1), device=dev, dtype=torch.float32)
-        w_emb = self.get_guidance_scale_embedding(w, embedding_dim=256)
+        cfg, cemb, w_emb = self._context(cond, guidance_scale, unconditional_conditioning, unconditional_guidance_scale)
         # DiT calls: the windows of g clips each, rows k * g + j ([uc; c] halves with guidance), so that the rows of a
         # call, and with them the DiT's kernel plan, do not depend on the batch; one window is ``sample``'s own call
         per_clip = K * (2 if cfg else 1)
@@ -399,13 +413,9 @@ class LCMSampler:
                 if cfg or not whole:
                     ec.view(K, B, Cc, W)[:, b0:b1] = e[-n:].view(K, b1 - b0, Cc, W)
             last = i + 1 == len(plan)
-            kw = dict(eps_uncond=eu, cfg_scale=float(unconditional_guidance_scale), prev=outs[i % 2], den=denoised,
-                      xw=None if last else xw, want_xw=not last)
-            nz = noise[i] if p["add_noise"] else None
-            if z0 is not None:
-                kernels.lcm_step_joint_edit(img, ec, nz, p["coeffs"], starts, wn, z0, mask, **kw)
-            else:
-                kernels.lcm_step_joint(img, ec, nz, p["coeffs"], starts, wn, ring=ring, **kw)
+            kernels.lcm_step_joint(img, ec, noise[i] if p["add_noise"] else None, p["coeffs"], starts, wn, eps_uncond=eu,
+                                   cfg_scale=float(unconditional_guidance_scale), prev=outs[i % 2], den=denoised,
+                                   xw=None if last else xw, want_xw=not last, ring=ring, z0=z0, mask=mask)
             img = outs[i % 2]
         return denoised, img
 
@@ -428,14 +438,9 @@ class LCMSampler:
         RNG: with ``seeds``, per prompt n0, the step noise and e0 from ``recipe.edit_noise``; ``init_noise``, ``noise``
         and ``posterior_noise`` replace the respective draw; without seeds the global device RNG.
         Returns (denoised, last sample) like ``sample``."""
-        cond = conditioning
-        if isinstance(cond, dict):
-            cond = cond[list(cond.keys())[0]]
-            while isinstance(cond, list):
-                cond = cond[0]
         plan, img, z0, noise, mask = self._edit_start(S, init, mask, strength, seeds, noise, init_noise,
                                                       posterior_noise, sample_posterior, original_inference_steps)
-        return self._run(plan, img, noise, cond, img.shape[0], guidance_scale, unconditional_conditioning,
+        return self._run(plan, img, noise, self._cond(conditioning), img.shape[0], guidance_scale, unconditional_conditioning,
                          unconditional_guidance_scale, z0=z0 if mask is not None else None, mask=mask)
 
     def _edit_start(self, S, init, mask, strength, seeds, noise, init_noise, posterior_noise, sample_posterior,
@@ -469,9 +474,7 @@ class LCMSampler:
                 raise ValueError(f"mask must be (B, T) = {(B, T)}, got {tuple(mask.shape)}")
             mask = mask.to(dev).contiguous()
         plan = schedule.sample_plan(S, original_inference_steps, strength=strength)
-        self.num_inference_steps = len(plan)
-        self.timesteps = torch.tensor([p["t"] for p in plan], dtype=torch.long)
-        n_noise = sum(1 for p in plan if p["add_noise"])
+        n_noise = self._set_plan(plan)
         e0 = posterior_noise if post is not None and sample_posterior else None
         draw_e0 = post is not None and sample_posterior and posterior_noise is None
         if seeds is not None:

@@ -8,197 +8,27 @@ SURVEY.md §8f) and per-prompt seeds.
 """
 from __future__ import annotations
 
-import functools
 from typing import Dict, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import recipe
+from . import recipe, windows
 from .audio_in import FRAME_SAMPLES, SAMPLE_RATE, EditPlan, finish_output, frame_samples_of, spans_to_mask
 from .lcm import LCM_audio, LCMSampler
-from .models import AutoencoderKL, BigVGAN, ConcatDiT2MLP
-
-
-def edit_windows(union, window: int, overlap: Optional[int] = None):
-    """(window starts, window length W) of ``edit_long`` for a clip of L = len(union) latent frames: ``union[t]`` is
-    true where any clip of the batch regenerates frame t.  W = min(window, L); ``overlap`` defaults to W // 2.  Each
-    window starts ``overlap`` frames before the first frame still to do (clamped to the clip) and clears its W frames; a
-    span longer than a window is continued by the next one, which sees the frames already produced as known context."""
-    todo = [bool(v) for v in union]
-    L = len(todo)
-    W = min(window, L)
-    overlap = W // 2 if overlap is None else overlap
-    if not 0 < overlap < W:
-        raise ValueError("need 0 < overlap < window")
-    starts = []
-    while any(todo):
-        s = min(max(todo.index(True) - overlap, 0), L - W)
-        starts.append(s)
-        todo[s:s + W] = [False] * W
-    return starts, W
-
-
-def paste_regions(union, halo: int):
-    """The latent-frame ranges [a, b) ``edit_long(keep_original=True)`` decodes: every maximal run [lo, hi) of
-    regenerated frames widened by ``halo`` frames either side, clamped to the clip; overlapping or touching ranges are
-    merged."""
-    todo = [bool(v) for v in union]
-    L = len(todo)
-    regions, t = [], 0
-    while t < L:
-        if not todo[t]:
-            t += 1
-            continue
-        hi = t
-        while hi < L and todo[hi]:
-            hi += 1
-        a, b = max(t - halo, 0), min(hi + halo, L)
-        if regions and a <= regions[-1][1]:
-            regions[-1] = (regions[-1][0], b)
-        else:
-            regions.append((a, b))
-        t = hi
-    return regions
-
-
-JOINT_MAX_WINDOWS = 32  # alcm_lcm_step_joint: the window starts travel in the kernel's arguments
-
-
-@functools.lru_cache(maxsize=None)
-def _joint_weights(starts: tuple, W: int, L: int, overlap: int) -> np.ndarray:
-    K = len(starts)
-    if not 1 <= K <= JOINT_MAX_WINDOWS:
-        raise ValueError(f"need 1 to {JOINT_MAX_WINDOWS} windows, got {K}")
-    if W < 1 or overlap < 0:
-        raise ValueError("need window >= 1 and overlap >= 0")
-    if starts[0] != 0:
-        raise ValueError("the first window must start at frame 0")
-    for a, b in zip(starts, starts[1:]):
-        if b <= a:
-            raise ValueError(f"window starts must ascend strictly, got {list(starts)}")
-        if b > a + W:
-            raise ValueError(f"frames {a + W} .. {b - 1} are under no window")
-    if starts[-1] + W != L:
-        raise ValueError(f"the last window must end at the clip's {L} frames, it ends at {starts[-1] + W}")
-    j = np.arange(W, dtype=np.float64)
-    w = np.minimum(1.0, (np.minimum(j, W - 1 - j) + 1.0) / (overlap + 1.0))
-    total = np.zeros(L, dtype=np.float64)
-    for s in starts:
-        total[s:s + W] += w
-    wn = np.stack([w / total[s:s + W] for s in starts], 0).astype(np.float32)
-    wn.setflags(write=False)
-    return wn
+from .models import AutoencoderKL, BigVGAN, ConcatDiT2MLP, DiagonalGaussianDistribution
+from .windows import JOINT_MAX_WINDOWS, edit_windows, joint_edit_regions, paste_regions  # noqa: F401  (public here too)
+from .windows import long_windows as _long_windows  # noqa: F401  (the name the joint-edit tests import)
 
 
 def joint_weights(starts, W: int, L: int, overlap: int) -> np.ndarray:
-    """The host plan of joint long-form denoising (``LCMSampler.sample_joint``, alcm_lcm_step_joint): the normalised
-    weights wn (K, W), fp32, of K windows of W frames at the frames ``starts`` (``long_windows``' starts) of a clip of L
-    frames.  The raw profile of a window is a linear ramp over ``overlap`` frames at each end,
-    w[j] = min(1, (min(j, W - 1 - j) + 1) / (overlap + 1)), strictly positive; wn[k][j] = w[j] over the sum of w over
-    the windows that cover frame starts[k] + j, evaluated in float64 and rounded to fp32 once: per frame the covering
-    weights sum to 1, and a frame under one window has exactly 1.0.  ValueError unless the starts begin at 0, ascend
-    strictly, leave no frame uncovered (starts[k] <= starts[k - 1] + W), end at L (starts[-1] + W == L) and are 1 to 32.
-    Built once per argument tuple; the array is read-only."""
-    return _joint_weights(tuple(int(s) for s in starts), int(W), int(L), int(overlap))
-
-
-def _long_windows(latent_len: int, window: int, overlap: Optional[int] = None):
-    """``AudioLCMPipeline.long_windows`` for a given window length."""
-    overlap = window // 2 if overlap is None else overlap
-    if not 0 < overlap < window:
-        raise ValueError("need 0 < overlap < window")
-    if latent_len <= window:
-        return [(0, 0)], latent_len
-    spans, end = [(0, 0)], window
-    while end < latent_len:
-        start = min(end - overlap, latent_len - window)
-        spans.append((start, end - start))
-        end = start + window
-    return spans, window
-
-
-def joint_edit_regions(union, window: int, overlap: Optional[int] = None):
-    """The host plan of ``edit_long(joint=True)`` for a clip of L = len(union) latent frames, ``union[t]`` true where
-    any clip of the batch regenerates frame t: a list of (a, b, starts, W).  Every maximal run of regenerated frames
-    is widened by ``overlap`` frames of known context either side and clamped to the clip, and touching or overlapping
-    ranges are merged (``paste_regions(union, overlap)``); region [a, b) of R = b - a frames is denoised jointly on
-    ``long_windows(R, window, overlap)``'s plan: K windows of W = min(window, R) frames at ``starts``, relative to a.
-    ``overlap`` defaults to min(window, L) // 2.  ValueError for a region of more than ``JOINT_MAX_WINDOWS``
-    windows."""
-    L = len(union)
-    overlap = min(window, L) // 2 if overlap is None else overlap
-    if not 0 < overlap < window:
-        raise ValueError("need 0 < overlap < window")
-    plan = []
-    for a, b in paste_regions(union, overlap):
-        spans, W = _long_windows(b - a, window, overlap)
-        if len(spans) > JOINT_MAX_WINDOWS:
-            raise ValueError(f"the region of frames {a} .. {b} needs {len(spans)} windows of {W} frames: at most "
-                             f"{JOINT_MAX_WINDOWS} are denoised jointly")
-        plan.append((a, b, [s for s, _ in spans], W))
-    return plan
-
-
-_joint_dev = {}
-
-
-def joint_weights_device(starts, W: int, L: int, overlap: int, device) -> torch.Tensor:
-    """``joint_weights(...)`` on ``device``, uploaded once per argument tuple and device."""
-    key = (tuple(int(s) for s in starts), int(W), int(L), int(overlap), torch.device(device))
-    if key not in _joint_dev:
-        _joint_dev[key] = torch.from_numpy(joint_weights(*key[:4]).copy()).to(device)
-    return _joint_dev[key]
-
-
-@functools.lru_cache(maxsize=None)
-def _ring_weights(starts: tuple, W: int, L: int, overlap: int) -> np.ndarray:
-    K = len(starts)
-    if not 2 <= K <= JOINT_MAX_WINDOWS:
-        raise ValueError(f"a ring needs 2 to {JOINT_MAX_WINDOWS} windows, got {K}")
-    if not 1 <= W <= L or overlap < 0:
-        raise ValueError(f"need 1 <= window <= the ring's {L} frames and overlap >= 0")
-    if starts[0] != 0:
-        raise ValueError("the first window must start at frame 0")
-    for a, b in zip(starts, starts[1:]):
-        if b <= a:
-            raise ValueError(f"window starts must ascend strictly, got {list(starts)}")
-        if b > a + W:
-            raise ValueError(f"frames {a + W} .. {b - 1} are under no window")
-    if starts[-1] >= L:
-        raise ValueError(f"the last window starts at {starts[-1]}, past the ring's {L} frames")
-    if starts[-1] + W < L:
-        raise ValueError(f"frames {starts[-1] + W} .. {L - 1} are under no window")
-    j = np.arange(W, dtype=np.float64)
-    w = np.minimum(1.0, (np.minimum(j, W - 1 - j) + 1.0) / (overlap + 1.0))
-    frames = [(s + np.arange(W)) % L for s in starts]
-    total = np.zeros(L, dtype=np.float64)
-    for f in frames:
-        total[f] += w     # W <= L: a window covers a frame at most once
-    wn = np.stack([w / total[f] for f in frames], 0).astype(np.float32)
-    wn.setflags(write=False)
-    return wn
+    """``windows.window_weights`` of a clip with two ends (``generate_long(joint=True)``, ``edit_long(joint=True)``)."""
+    return windows.window_weights(starts, W, L, overlap)
 
 
 def ring_weights(starts, W: int, L: int, overlap: int) -> np.ndarray:
-    """``joint_weights`` on a ring of L frames (``sample_joint(ring=True)``, alcm_lcm_step_ring): window k covers the
-    frames (starts[k] + j) mod L, j = 0 .. W - 1.  The same raw profile w[j] = min(1, (min(j, W - 1 - j) + 1) /
-    (overlap + 1)), normalised in float64 over the windows that cover frame (starts[k] + j) mod L and rounded to fp32
-    once.  ValueError unless there are 2 to 32 windows, 1 <= W <= L, the starts begin at 0, ascend strictly and stay
-    below L, and no frame is uncovered (starts[k] <= starts[k - 1] + W, and starts[-1] + W >= L for the gap across the
-    wrap).  Built once per argument tuple; the array is read-only."""
-    return _ring_weights(tuple(int(s) for s in starts), int(W), int(L), int(overlap))
-
-
-_ring_dev = {}
-
-
-def ring_weights_device(starts, W: int, L: int, overlap: int, device) -> torch.Tensor:
-    """``ring_weights(...)`` on ``device``, uploaded once per argument tuple and device."""
-    key = (tuple(int(s) for s in starts), int(W), int(L), int(overlap), torch.device(device))
-    if key not in _ring_dev:
-        _ring_dev[key] = torch.from_numpy(ring_weights(*key[:4]).copy()).to(device)
-    return _ring_dev[key]
+    """``windows.window_weights`` of a ring (``generate_loop``)."""
+    return windows.window_weights(starts, W, L, overlap, ring=True)
 
 
 class AudioLCMPipeline:
@@ -349,13 +179,11 @@ class AudioLCMPipeline:
         if keep_original:
             if fade_samples is None:
                 fade_samples = 1536 if native else 512
-            if not 0 <= fade_samples <= kernels.PASTE_MAX_FADE_FRAMES * F:
-                raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * F}")
-            fade16 = -(-fade_samples * SAMPLE_RATE // rate)
-            reach = fade16 + abs(rs.plan(SAMPLE_RATE, rate).first) + 1 if native else fade16
-            if halo_frames * FRAME_SAMPLES < reach and (native or any(a > 0 or b < L for a, b in regions)):
-                raise ValueError(f"halo_frames * 512 must be at least {reach}: the fade ({fade16} samples at 16 kHz), "
-                                 "and at another rate the resampling filter's reach, must end inside the decoded region")
+            reach = -(-fade_samples * SAMPLE_RATE // rate)      # the fade in 16 kHz samples
+            if native:
+                reach += abs(rs.plan(SAMPLE_RATE, rate).first) + 1
+            self._check_fade(fade_samples, F, halo_frames, reach,
+                             native or any(a > 0 or b < L for a, b in regions))
         wav16 = kernels.resample(wav, rate, SAMPLE_RATE) if native else wav     # for the encoder only
         assert wav16 is None or wav16.shape[1] == L * FRAME_SAMPLES
         z = self._edit_long_latent(cond, seeds, wav16, latent, mask, union, W, overlap, strength, sample_posterior,
@@ -367,13 +195,48 @@ class AudioLCMPipeline:
         self._paste_regions(out, z, pm, regions, fade_samples, rate, F)
         return dict(latent=z, wav=out, regions=regions)
 
+    @staticmethod
+    def _check_fade(fade: int, frame_samples: int, halo_frames: int, reach: int, inside: bool):
+        """The fade and halo rules of a paste: ``fade`` counts samples of ``frame_samples`` per latent frame and stays
+        within ``wave_paste``'s ramp; ``reach`` 16 kHz samples past a regenerated frame must lie inside the decoded
+        region wherever that region's edge is ``inside`` the clip."""
+        from . import kernels
+        if not 0 <= fade <= kernels.PASTE_MAX_FADE_FRAMES * frame_samples:
+            raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * frame_samples}")
+        if inside and halo_frames * FRAME_SAMPLES < reach:
+            raise ValueError(f"halo_frames * 512 must be at least {reach}: the fade, and at another rate the resampling "
+                             "filter's reach, must end inside the decoded region")
+
+    def _encode_latent(self, wav16, seeds, S, sample_posterior=True):
+        """``wav16`` (B, L * 512) on the device -> the scaled latent z (B, C, L) of the whole recording: the posterior's
+        sample with e0 = ``recipe.edit_noise(seeds, S, C, L)[2]`` (the global device RNG without seeds), or its mode
+        without ``sample_posterior``."""
+        from . import kernels
+        post = self._encode(wav16)
+        e0 = None
+        if sample_posterior:
+            B, Cc, L = wav16.shape[0], post.parameters.shape[1] // 2, wav16.shape[1] // FRAME_SAMPLES
+            e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(wav16.device) if seeds is not None
+                  else torch.randn((B, Cc, L), device=wav16.device))
+        return kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
+                                   scale=float(self.model.scale_factor), want_x=False)[0]
+
+    def _joint_region(self, z, m, region, r, cond, seeds, S, overlap, strength, clips_per_call, **kw):
+        """Denoises ``region`` = (a, b, starts, W) of the latent ``z`` (B, C, L) jointly, in place: one ``sample_joint``
+        call from z[:, :, a:b] under the mask m[:, a:b], with the seeds ``recipe.window_seed(seed, r)``; ``kw`` are the
+        sampler's guidance arguments."""
+        a, b, starts, W = region
+        rseeds = None if seeds is None else [recipe.window_seed(sd, r) for sd in seeds]
+        zr, _ = self.sampler.sample_joint(S=S, conditioning=cond, length=b - a, starts=starts, window=W,
+                                          overlap=overlap, seeds=rseeds, clips_per_call=clips_per_call,
+                                          init=z[:, :, a:b].contiguous(), mask=m[:, a:b], strength=strength, **kw)
+        z[:, :, a:b] = zr
+
     def _edit_long_latent(self, cond, seeds, wav, latent, mask, union, W, overlap, strength, sample_posterior, steps,
                           unconditional, cfg_scale, joint=False, joint_clips_per_call=1):
         """The latent of ``edit_long``: ``wav`` (B, L * 512) on the device or ``latent`` (B, C, L), ``mask`` (B, L) on
         the host or None, ``union`` its per-frame any over the batch, W the window length.  ``joint``: one
         ``sample_joint`` call per region of ``joint_edit_regions`` instead of one ``sample_edit`` call per window."""
-        from . import kernels
-        dev = torch.device("cuda")
         S = steps or self.steps
         L = len(union)
         B = wav.shape[0] if wav is not None else latent.shape[0]
@@ -381,28 +244,16 @@ class AudioLCMPipeline:
             return self._edit_latent(cond, seeds, wav, latent, mask, strength, sample_posterior, steps, unconditional,
                                      cfg_scale)
         if wav is not None:
-            post = self._encode(wav)
-            e0 = None
-            if sample_posterior:
-                Cc = post.parameters.shape[1] // 2
-                e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(dev) if seeds is not None
-                      else torch.randn((B, Cc, L), device=dev))
-            z = kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
-                                    scale=float(self.model.scale_factor), want_x=False)[0]
+            z = self._encode_latent(wav, seeds, S, sample_posterior)
         else:
-            z = latent.to(dev).float().clone()
+            z = latent.to(torch.device("cuda")).float().clone()
         kw = dict(guidance_scale=self.guidance_scale, original_inference_steps=self.original_inference_steps,
                   unconditional_conditioning=unconditional, unconditional_guidance_scale=cfg_scale)
         if joint:
             m = torch.ones((B, L)) if mask is None else mask.cpu()
             ov = W // 2 if overlap is None else overlap
-            for r, (a, b, starts, Wr) in enumerate(joint_edit_regions(union, W, ov)):
-                rseeds = None if seeds is None else [recipe.window_seed(sd, r) for sd in seeds]
-                zr, _ = self.sampler.sample_joint(S=S, conditioning=cond, length=b - a, starts=starts, window=Wr,
-                                                  overlap=ov, seeds=rseeds, clips_per_call=joint_clips_per_call,
-                                                  init=z[:, :, a:b].contiguous(), mask=m[:, a:b], strength=strength,
-                                                  **kw)
-                z[:, :, a:b] = zr
+            for r, region in enumerate(joint_edit_regions(union, W, ov)):
+                self._joint_region(z, m, region, r, cond, seeds, S, ov, strength, joint_clips_per_call, **kw)
         elif any(union):
             m = torch.ones((B, L)) if mask is None else mask.cpu().clone()
             for k, s in enumerate(edit_windows(union, W, overlap)[0]):
@@ -438,30 +289,26 @@ class AudioLCMPipeline:
         denoised jointly, and a variation or an inpainting is ``edit_long(joint=True)`` on the whole recording instead
         of a crop.  Extend: ``extend`` on the recording's whole frames, cropped to the plan's sample count."""
         B = cond.shape[0]
-        if plan.mode == "extend":
+
+        def span_mask(T):
+            return None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
+        if plan.mode in ("extend", "keep_original") or plan.joint:      # the whole recording, once per clip
             wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
-            out = self.extend(cond, seeds, wav, plan.extend_frames, fade_samples=plan.fade)
-            return out["wav"][:, :plan.n_out], plan.out_rate, None
-        if plan.mode == "keep_original":
-            wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
-            mask = np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
-            out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, keep_original=True, rate=plan.rate,
-                                 fade_samples=plan.fade, joint=plan.joint)
-            return out["wav"][:, :plan.n_samples], plan.out_rate, None
-        if plan.joint:
-            T = plan.samples.size // plan.frame_samples
-            wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
-            mask = None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
-            out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, joint=True)
-            wav, rate = finish_output(out["wav"], plan.out_rate, plan.level)
-            return wav, rate, out["mel"]
-        from .models import DiagonalGaussianDistribution
-        crop = self.model.unet.diffusion_model.cfg.max_latent_len * plan.frame_samples
-        post = self._encode(plan.samples[:crop])
-        T = post.mean.shape[2]
-        mask = None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
-        init = DiagonalGaussianDistribution(post.parameters.expand(B, -1, -1).contiguous())
-        out = self.edit(cond, seeds, latent=init, mask=mask, strength=strength)
+            if plan.mode == "extend":
+                out = self.extend(cond, seeds, wav, plan.extend_frames, fade_samples=plan.fade)
+                return out["wav"][:, :plan.n_out], plan.out_rate, None
+            if plan.mode == "keep_original":
+                mask = np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
+                out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, keep_original=True,
+                                     rate=plan.rate, fade_samples=plan.fade, joint=plan.joint)
+                return out["wav"][:, :plan.n_samples], plan.out_rate, None
+            out = self.edit_long(cond, seeds, wav=wav, mask=span_mask(plan.samples.size // plan.frame_samples),
+                                 strength=strength, joint=True)
+        else:
+            crop = self.model.unet.diffusion_model.cfg.max_latent_len * plan.frame_samples
+            post = self._encode(plan.samples[:crop])
+            init = DiagonalGaussianDistribution(post.parameters.expand(B, -1, -1).contiguous())
+            out = self.edit(cond, seeds, latent=init, mask=span_mask(post.mean.shape[2]), strength=strength)
         wav, rate = finish_output(out["wav"], plan.out_rate, plan.level)
         return wav, rate, out["mel"]
 
@@ -506,43 +353,25 @@ class AudioLCMPipeline:
         if context < 0:
             raise ValueError("context_frames must not be negative")
         a = max(L0 - context, 0)
-        spans, Wr = _long_windows(L - a, W, ov)
-        if len(spans) > JOINT_MAX_WINDOWS:
-            raise ValueError(f"the region of frames {a} .. {L} needs {len(spans)} windows of {Wr} frames: at most "
-                             f"{JOINT_MAX_WINDOWS} are denoised jointly")
+        spans, Wr = windows.long_windows(L - a, W, ov)
+        windows.check_region_windows(a, L, len(spans), Wr)
         fade = FRAME_SAMPLES if fade_samples is None else int(fade_samples)
-        if not 0 <= fade <= kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES:
-            raise ValueError(f"fade_samples must be in 0 .. {kernels.PASTE_MAX_FADE_FRAMES * FRAME_SAMPLES}")
         h0 = max(L0 - int(halo_frames), 0)
-        if h0 > 0 and halo_frames * FRAME_SAMPLES < fade:
-            raise ValueError(f"halo_frames * 512 must be at least the fade's {fade} samples: the fade must end inside "
-                             "the decoded region")
-        post = self._encode(wav)
-        Cc = post.parameters.shape[1] // 2
-        e0 = (recipe.edit_noise(seeds, S, Cc, L0)[2].to(dev) if seeds is not None
-              else torch.randn((B, Cc, L0), device=dev))
-        z_rec = kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
-                                    scale=float(self.model.scale_factor), want_x=False)[0]
-        z = torch.cat([z_rec, torch.zeros((B, Cc, extra), device=dev)], 2)
+        self._check_fade(fade, FRAME_SAMPLES, halo_frames, fade, h0 > 0)
+        z_rec = self._encode_latent(wav, seeds, S)
+        z = torch.cat([z_rec, torch.zeros((B, z_rec.shape[1], extra), device=dev)], 2)
         m = torch.zeros((B, L), device=dev)
         m[:, L0:] = 1.0
-        rseeds = None if seeds is None else [recipe.window_seed(sd, 0) for sd in seeds]
-        zr, _ = self.sampler.sample_joint(S=S, conditioning=cond, length=L - a, starts=[s for s, _ in spans],
-                                          window=Wr, overlap=ov, seeds=rseeds, clips_per_call=joint_clips_per_call,
-                                          init=z[:, :, a:].contiguous(), mask=m[:, a:].contiguous(), strength=1.0,
-                                          guidance_scale=self.guidance_scale,
-                                          original_inference_steps=self.original_inference_steps)
-        z[:, :, a:] = zr
+        self._joint_region(z, m, (a, L, [s for s, _ in spans], Wr), 0, cond, seeds, S, ov, 1.0, joint_clips_per_call,
+                           guidance_scale=self.guidance_scale, original_inference_steps=self.original_inference_steps)
         gen = self.decode(z[:, :, h0:].contiguous())["wav"].contiguous()
         out = torch.cat([wav, torch.zeros((B, extra * FRAME_SAMPLES), device=dev)], 1)
         kernels.wave_paste(out, gen, m, gen_start=h0 * FRAME_SAMPLES, fade_samples=fade, out=out)
         return dict(latent=z, wav=out, region=(a, L))
 
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
-        """([(start, known)], window length) of ``generate_long``: window k covers frames start .. start + window, of
-        which the first ``known`` are already generated.  The stride is window - overlap; the last window is shifted
-        back to end at latent_len when the stride does not divide; a clip no longer than one window is that one window."""
-        return _long_windows(latent_len, window or self.latent_shape[1], overlap)
+        """``windows.long_windows``, the plan of ``generate_long``; ``window`` defaults to latent_shape[1]."""
+        return windows.long_windows(latent_len, window or self.latent_shape[1], overlap)
 
     @torch.no_grad()
     def generate_long(self, cond: torch.Tensor, seeds: Sequence[int], latent_len: int, window: Optional[int] = None,
@@ -584,29 +413,8 @@ class AudioLCMPipeline:
         return dict(latent=z, **self.decode(z))
 
     def loop_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
-        """(window starts, window length W, overlap) of ``generate_loop``: the plan of a ring of L = ``latent_len``
-        frames.  W = min(window or latent_shape[1], L); ``overlap`` defaults to W // 2, 0 < overlap < W.  K = max(2,
-        ceil(L / (W - overlap))) windows start at floor(k * L / K): every gap between cyclic neighbours is at most
-        W - overlap, so they share at least ``overlap`` frames.  One window cannot close a ring, so K is never 1: a ring
-        of one window's length is covered by two windows with different cut points.  When L and W are multiples of 4
-        the starts are rounded down to multiples of 4 (the step kernel's 16-byte path), provided they stay strictly
-        ascending and no cyclic gap exceeds W - overlap.  ValueError for more than 32 windows."""
-        L = int(latent_len)
-        W = min(int(window or self.latent_shape[1]), L)
-        overlap = W // 2 if overlap is None else int(overlap)
-        if not 0 < overlap < W:
-            raise ValueError("need 0 < overlap < window")
-        stride = W - overlap
-        K = max(2, -(-L // stride))
-        if K > JOINT_MAX_WINDOWS:
-            raise ValueError(f"{K} windows of {W} frames for a ring of {L}: at most {JOINT_MAX_WINDOWS}")
-        starts = [k * L // K for k in range(K)]
-        if L % 4 == 0 and W % 4 == 0:
-            r = [s - s % 4 for s in starts]
-            gaps = [b - a for a, b in zip(r, r[1:] + [L])]
-            if min(gaps) > 0 and max(gaps) <= stride:
-                starts = r
-        return starts, W, overlap
+        """``windows.loop_windows``, the plan of ``generate_loop``; ``window`` defaults to latent_shape[1]."""
+        return windows.loop_windows(latent_len, window or self.latent_shape[1], overlap)
 
     @torch.no_grad()
     def generate_loop(self, cond: torch.Tensor, seeds: Optional[Sequence[int]], latent_len: int,

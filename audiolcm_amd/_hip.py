@@ -67,6 +67,30 @@ class GemmPlanInfo(C.Structure):
                 ("wn", C.c_int), ("grid", C.c_int * 3), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class ActArgs(C.Structure):
+    _fields_ = [("x", vp), ("x_is_f16", C.c_int), ("y", vp * 3), ("nset", C.c_int), ("B", C.c_int), ("T", C.c_int),
+                ("C", C.c_int), ("Cp", C.c_int), ("alpha_exp", fp * 3), ("inv_beta", fp * 3), ("up_filter", fp),
+                ("down_filter", fp), ("prec", C.c_int)]
+
+
+class ActPlanInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 64), ("kernel", C.c_int), ("prec", C.c_int), ("np", C.c_int), ("nset", C.c_int),
+                ("defer", C.c_int), ("in16", C.c_int), ("grid", i64), ("tiles_t", C.c_int), ("tiles_c", C.c_int),
+                ("strips_t", C.c_int), ("y_lo", i64), ("flops", C.c_double), ("bytes", C.c_double)]
+
+
+class AttnArgs(C.Structure):
+    _fields_ = [("qkv", fp), ("qkv_plane", vp), ("out", fp), ("out_plane", vp), ("B", C.c_int), ("L", C.c_int),
+                ("H", C.c_int), ("heads", C.c_int), ("prec", C.c_int), ("bias", fp), ("bld", C.c_int),
+                ("scale", C.c_float)]
+
+
+class AttnPlanInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 80), ("form", C.c_int), ("prec", C.c_int), ("bias", C.c_int), ("lp", C.c_int),
+                ("dh", C.c_int), ("scale", C.c_float), ("grid", i64), ("block", C.c_int), ("flops", C.c_double),
+                ("bytes", C.c_double)]
+
+
 VOC_MAX_RB, VOC_MAX_DIL = 8, 8
 
 
@@ -107,6 +131,7 @@ _SIGS = [
     ("alcm_activation1d", C.c_int, [fp, fp, C.c_int, C.c_int, C.c_int, i64, i64, fp, fp, fp, fp, vp]),
     ("alcm_activation1d_op", C.c_int, [fp, vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_int, vp]),
     ("alcm_activation1d_op_f16in", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, fp, fp, C.c_int, vp]),
+    ("alcm_activation1d_planes", C.c_int, [C.POINTER(ActArgs), vp]),
     ("alcm_opconv", C.c_int, [C.POINTER(OpConvArgs), vp]),
     ("alcm_opconv_sum", C.c_int, [C.POINTER(OpConvArgs), C.c_int, vp]),
     ("alcm_opconv_dense", C.c_int, [C.POINTER(OpConvArgs), vp]),
@@ -148,6 +173,8 @@ _SIGS = [
     ("alcm_debug_conv_plan", C.c_int, [C.POINTER(OpConvArgs), C.c_int, C.c_int, C.c_int, C.POINTER(ConvPlanInfo),
                                        C.POINTER(C.c_int)]),
     ("alcm_debug_gemm_plan", C.c_int, [C.POINTER(GemmArgs), C.POINTER(GemmPlanInfo)]),
+    ("alcm_debug_act_plan", C.c_int, [C.POINTER(ActArgs), C.POINTER(ActPlanInfo)]),
+    ("alcm_debug_attn_plan", C.c_int, [C.POINTER(AttnArgs), C.POINTER(AttnPlanInfo)]),
     ("alcm_debug_voc_plan", C.c_int, [C.POINTER(VocStageShape), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(VocStagePlan)]),
     ("alcm_debug_ksplit_parts", C.c_int, [i64, i64, C.c_int, C.c_double, C.c_double]),
@@ -279,6 +306,29 @@ def debug_gemm_plan(args) -> dict:
     check(lib().alcm_debug_gemm_plan(C.byref(args), C.byref(out)), "alcm_debug_gemm_plan")
     return dict(name=out.name.decode(), family=GEMM_FAMILIES[out.family], bm=out.bm, bn=out.bn, wm=out.wm, wn=out.wn,
                 grid=list(out.grid), flops=out.flops, bytes=out.bytes)
+
+
+ACT_KERNELS = ("coop", "mfma", "mfma3")
+ATTN_FORMS = ("resident_plane", "resident_f32", "tiled")
+
+
+def debug_act_plan(args) -> dict:
+    """Diagnostics: the launch alcm_activation1d_planes (alcm_activation1d_op / _f16in) would make for an ActArgs under
+    the current ALCM_* switches; raises HipError with the call's own error.  Host only (alcm_debug_act_plan)."""
+    out = ActPlanInfo()
+    check(lib().alcm_debug_act_plan(C.byref(args), C.byref(out)), "alcm_debug_act_plan")
+    return dict(name=out.name.decode(), kernel=ACT_KERNELS[out.kernel], prec=out.prec, np=out.np, nset=out.nset,
+                defer=out.defer, in16=out.in16, grid=int(out.grid), tiles_t=out.tiles_t, tiles_c=out.tiles_c,
+                strips_t=out.strips_t, y_lo=int(out.y_lo), flops=out.flops, bytes=out.bytes)
+
+
+def debug_attn_plan(args) -> dict:
+    """Diagnostics: the launch alcm_flash_attention_ex would make for an AttnArgs; raises HipError with the call's own
+    error.  Host only (alcm_debug_attn_plan)."""
+    out = AttnPlanInfo()
+    check(lib().alcm_debug_attn_plan(C.byref(args), C.byref(out)), "alcm_debug_attn_plan")
+    return dict(name=out.name.decode(), form=ATTN_FORMS[out.form], prec=out.prec, bias=out.bias, lp=out.lp, dh=out.dh,
+                scale=out.scale, grid=int(out.grid), block=out.block, flops=out.flops, bytes=out.bytes)
 
 
 VOC_UPS = ("planes", "ups2", "phases")

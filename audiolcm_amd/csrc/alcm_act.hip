@@ -169,44 +169,6 @@ __global__ __launch_bounds__(256) void act_coop_kernel(const float* __restrict__
   }
 }
 
-// nset parameter sets (1 or 3) of one input: y[i], alpha_exp[i], inv_beta[i]
-int act_coop(const float* x, void* const* y, int nset, int B, int T, int C, int Cp, const float* const* alpha_exp,
-             const float* const* inv_beta, const Taps12O& f, int prec, hipStream_t s) {
-  if (nset != 1 && nset != 3) return set_error(ALCM_E_INVALID, "activation1d: 1 or 3 parameter sets");
-  // 64-channel tiles (whole 128-B output lines) measured faster at C = 768 (-15 %) and for the two-plane split
-  // output (-10 %), slower at C = 384 (+10..15 %), even at C = 192 fp16 (scripts/microbench.py actnp)
-  const bool wide = Cp % 64 == 0 && (C >= 768 || prec == PREC_SPLIT);
-  const int np = wide ? 32 : 16, tt = 2048 / np;
-  const int tiles_t = (T + tt - 1) / tt, tiles_c = Cp / (2 * np);
-  const int64_t nwg = (int64_t)B * tiles_t * tiles_c;
-  if (nwg >= (1ll << 31)) return set_error(ALCM_E_INVALID, "activation1d_op: problem too large");
-  const int64_t y_lo = (int64_t)B * T * Cp;
-  ActSets S{};
-  for (int i = 0; i < nset; ++i) {
-    S.y[i] = (u16*)y[i];
-    S.aexp[i] = alpha_exp[i];
-    S.ibeta[i] = inv_beta[i];
-  }
-  auto launch = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), 0, s, x, S, y_lo, T, C, Cp, f, tiles_t, tiles_c);
-  };
-  auto pick = [&](auto npc) {
-    constexpr int NP = decltype(npc)::value;
-    if (nset == 3) {
-      if (prec == PREC_SPLIT) launch(act_coop_kernel<PREC_SPLIT, NP, 3>);
-      else if (prec == PREC_BF16) launch(act_coop_kernel<PREC_BF16, NP, 3>);
-      else launch(act_coop_kernel<PREC_F16, NP, 3>);
-    } else {
-      if (prec == PREC_SPLIT) launch(act_coop_kernel<PREC_SPLIT, NP, 1>);
-      else if (prec == PREC_BF16) launch(act_coop_kernel<PREC_BF16, NP, 1>);
-      else launch(act_coop_kernel<PREC_F16, NP, 1>);
-    }
-  };
-  if (wide) pick(std::integral_constant<int, 32>{});
-  else pick(std::integral_constant<int, 16>{});
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // Activation1d on MFMA (alias_free_torch/act.py:23-27), fp16 operand planes out, for the wide BigVGAN stages (C = 768 /
 // 384 / 192 under the mixed policy).  Both 12-tap FIRs are banded Toeplitz products per 16-channel group:
@@ -233,8 +195,6 @@ __device__ __forceinline__ uint32_t am_pair(float v) {  // (v, v) as two fp16
   const uint32_t h = __builtin_bit_cast(u16, (_Float16)v);
   return h | (h << 16);
 }
-
-constexpr int AM_STRIP = 8;          // wave tiles per workgroup strip (the tap fragments are built once per strip)
 
 // TT outputs per wave tile: 64 (two 59 KB workgroups per CU).  A 48-output tile (7 up / 3 down blocks, 51 KB: three
 // workgroups per CU) measured the same (8.92 vs 8.94 ms/step over the 270 launches, profiles/r4z): occupancy is not
@@ -574,40 +534,87 @@ __global__ __launch_bounds__(256, 2) void act_mfma3_kernel(const float* __restri
   }
 }
 
-int act_mfma3(const float* x, void* const y[3], int B, int T, int C, int Cp, const float* const alpha_exp[3],
-              const float* const inv_beta[3], const Taps12O& f, hipStream_t s) {
-  if ((((uintptr_t)x) & 15)) return set_error(ALCM_E_INVALID, "act_mfma3: alignment");
-  ActSets S{};
-  for (int i = 0; i < 3; ++i) {
-    if ((((uintptr_t)y[i]) & 15)) return set_error(ALCM_E_INVALID, "act_mfma3: alignment");
-    S.y[i] = (u16*)y[i];
-    S.aexp[i] = alpha_exp[i];
-    S.ibeta[i] = inv_beta[i];
+// ------------------------------------------------------------------------------------------------------------------
+// The one launcher of the three kernels above.  Every check and the kernel choice are act_plan's (alcm_actplan.cpp);
+// what follows builds the taps and the parameter sets, picks the instantiation the plan names and launches it.
+template <int NP, int NSET>
+static auto coop_kernel(int prec) {
+  return prec == PREC_SPLIT  ? act_coop_kernel<PREC_SPLIT, NP, NSET>
+         : prec == PREC_BF16 ? act_coop_kernel<PREC_BF16, NP, NSET>
+                             : act_coop_kernel<PREC_F16, NP, NSET>;
+}
+
+int activation1d_planes(const alcm_act_args& a, hipStream_t s) {
+  ActPlan pl;
+  if (act_plan(a, knobs(), prof_enabled(), &pl)) return set_error(ALCM_E_INVALID, pl.err);
+  Taps12O f;
+  for (int k = 0; k < 12; ++k) {
+    f.up[k] = 2.0f * a.up_filter[k];
+    f.dn[k] = a.down_filter[k];
   }
-  constexpr int TT = 64;
-  const int tiles_t = (T + TT - 1) / TT, tiles_c = C / 64;
-  const int strips_t = (tiles_t + AM_STRIP - 1) / AM_STRIP;
-  const int64_t nwg = (int64_t)B * strips_t * tiles_c;
-  if (nwg >= (1ll << 31) || (int64_t)T * C >= (1ll << 31)) return set_error(ALCM_E_INVALID, "act_mfma3: too large");
-  hipLaunchKernelGGL(act_mfma3_kernel<TT>, dim3((unsigned)nwg), dim3(256), 0, s, x, S, T, C, Cp, f, strips_t, tiles_c);
+  ActSets S{};
+  for (int i = 0; i < a.nset; ++i) {
+    S.y[i] = (u16*)a.y[i];
+    S.aexp[i] = a.alpha_exp[i];
+    S.ibeta[i] = a.inv_beta[i];
+  }
+  const dim3 grid((unsigned)pl.grid), block(256);
+  void* tok = prof_start(s);
+  if (pl.kernel == AK_COOP) {
+    auto kern = pl.np == 32 ? (pl.nset == 3 ? coop_kernel<32, 3>(pl.prec) : coop_kernel<32, 1>(pl.prec))
+                            : (pl.nset == 3 ? coop_kernel<16, 3>(pl.prec) : coop_kernel<16, 1>(pl.prec));
+    hipLaunchKernelGGL(kern, grid, block, 0, s, (const float*)a.x, S, pl.y_lo, a.T, a.C, a.Cp, f, pl.tiles_t,
+                       pl.tiles_c);
+  } else if (pl.kernel == AK_MFMA3) {
+    hipLaunchKernelGGL(act_mfma3_kernel<AM_TILE>, grid, block, 0, s, (const float*)a.x, S, a.T, a.C, a.Cp, f,
+                       pl.strips_t, pl.tiles_c);
+  } else {
+    auto kern = pl.in16 ? (pl.defer ? act_mfma_kernel<AM_TILE, true, true> : act_mfma_kernel<AM_TILE, false, true>)
+                        : (pl.defer ? act_mfma_kernel<AM_TILE, true> : act_mfma_kernel<AM_TILE, false>);
+    hipLaunchKernelGGL(kern, grid, block, 0, s, a.x, S.y[0], a.T, a.C, a.Cp, S.aexp[0], S.ibeta[0], f, pl.strips_t,
+                       pl.tiles_c);
+  }
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
   ALCM_HIP(hipGetLastError());
   return 0;
 }
 
-int act_mfma(const void* x, bool x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
-             const float* inv_beta, const Taps12O& f, hipStream_t s) {
-  if ((((uintptr_t)x) & 15) || (((uintptr_t)y) & 15)) return set_error(ALCM_E_INVALID, "act_mfma: alignment");
-  constexpr int TT = 64;
-  const int tiles_t = (T + TT - 1) / TT, tiles_c = C / 64;
-  const int strips_t = (tiles_t + AM_STRIP - 1) / AM_STRIP;
-  const int64_t nwg = (int64_t)B * strips_t * tiles_c;
-  if (nwg >= (1ll << 31) || (int64_t)T * C >= (1ll << 31)) return set_error(ALCM_E_INVALID, "act_mfma: too large");
-  auto kern = x16 ? (knobs().act_defer ? act_mfma_kernel<TT, true, true> : act_mfma_kernel<TT, false, true>)
-                  : (knobs().act_defer ? act_mfma_kernel<TT, true> : act_mfma_kernel<TT, false>);
-  hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), 0, s, x, (u16*)y, T, C, Cp, alpha_exp, inv_beta, f,
-                     strips_t, tiles_c);
-  ALCM_HIP(hipGetLastError());
-  return 0;
+// The argument forms the models and the C entries use.
+// Three Activation1d of one input with their own SnakeBeta parameters and the same FIR taps (a BigVGAN stage's three
+// resblocks' first half-layer): one pass, the input window loaded once (bit-identical to three calls)
+int activation1d_x3(const float* x, void* const y[3], int B, int T, int C, int Cp, const float* const alpha_exp[3],
+                    const float* const inv_beta[3], const float* up_filter, const float* down_filter, int prec,
+                    hipStream_t s) {
+  alcm_act_args a{};
+  a.x = x; a.nset = 3; a.B = B; a.T = T; a.C = C; a.Cp = Cp;
+  for (int i = 0; i < 3; ++i) {
+    a.y[i] = y[i]; a.alpha_exp[i] = alpha_exp[i]; a.inv_beta[i] = inv_beta[i];
+  }
+  a.up_filter = up_filter; a.down_filter = down_filter; a.prec = prec;
+  return activation1d_planes(a, s);
+}
+
+// x16: x is an fp16 plane [B][T][C] (the wide-stage AMPBlock conv1 written by alcm_opconv's out_plane epilogue) instead
+// of fp32: only the MFMA kernel's shapes, whose FIR input is that fp16 value anyway (bit-identical to the fp32-input
+// call on the conv's fp32 output)
+static int activation1d_one(const void* x, bool x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
+                            const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
+                            hipStream_t s) {
+  alcm_act_args a{};
+  a.x = x; a.x_is_f16 = x16; a.nset = 1; a.B = B; a.T = T; a.C = C; a.Cp = Cp;
+  a.y[0] = y; a.alpha_exp[0] = alpha_exp; a.inv_beta[0] = inv_beta;
+  a.up_filter = up_filter; a.down_filter = down_filter; a.prec = prec;
+  return activation1d_planes(a, s);
+}
+int activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
+                    const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
+                    hipStream_t s) {
+  return activation1d_one(x, false, y, B, T, C, Cp, alpha_exp, inv_beta, up_filter, down_filter, prec, s);
+}
+int activation1d_op_h16(const void* x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
+                        const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
+                        hipStream_t s) {
+  return activation1d_one(x16, true, y, B, T, C, Cp, alpha_exp, inv_beta, up_filter, down_filter, prec, s);
 }
 
 // Fused BigVGAN output head (models.py:201-203): activation_post (Activation1d) -> conv_post (k7, C -> 1, zero pad 3)
@@ -769,3 +776,37 @@ int to_planes(const float* x, void* y, int64_t rows, int C, int Cp, int prec, hi
 }
 
 }  // namespace alcm
+
+extern "C" int alcm_activation1d_planes(const alcm_act_args* args, alcm_stream_t stream) {
+  if (!args) return alcm::set_error(ALCM_E_INVALID, "null args");
+  return alcm::activation1d_planes(*args, (hipStream_t)stream);
+}
+
+extern "C" int alcm_activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
+                                    const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
+                                    alcm_stream_t stream) {
+  return alcm::activation1d_op(x, y, B, T, C, Cp, alpha_exp, inv_beta, up_filter, down_filter, prec,
+                               (hipStream_t)stream);
+}
+
+extern "C" int alcm_activation1d_op_f16in(const void* x16, void* y, int B, int T, int C, int Cp,
+                                          const float* alpha_exp, const float* inv_beta, const float* up_filter,
+                                          const float* down_filter, int prec, alcm_stream_t stream) {
+  return alcm::activation1d_op_h16(x16, y, B, T, C, Cp, alpha_exp, inv_beta, up_filter, down_filter, prec,
+                                   (hipStream_t)stream);
+}
+
+extern "C" int alcm_debug_act_plan(const alcm_act_args* args, alcm_act_plan_info* out) {
+  if (!args || !out) return alcm::set_error(ALCM_E_INVALID, "debug_act_plan: bad arguments");
+  alcm::ActPlan pl;
+  if (alcm::act_plan(*args, alcm::knobs(), true, &pl)) return alcm::set_error(ALCM_E_INVALID, pl.err);
+  std::snprintf(out->name, sizeof(out->name), "%s", pl.name);
+  out->kernel = pl.kernel;
+  out->prec = pl.prec; out->np = pl.np; out->nset = pl.nset; out->defer = pl.defer; out->in16 = pl.in16;
+  out->grid = pl.grid;
+  out->tiles_t = pl.tiles_t; out->tiles_c = pl.tiles_c; out->strips_t = pl.strips_t;
+  out->y_lo = pl.y_lo;
+  out->flops = pl.flops;
+  out->bytes = pl.bytes;
+  return 0;
+}

@@ -24,9 +24,8 @@
 
 namespace alcm {
 
-constexpr int FA_Q = 64;       // queries per workgroup
-constexpr int FA_KT = 64;      // keys per tile
-constexpr int FA_DK = 96;      // head dim padded for the QK^T contraction (3 x 32)
+// (FA_Q queries per workgroup, FA_KT keys per tile, FR_MAXL, FR_MAXDH, FR_THREADS: alcm_attnplan.h)
+constexpr int FA_DK = 96;     // head dim padded for the QK^T contraction (3 x 32)
 constexpr int FA_DV = 80;      // head dim padded for the PV output rows (5 x 16)
 constexpr int FA_KS = 104;     // K tile row stride (elements): 208 B
 constexpr int FA_VS = 68;      // V^T tile row stride (elements): 136 B
@@ -204,10 +203,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const float* __restrict
 // all key tiles with no further barrier.  The tiled kernel above re-reads K/V from HBM once per 64-query
 // workgroup (8x at L = 467); here each head's K/V leave HBM once, and B * heads workgroups (256 at B = 32)
 // fill the 256 CUs one per CU.  Same arithmetic and rounding as the tiled kernel (identical per-tile sums).
-constexpr int FR_MAXL = 512;   // keys padded to a multiple of 64
 constexpr int FR_KS = 80;      // K row stride (elements, 160 B): conflict-free ds_read_b128; dims dh..79 zero
-constexpr int FR_MAXDH = 72;
-constexpr int FR_THREADS = 1024;  // 16 waves: 4 per SIMD hide the per-tile softmax / LDS latency chain
 // (round 4: scores in the log2 domain (q pre-scaled), exp2 straight to v_exp_f32, masking only in the last key tile,
 // the running-output rescale skipped when no query's max moved)
 
@@ -435,76 +431,57 @@ __global__ __launch_bounds__(FR_THREADS) void flash_attn_res_kernel(const void* 
   }
 }
 
-// qkv: (B, L, 3H) fp32 rows [q | k | v], head h at columns h*dh; O: (B, L, H) fp32
+// The launcher.  Every check, the choice between the resident and the tiled kernel and the score scale are
+// attn_plan's (alcm_attnplan.cpp).  qkv: (B, L, 3H) rows [q | k | v], head h at columns h*dh; O: (B, L, H)
+template <bool QH>
+static auto res_kernel(int prec, bool bias) {
+  return prec == PREC_F16 ? (bias ? flash_attn_res_kernel<PREC_F16, true, QH> : flash_attn_res_kernel<PREC_F16, false, QH>)
+                          : (bias ? flash_attn_res_kernel<PREC_BF16, true, QH> : flash_attn_res_kernel<PREC_BF16, false, QH>);
+}
+
 int flash_attention(const float* qkv, float* O, int B, int L, int H, int nh, int prec, hipStream_t s, void* o_plane,
-                    const float* bias, int bld, float scale_in, const void* qkv_plane) {
-  if (qkv_plane) {  // q / k / v as PREC operand rows: the resident-K/V kernel only
-    const int Lp = (L + FA_KT - 1) / FA_KT * FA_KT;
-    const int dh = nh > 0 ? H / nh : 0;
-    if (qkv || (!O && !o_plane) || B <= 0 || L <= 0 || nh <= 0 || H % nh || dh > FR_MAXDH || dh % 4 || Lp > FR_MAXL ||
-        (prec != PREC_F16 && prec != PREC_BF16) || (((uintptr_t)qkv_plane) & 7) ||
-        (bias && bld < L))
-      return set_error(ALCM_E_INVALID, "flash_attention: bad plane-input arguments");
-    const float scale = scale_in > 0.f ? scale_in : 1.0f / std::sqrt((float)dh);
-    void* tok = prof_start(s);
-    auto kern = prec == PREC_F16
-                    ? (bias ? flash_attn_res_kernel<PREC_F16, true, true> : flash_attn_res_kernel<PREC_F16, false, true>)
-                    : (bias ? flash_attn_res_kernel<PREC_BF16, true, true> : flash_attn_res_kernel<PREC_BF16, false, true>);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(B * nh)), dim3(FR_THREADS), 0, s, qkv_plane, O, (u16*)o_plane, L, Lp, H, nh,
-                       dh, scale, bias, bld);
-    if (tok) {
-      char name[80];
-      std::snprintf(name, sizeof(name), "alcm::flash_attn_res_kernel<%d, %s, true>", prec, bias ? "true" : "false");
-      const double z = (double)B * nh;
-      prof_stop(tok, s, name, z * 4.0 * L * (double)L * dh, (double)B * L * (3.0 * H * 2.0 + H * 2.0));
-    }
-    ALCM_HIP(hipGetLastError());
-    return 0;
-  }
-  if (!qkv || (!O && !o_plane) || B <= 0 || L <= 0 || nh <= 0 || H % nh) return set_error(ALCM_E_INVALID, "flash_attention: bad args");
-  const int dh = H / nh;
-  if (dh > 72 || dh % 4 || H % 4) return set_error(ALCM_E_INVALID, "flash_attention: head dim must be <= 72, % 4");
-  if (prec != PREC_F16 && prec != PREC_BF16) return set_error(ALCM_E_INVALID, "flash_attention: F16 or BF16 only");
-  if (((uintptr_t)qkv) & 15) return set_error(ALCM_E_INVALID, "flash_attention: qkv must be 16-byte aligned");
-  const float scale = scale_in > 0.f ? scale_in : 1.0f / std::sqrt((float)dh);
-  if (bias && bld < L) return set_error(ALCM_E_INVALID, "flash_attention: bias pitch < L");
-  const int Lp = (L + FA_KT - 1) / FA_KT * FA_KT;
-  if (Lp <= FR_MAXL && dh <= FR_MAXDH && (int64_t)B * nh < (1ll << 31)) {
-    void* tok = prof_start(s);
-    const dim3 grid((unsigned)(B * nh));
-    auto kern = prec == PREC_F16
-                    ? (bias ? flash_attn_res_kernel<PREC_F16, true, false> : flash_attn_res_kernel<PREC_F16, false, false>)
-                    : (bias ? flash_attn_res_kernel<PREC_BF16, true, false> : flash_attn_res_kernel<PREC_BF16, false, false>);
-    hipLaunchKernelGGL(kern, grid, dim3(FR_THREADS), 0, s, qkv, O, (u16*)o_plane, L, Lp, H, nh, dh, scale, bias, bld);
-    if (tok) {
-      char name[64];
-      std::snprintf(name, sizeof(name), "alcm::flash_attn_res_kernel<%d, %s, false>", prec, bias ? "true" : "false");
-      const double z = (double)B * nh;
-      prof_stop(tok, s, name, z * 4.0 * L * (double)L * dh, (double)B * L * (3.0 * H + H) * 4.0);
-    }
-    ALCM_HIP(hipGetLastError());
-    return 0;
-  }
-  if (bias || scale_in > 0.f) return set_error(ALCM_E_INVALID, "flash_attention: score bias / scale only for L <= 512");
-  const int64_t nwg = (int64_t)((L + FA_Q - 1) / FA_Q) * B * nh;
-  if (nwg >= (1ll << 31)) return set_error(ALCM_E_INVALID, "flash_attention: problem too large");
-  const dim3 grid((unsigned)nwg);
+                    const float* bias, int bld, float scale, const void* qkv_plane) {
+  const alcm_attn_args a{qkv, qkv_plane, O, o_plane, B, L, H, nh, prec, bias, bld, scale};
+  AttnPlan pl;
+  if (attn_plan(a, knobs(), prof_enabled(), &pl)) return set_error(ALCM_E_INVALID, pl.err);
+  const dim3 grid((unsigned)pl.grid), block(pl.block);
+  u16* const op = (u16*)a.out_plane;
   void* tok = prof_start(s);
-  if (prec == PREC_F16)
-    hipLaunchKernelGGL(flash_attn_kernel<PREC_F16>, grid, dim3(256), 0, s, qkv, O, (u16*)o_plane, L, H, nh, dh, scale);
-  else
-    hipLaunchKernelGGL(flash_attn_kernel<PREC_BF16>, grid, dim3(256), 0, s, qkv, O, (u16*)o_plane, L, H, nh, dh, scale);
-  if (tok) {
-    char name[64];
-    std::snprintf(name, sizeof(name), "alcm::flash_attn_kernel<%d>", prec);
-    const double z = (double)B * nh;
-    prof_stop(tok, s, name, z * 4.0 * L * (double)L * dh, (double)B * L * (3.0 * H + H) * 4.0);
+  switch (pl.form) {
+    case AF_RES_PLANE:
+      hipLaunchKernelGGL(res_kernel<true>(pl.prec, pl.bias), grid, block, 0, s, a.qkv_plane, a.out, op, a.L, pl.Lp, a.H,
+                         a.heads, pl.dh, pl.scale, a.bias, a.bld);
+      break;
+    case AF_RES_F32:
+      hipLaunchKernelGGL(res_kernel<false>(pl.prec, pl.bias), grid, block, 0, s, a.qkv, a.out, op, a.L, pl.Lp, a.H,
+                         a.heads, pl.dh, pl.scale, a.bias, a.bld);
+      break;
+    default:
+      hipLaunchKernelGGL(pl.prec == PREC_F16 ? flash_attn_kernel<PREC_F16> : flash_attn_kernel<PREC_BF16>, grid, block,
+                         0, s, a.qkv, a.out, op, a.L, a.H, a.heads, pl.dh, pl.scale);
   }
+  if (tok) prof_stop(tok, s, pl.name, pl.flops, pl.bytes);
   ALCM_HIP(hipGetLastError());
   return 0;
 }
 
 }  // namespace alcm
+
+extern "C" int alcm_debug_attn_plan(const alcm_attn_args* args, alcm_attn_plan_info* out) {
+  if (!args || !out) return alcm::set_error(ALCM_E_INVALID, "debug_attn_plan: bad arguments");
+  alcm::AttnPlan pl;
+  if (alcm::attn_plan(*args, alcm::knobs(), true, &pl)) return alcm::set_error(ALCM_E_INVALID, pl.err);
+  std::snprintf(out->name, sizeof(out->name), "%s", pl.name);
+  out->form = pl.form;
+  out->prec = pl.prec; out->bias = pl.bias;
+  out->lp = pl.Lp; out->dh = pl.dh;
+  out->scale = pl.scale;
+  out->grid = pl.grid;
+  out->block = pl.block;
+  out->flops = pl.flops;
+  out->bytes = pl.bytes;
+  return 0;
+}
 
 extern "C" int alcm_flash_attention(const float* qkv, float* out, int B, int L, int H, int heads, int prec,
                                     alcm_stream_t stream) {

@@ -6,6 +6,8 @@
 #include <string>
 
 #include "audiolcm_hip.h"
+#include "alcm_actplan.h"
+#include "alcm_attnplan.h"
 #include "alcm_convplan.h"
 #include "alcm_knobs.h"
 #include "alcm_vocplan.h"
@@ -75,23 +77,22 @@ int to_planes(const float* x, void* y, int64_t rows, int C, int Cp, int prec, hi
 struct Taps12O;
 int act_conv_post(const float* x, float* wav, int B, int T, int C, const float* alpha_exp, const float* inv_beta,
                   const Taps12O& f, const float* w_tc, float bias, hipStream_t s);
+// Activation1d into MFMA operand planes (alcm_act.hip): planned by act_plan (alcm_actplan.h), which holds every check
+// and the choice between the VALU kernel and the MFMA-FIR kernels; activation1d_planes only launches.  The three
+// below are its argument forms: three parameter sets of one input, one set, one set of an fp16 plane x16 [B][T][C]
+// (the wide-stage conv1 output, alcm_opconv's out_plane; the MFMA kernel's shapes only, ALCM_E_INVALID otherwise)
+int activation1d_planes(const alcm_act_args& a, hipStream_t s);
 int activation1d_x3(const float* x, void* const y[3], int B, int T, int C, int Cp, const float* const alpha_exp[3],
                     const float* const inv_beta[3], const float* up_filter, const float* down_filter, int prec,
                     hipStream_t s);
 int activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
                     const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
                     hipStream_t s);
-// Activation1d with both FIRs on MFMA, fp16 planes out (alcm_act.hip; where act_mfma_ok, alcm_vocplan.h)
-// x16: x is an fp16 plane [B][T][C] (the wide-stage conv1 output, alcm_opconv's out_plane) instead of fp32
-int act_mfma3(const float* x, void* const y[3], int B, int T, int C, int Cp, const float* const alpha_exp[3],
-              const float* const inv_beta[3], const Taps12O& f, hipStream_t s);
-int act_mfma(const void* x, bool x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
-             const float* inv_beta, const Taps12O& f, hipStream_t s);
-// Activation1d of an fp16 plane x16 [B][T][C] into fp16 planes (act_mfma shapes only; ALCM_E_INVALID otherwise)
 int activation1d_op_h16(const void* x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
                         const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
                         hipStream_t s);
 int opconv(const alcm_opconv_args& a, hipStream_t s);
+// The fused attention (alcm_attn.hip): planned by attn_plan (alcm_attnplan.h), the launcher switches once on the plan.
 // o_plane != nullptr: write the output as an fp16 / bf16 operand plane [B][L][H] instead of fp32 O
 // bias != nullptr: + bias[(head * bld + query) * bld + key] on the scores (L <= 512); scale > 0 replaces 1/sqrt(dh);
 // qkv_plane != nullptr (then qkv == nullptr): q / k / v rows as PREC operand elements (L <= 512)

@@ -4,8 +4,9 @@
 // Here it runs as two kernels:
 //   activation1d_op Activation1d (alias_free_torch/act.py:23-27: up-FIR x2 -> SnakeBeta -> down-FIR)
 //                   of the fp32 (B, T, C) tensor, written straight in MFMA operand format: fp16, or
-//                   bf16 hi/lo planes for the bf16x3 split, channels padded to Cp = round_up(C, 32)
-//                   (act_mfma_kernel / act_coop_kernel in alcm_act.hip);
+//                   bf16 hi/lo planes for the bf16x3 split, channels padded to Cp = round_up(C, 32).
+//                   Kernels, launcher and C entries live in alcm_act.hip, planned by alcm_actplan.cpp;
+//                   this file holds the convs only;
 //   opconv_kernel   implicit-GEMM conv1d on those planes: per 32-channel chunk the input window
 //                   rows [t0 - pad, t0 + BM + (k-1)d - pad) are copied once into LDS (double-buffered
 //                   across chunks) and reused by all k taps; the packed weight tile of each (chunk, tap)
@@ -23,109 +24,6 @@
 #include "alcm_actepi.h"
 
 namespace alcm {
-
-int act_coop(const float* x, void* const* y, int nset, int B, int T, int C, int Cp, const float* const* alpha_exp,
-             const float* const* inv_beta, const Taps12O& f, int prec, hipStream_t s);
-
-// three Activation1d of one input with their own SnakeBeta parameters and the same FIR taps (a BigVGAN stage's three
-// resblocks' first half-layer): one cooperative pass, the input window loaded once (bit-identical to three calls)
-int activation1d_x3(const float* x, void* const y[3], int B, int T, int C, int Cp, const float* const alpha_exp[3],
-                    const float* const inv_beta[3], const float* up_filter, const float* down_filter, int prec,
-                    hipStream_t s) {
-  if (!x || !y[0] || !y[1] || !y[2] || !up_filter || !down_filter || B <= 0 || T <= 0 || C <= 0 || C % 2 ||
-      Cp < C || Cp % 32 || prec < PREC_BF16 || prec > PREC_F16W2 || (((uintptr_t)x) & 7))
-    return set_error(ALCM_E_INVALID, "activation1d_x3: bad arguments");
-  for (int i = 0; i < 3; ++i)
-    if (!alpha_exp[i] || !inv_beta[i] || (((uintptr_t)y[i]) & 3)) return set_error(ALCM_E_INVALID, "activation1d_x3: bad arguments");
-  if ((int64_t)B * T * Cp >= (1ll << 40)) return set_error(ALCM_E_INVALID, "activation1d_x3: problem too large");
-  Taps12O f;
-  for (int k = 0; k < 12; ++k) {
-    f.up[k] = 2.0f * up_filter[k];
-    f.dn[k] = down_filter[k];
-  }
-  void* tok = prof_start(s);
-  // the wide stages' MFMA FIR kernel where it applies (its fp16 FIR inputs: the mixed policy's stages 0-2)
-  const bool am = knobs().act_x3_mfma && act_mfma_ok(knobs(), C, Cp, prec) && !(((uintptr_t)x) & 15) &&
-                  !(((uintptr_t)y[0]) & 15) && !(((uintptr_t)y[1]) & 15) && !(((uintptr_t)y[2]) & 15);
-  if (am) ALCM_TRY(act_mfma3(x, y, B, T, C, Cp, alpha_exp, inv_beta, f, s));
-  else ALCM_TRY(act_coop(x, y, 3, B, T, C, Cp, alpha_exp, inv_beta, f, prec, s));
-  if (tok) {
-    char name[64];
-    if (am) std::snprintf(name, sizeof(name), "alcm::act_mfma3_kernel<64>");
-    else std::snprintf(name, sizeof(name), "alcm::act_coop_kernel<%d>, x3", prec == PREC_F16W2 ? PREC_F16 : prec);
-    const double e = (double)B * T;
-    prof_stop(tok, s, name, 3 * 2.0 * 36.0 * e * C, e * (4.0 * C + 3 * 2.0 * Cp * (prec == PREC_SPLIT ? 2 : 1)));
-  }
-  ALCM_HIP(hipGetLastError());
-  return 0;
-}
-
-// Activation1d of an fp16 plane (the wide-stage AMPBlock conv1 written by alcm_opconv's out_plane epilogue): only
-// the MFMA kernel's shapes, whose FIR input is that fp16 value anyway (bit-identical to the fp32-input call on the
-// conv's fp32 output)
-int activation1d_op_h16(const void* x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
-                        const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
-                        hipStream_t s) {
-  if (!x16 || !y || !alpha_exp || !inv_beta || !up_filter || !down_filter || B <= 0 || T <= 0 || C <= 0)
-    return set_error(ALCM_E_INVALID, "activation1d_op_f16in: bad arguments");
-  if (!act_mfma_ok(knobs(), C, Cp, prec) || (((uintptr_t)x16) & 15) || (((uintptr_t)y) & 15))
-    return set_error(ALCM_E_INVALID, "activation1d_op_f16in: needs prec F16, C >= 192, C % 64 == 0, Cp == C and "
-                                     "16-byte aligned x / y");
-  Taps12O f;
-  for (int k = 0; k < 12; ++k) {
-    f.up[k] = 2.0f * up_filter[k];
-    f.dn[k] = down_filter[k];
-  }
-  void* tok = prof_start(s);
-  ALCM_TRY(act_mfma(x16, true, y, B, T, C, Cp, alpha_exp, inv_beta, f, s));
-  if (tok) {
-    const double e = (double)B * T;
-    prof_stop(tok, s, knobs().act_defer ? "alcm::act_mfma_kernel<64, true, true>" : "alcm::act_mfma_kernel<64, false, true>",
-                2.0 * 36.0 * e * C, e * (2.0 * C + 2.0 * Cp));
-  }
-  return 0;
-}
-
-int activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
-                    const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
-                    hipStream_t s) {
-  if (!x || !y || !alpha_exp || !inv_beta || !up_filter || !down_filter || B <= 0 || T <= 0 || C <= 0)
-    return set_error(ALCM_E_INVALID, "activation1d_op: bad arguments");
-  if (Cp < C || Cp % 32) return set_error(ALCM_E_INVALID, "activation1d_op: Cp must be >= C and a multiple of 32");
-  if (C % 2) return set_error(ALCM_E_INVALID, "activation1d_op: C must be even");
-  if (prec < PREC_BF16 || prec > PREC_F16W2) return set_error(ALCM_E_INVALID, "activation1d_op: bad prec");
-  if ((((uintptr_t)x) & 7) || (((uintptr_t)y) & 3)) return set_error(ALCM_E_INVALID, "activation1d_op: alignment");
-  if ((int64_t)B * T * Cp >= (1ll << 40)) return set_error(ALCM_E_INVALID, "activation1d_op: problem too large");
-  Taps12O f;
-  for (int k = 0; k < 12; ++k) {
-    f.up[k] = 2.0f * up_filter[k];
-    f.dn[k] = down_filter[k];
-  }
-  if (act_mfma_ok(knobs(), C, Cp, prec) && !(((uintptr_t)x) & 15) && !(((uintptr_t)y) & 15)) {  // both FIRs on MFMA (alcm_act.hip): the wide stages under the mixed policy
-    void* tok = prof_start(s);
-    ALCM_TRY(act_mfma(x, false, y, B, T, C, Cp, alpha_exp, inv_beta, f, s));
-    if (tok) {
-      const double e = (double)B * T;
-      prof_stop(tok, s, knobs().act_defer ? "alcm::act_mfma_kernel<64, true, false>" : "alcm::act_mfma_kernel<64, false, false>",
-                2.0 * 36.0 * e * C, e * (4.0 * C + 2.0 * Cp));
-    }
-    return 0;
-  }
-  // otherwise the LDS-cooperative kernel (alcm_act.hip)
-  void* tok = prof_start(s);
-  void* ys[1] = {y};
-  const float* ae[1] = {alpha_exp};
-  const float* ib[1] = {inv_beta};
-  ALCM_TRY(act_coop(x, ys, 1, B, T, C, Cp, ae, ib, f, prec, s));
-  if (tok) {
-    char name[64];
-    std::snprintf(name, sizeof(name), "alcm::act_coop_kernel<%d>", prec == PREC_F16W2 ? PREC_F16 : prec);
-    const double e = (double)B * T;
-    prof_stop(tok, s, name, 2.0 * 36.0 * e * C, e * (4.0 * C + 2.0 * Cp * (prec == PREC_SPLIT ? 2 : 1)));
-  }
-  ALCM_HIP(hipGetLastError());
-  return 0;
-}
 
 // ------------------------------------------------------------------ implicit-GEMM conv on operand planes
 struct OpConvDev {
@@ -639,20 +537,6 @@ int opconv_sum(const alcm_opconv_args* a, int n, hipStream_t s) {
 
 extern "C" int alcm_opconv_sum(const alcm_opconv_args* args, int n, alcm_stream_t stream) {
   return alcm::opconv_sum(args, n, (hipStream_t)stream);
-}
-
-extern "C" int alcm_activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
-                                    const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
-                                    alcm_stream_t stream) {
-  return alcm::activation1d_op(x, y, B, T, C, Cp, alpha_exp, inv_beta, up_filter, down_filter, prec,
-                               (hipStream_t)stream);
-}
-
-extern "C" int alcm_activation1d_op_f16in(const void* x16, void* y, int B, int T, int C, int Cp,
-                                          const float* alpha_exp, const float* inv_beta, const float* up_filter,
-                                          const float* down_filter, int prec, alcm_stream_t stream) {
-  return alcm::activation1d_op_h16(x16, y, B, T, C, Cp, alpha_exp, inv_beta, up_filter, down_filter, prec,
-                                   (hipStream_t)stream);
 }
 
 extern "C" int alcm_opconv(const alcm_opconv_args* args, alcm_stream_t stream) {

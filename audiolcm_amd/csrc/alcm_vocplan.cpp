@@ -72,10 +72,6 @@ bool sum_writes_planes(const VocStageShape& S, int prec, int B, int To, int ncu,
 
 }  // namespace
 
-bool act_mfma_ok(const Knobs& k, int C, int Cp, int prec) {
-  return k.act_mfma && prec == PREC_F16 && C >= 192 && C % 64 == 0 && Cp == C;
-}
-
 bool ups2_supported(int cin, int cout, int cpad, int rate, int taps) {
   if (rate != 2 || taps != 2) return false;
   return (cin == 96 && cpad == 96 && cout == 48) || (cin == 48 && cpad == 48 && cout == 24);
@@ -111,11 +107,13 @@ int voc_plan(const VocStageShape* st, int n, int policy, bool streams, int B, in
     // the wide stages' conv1 -> Activation1d hand-off as an fp16 plane (ALCM_CONV1_H16=0: fp32, the A/B reference).
     // Only from B * To >= 1024 rows, where the fp32 route takes the same wide kernel (below it the fp32 output would
     // go to opconv_kernel, whose K order differs): the A/B stays bit-exact at every size
-    const bool amok = act_mfma_ok(k, S.cout, Cp, p.prec);  // C >= 192: never a fused stage
-    p.h16 = !fuse && k.conv1_h16 && p.prec == PREC_F16 && amok && (int64_t)B * To >= 1024;
+    // (which kernel an Activation1d launch of the stage gets is act_plan's choice, asked here without pointers: the
+    // workspace buffers it will see are 256-byte aligned.  The fp16-input form exists on the MFMA-FIR kernel only)
+    const auto act_kernel = [&](int nset, bool x16) { return act_kernel_for(k, nset, S.cout, Cp, p.prec, x16); };
+    p.h16 = !fuse && k.conv1_h16 && act_kernel(1, true) == AK_MFMA && (int64_t)B * To >= 1024;
     // the three chains' first Activation1d in one pass over the upsampler output (their own planes, the same taps):
     // the narrow fused stages on the VALU kernel, the wide MFMA-FIR stages on its three-set form (ALCM_ACT_X3_MFMA)
-    p.act3 = S.nrb == 3 && (fuse ? !amok : (amok && k.act_x3_mfma)) && S.act0_equal;
+    p.act3 = S.nrb == 3 && (fuse ? act_kernel(1, false) == AK_COOP : act_kernel(3, false) == AK_MFMA3) && S.act0_equal;
     // each chain on its own buffers when the chains run concurrently, and when act3 wrote three sets of planes (so the
     // serialised profile pass runs the same kernels as the concurrent one)
     p.own_bufs = p.concurrent || p.act3;

@@ -3,6 +3,7 @@
 // closing sum).  Same rules as alcm_convplan.h: no HIP header, no device call, no pointer dereferenced.
 // bigvgan_forward (alcm_models.cpp) executes the plans and decides nothing.
 #pragma once
+#include "alcm_actplan.h"
 #include "alcm_convplan.h"
 
 namespace alcm {
@@ -18,8 +19,6 @@ enum VocAmp { VA_FUSED = 0, VA_FUSED_DENSE, VA_WIDE };
 int voc_plan(const VocStageShape* st, int n, int policy, bool streams, int B, int M, int ncu, const Knobs& k,
              VocStagePlan* out);
 
-// Activation1d with both FIRs on MFMA, fp16 planes out (alcm_act.hip; ALCM_ACT_MFMA=0: never)
-bool act_mfma_ok(const Knobs& k, int C, int Cp, int prec);
 // the stride-2 / 4-tap upsampler with both phases in one split-precision pass (alcm_ups.hip)
 bool ups2_supported(int cin, int cout, int cpad, int rate, int taps);
 

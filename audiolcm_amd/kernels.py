@@ -647,6 +647,40 @@ def activation1d_op_f16in(x16: torch.Tensor, alpha: torch.Tensor, beta: torch.Te
     return y
 
 
+def activation1d_op_x3(x_cl: torch.Tensor, alphas, betas, up_filter: torch.Tensor, down_filter: torch.Tensor,
+                       prec: int) -> list:
+    """Three Activation1d of one channels-last (B, T, C) input, with their own SnakeBeta parameters and the same FIR
+    taps, in one launch (alcm_activation1d_planes, nset = 3) -> three operand planes int16 (NP, B, T, Cp)."""
+    B, T, Cc = x_cl.shape
+    Cp = _round_up(Cc, 32)
+    x_cl = x_cl.contiguous()
+    params = [tuple(t.contiguous() for t in snake_params(a, b)) for a, b in zip(alphas, betas)]
+    fu = up_filter.detach().reshape(-1).float().cpu().contiguous()
+    fd = down_filter.detach().reshape(-1).float().cpu().contiguous()
+    ys = [torch.empty((2 if prec == _hip.PREC_SPLIT else 1, B, T, Cp), dtype=torch.int16, device=x_cl.device)
+          for _ in range(3)]
+    a = _hip.ActArgs()
+    a.x, a.nset, a.B, a.T, a.C, a.Cp, a.prec = ptr(x_cl), 3, B, T, Cc, Cp, int(prec)
+    for i in range(3):
+        a.y[i], a.alpha_exp[i], a.inv_beta[i] = ptr(ys[i]), ptr(params[i][0]), ptr(params[i][1])
+    a.up_filter, a.down_filter = fu.data_ptr(), fd.data_ptr()
+    check(lib().alcm_activation1d_planes(C.byref(a), stream_handle()), "activation1d_planes")
+    return ys
+
+
+def act_plan(args: _hip.ActArgs) -> dict:
+    """Which kernel an Activation1d-into-planes call would launch: name = its profile row, kernel ("coop", "mfma",
+    "mfma3"), its template parameters prec, np, nset, defer, in16, grid, the kernel scalars tiles_t, tiles_c, strips_t,
+    y_lo, flops, bytes.  Launches nothing and needs no GPU."""
+    return _hip.debug_act_plan(args)
+
+
+def attn_plan(args: _hip.AttnArgs) -> dict:
+    """Which kernel a fused-attention call would launch: name = its profile row, form ("resident_plane",
+    "resident_f32", "tiled"), prec, bias, lp, dh, scale, grid, block, flops, bytes.  Launches nothing and needs no GPU."""
+    return _hip.debug_attn_plan(args)
+
+
 def conv_plan(args, ncu: int = 0, dense: bool = False) -> list:
     """Which kernel(s) an operand-plane conv call would launch: args is one _hip.OpConvArgs (alcm_opconv, or
     alcm_opconv_dense with dense = True) or a sequence of up to three (alcm_opconv_sum).  -> one dict per launch (name =

@@ -166,6 +166,24 @@ int alcm_activation1d_op(const float* x, void* y, int B, int T, int C, int Cp, c
 int alcm_activation1d_op_f16in(const void* x16, void* y, int B, int T, int C, int Cp, const float* alpha_exp,
                                const float* inv_beta, const float* up_filter, const float* down_filter, int prec,
                                alcm_stream_t stream);
+/* alcm_activation1d_planes: the general form of the two entries above, which are its nset = 1 cases.  x: (B,T,C) fp32,
+ *   or with x_is_f16 an fp16 plane [B][T][C] (alcm_activation1d_op_f16in's shapes only); nset = 1, or 3 for three
+ *   Activation1d of the one input with their own SnakeBeta parameters and the same FIR taps (a BigVGAN stage's three
+ *   resblocks' first half-layer) in one pass: planes y[i] from alpha_exp[i] / inv_beta[i], i < nset, bit-identical to
+ *   nset single calls.  Zero-initialise the struct before setting fields. */
+typedef struct alcm_act_args {
+  const void* x;
+  int x_is_f16;
+  void* y[3];
+  int nset;
+  int B, T, C, Cp;
+  const float* alpha_exp[3];
+  const float* inv_beta[3];
+  const float* up_filter;   /* HOST, 12 taps */
+  const float* down_filter; /* HOST, 12 taps */
+  int prec;
+} alcm_act_args;
+int alcm_activation1d_planes(const alcm_act_args* args, alcm_stream_t stream);
 /* alcm_opconv: out (B,T,N) = conv_{ksize,dil}(a) with same-length zero padding (2*pad == (ksize-1)*dil)
  * on operand planes a (as written by alcm_activation1d_op, lo plane a_lo_off elements after hi), weights
  * packed by alcm_pack_conv_weight with cpad = Cp; epilogue as alcm_gemm: v = acc + bias[n];
@@ -262,6 +280,17 @@ int alcm_flash_attention(const float* qkv, float* out, int B, int L, int H, int 
  * dh = H / heads <= 72, dh % 4 == 0; prec ALCM_PREC_F16 (2) or ALCM_PREC_BF16 (0).  ALCM_E_INVALID otherwise. */
 int alcm_flash_attention_ex(const float* qkv, const void* qkv_plane, float* out, void* out_plane, int B, int L, int H,
                             int heads, int prec, const float* bias, int bld, float scale, alcm_stream_t stream);
+/* the arguments of alcm_flash_attention_ex as a struct (alcm_debug_attn_plan) */
+typedef struct alcm_attn_args {
+  const float* qkv;
+  const void* qkv_plane;
+  float* out;
+  void* out_plane;
+  int B, L, H, heads, prec;
+  const float* bias;
+  int bld;
+  float scale;
+} alcm_attn_args;
 /* alcm_softmax_rows_bias: in-place softmax of HF T5Attention's scores + position_bias (the split-policy text
  * tower of FrozenCLAPFLANEmbedder.encode, ldm/modules/encoders/modules.py:567-582): rows = Z*L rows of pitch ld,
  * row r = (z, i) with i = r % L, head h = z % heads: x[r][j] = softmax_j(x[r][j] + bias[(h*bld + i)*bld + j]) for
@@ -512,6 +541,36 @@ typedef struct alcm_gemm_plan_info {
   double flops, bytes; /* the cost the profile row is charged */
 } alcm_gemm_plan_info;
 int alcm_debug_gemm_plan(const alcm_gemm_args* args, alcm_gemm_plan_info* out);
+/* diagnostics: what alcm_activation1d_planes (and with it alcm_activation1d_op / _f16in) would launch for these
+ * arguments under the current ALCM_* switches (alcm_actplan.h), or the ALCM_E* code the call itself would return.  Host
+ * only, as alcm_debug_gemm_plan.
+ * kernel: 0 act_coop_kernel<prec, np, nset>, 1 act_mfma_kernel<64, defer, in16>, 2 act_mfma3_kernel<64>; name: the
+ * profile row; grid: workgroups of 256 threads; tiles_t, tiles_c, strips_t, y_lo: the kernel's scalar arguments (0
+ * where the kernel has none). */
+typedef struct alcm_act_plan_info {
+  char name[64];
+  int kernel;
+  int prec, np, nset, defer, in16;
+  int64_t grid;
+  int tiles_t, tiles_c, strips_t;
+  int64_t y_lo;
+  double flops, bytes; /* the cost the profile row is charged */
+} alcm_act_plan_info;
+int alcm_debug_act_plan(const alcm_act_args* args, alcm_act_plan_info* out);
+/* diagnostics: the same for alcm_flash_attention_ex (alcm_attnplan.h).  form: 0 flash_attn_res_kernel<prec, bias, true>
+ * on operand rows, 1 flash_attn_res_kernel<prec, bias, false> on fp32 rows, 2 flash_attn_kernel<prec>; lp: keys padded
+ * to the key tile; scale: the resolved score scale; grid, block: workgroups and threads of each. */
+typedef struct alcm_attn_plan_info {
+  char name[80];
+  int form;
+  int prec, bias;
+  int lp, dh;
+  float scale;
+  int64_t grid;
+  int block;
+  double flops, bytes;
+} alcm_attn_plan_info;
+int alcm_debug_attn_plan(const alcm_attn_args* args, alcm_attn_plan_info* out);
 /* The BigVGAN stage planner (alcm_vocplan.h).  A stage's static shape: the upsampler ConvTranspose1d cin -> cout
  * at `rate` as `rate` phase convs of `taps` taps on input rows padded to `cpad` channels, and nrb AMPBlock1 resblocks of
  * kernel size rb_k[j] with the ndil dilations dil[] (one set for the stage's resblocks). */

@@ -2,7 +2,8 @@
 // decides, once, which kernel of alcm_attn.hip it gets — the resident-K/V kernel on operand rows or on fp32 rows, or the
 // tiled kernel — with which grid, scale and profile name.  Same rules as alcm_gemmplan.h: no HIP header and no device
 // call, pointers are only tested for null-ness and alignment, never dereferenced.  The launcher (alcm_attn.hip,
-// flash_attention) takes the plan and only launches.
+// flash_attention) takes the plan and only launches; the DiT and text forwards ask attn_form_for for the same choice
+// without pointers.
 #pragma once
 #include <cstdint>
 
@@ -18,7 +19,16 @@ constexpr int FR_MAXL = 512;      // flash_attn_res_kernel: most keys (padded to
 constexpr int FR_MAXDH = 72;      // largest head dim of either kernel
 constexpr int FR_THREADS = 1024;  // 16 waves: 4 per SIMD hide the per-tile softmax / LDS latency chain
 
-enum AttnForm { AF_RES_PLANE = 0, AF_RES_F32, AF_TILED };  // resident on operand rows, resident on fp32 rows, tiled
+// resident on operand rows, resident on fp32 rows, tiled; attn_form_for's refusals: a shape no kernel takes (sizes,
+// head dim, precision), or one only the resident kernel would take, beyond its length
+enum AttnForm { AF_INVALID = -2, AF_NONE = -1, AF_RES_PLANE = 0, AF_RES_F32, AF_TILED };
+
+// The form a call gets by its shape alone: B clips of L positions, H channels in `heads` heads at prec, q / k / v given
+// as operand rows (plane) or fp32 rows, with a score bias, with an explicit scale.  The one statement of the rule:
+// attn_plan decides through it, and the model forwards (alcm_models.cpp) ask it, without pointers, which stage may
+// feed the attention.  A refusal (< 0) leaves its message in *why
+int attn_form_for(const Knobs& k, int prec, int B, int L, int H, int heads, bool plane, bool bias, bool scale,
+                  const char** why = nullptr);
 
 struct AttnPlan {
   int form;             // AttnForm

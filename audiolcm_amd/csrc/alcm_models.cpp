@@ -716,6 +716,17 @@ static int lin(hipStream_t s, int prec, int R, const float* x, int C, const Conv
   return conv(s, prec, 1, R, View{x, 0, C, 1, R, C}, w, Out{y, 0, w.w.rows, 1, 1, 0}, o);
 }
 
+// The NCT input x (B, C, T) of a model's first conv as a View: copied to channels-last rows of cpad channels (zero
+// padded) in `rows` where its `cap` floats hold them, so the conv reads whole vectors instead of a stride-T gather per
+// element (ALCM_NCT_CL=0: the gather)
+static int nct_view(hipStream_t s, const float* x, int B, int C, int T, int cpad, float* rows, size_t cap, View* v) {
+  *v = View{x, (int64_t)C * T, 1, T, T, C};
+  if (!knobs().nct_cl || cpad % 4 || (size_t)B * T * cpad > cap) return 0;
+  ALCM_TRY(nct_to_cl(x, B, C, T, cpad, rows, s));
+  *v = View{rows, (int64_t)T * cpad, cpad, 1, T, cpad};
+  return 0;
+}
+
 // The alcm_opconv arguments of a same-length conv of the operand planes `in`, with no output yet: the caller names
 // what it wants (out, res, out_scale, accumulate, out_act, out_plane, geglu_plane, ksplit_ws, act_epilogue).  The one
 // place that fills them.  A linear over R rows is B = 1, T = R.  The lo plane of a bf16x3 operand lies B * T * cpad
@@ -794,6 +805,52 @@ static int mha(hipStream_t s, int prec, int B, int L, int nh, int dh, const floa
   return gemm(p, s);
 }
 
+// The attention sub-block on operand planes of the DiT block, the BERT layer and the T5 block: fused q / k / v
+// projection of the plane the caller wrote (k = 1 on the wide-layer kernel), attention writing the out-projection's
+// plane, out-projection + bias + residual.  The attention is the first form the attention planner has for the shape
+// (attn_form_for, asked once per forward): q / k / v as an operand plane into the resident kernel (attention rounds
+// them to prec anyway: half the bytes written and staged), fp32 q / k / v into the fused kernel, or fp32 q / k / v into
+// the two-GEMM mha, then to_planes
+enum AttnVia { AV_PLANE, AV_F32, AV_MHA };
+struct AttnSub {
+  int prec;
+  int B, T;              // plane_args' (B, T): the DiT's (clips, L); the text towers' linears are (1, clips * L)
+  int clips, L, nh, dh;  // attention over `clips` sequences of L positions, nh heads of dh channels
+  const float* bias;     // score bias [nh][bld][bld] or none
+  int bld;
+  float scale;           // 0: dh^-1/2
+  float *qkv, *S, *O;    // q / k / v rows (fp32, or as a plane); AV_MHA's scores and output
+  u16* opl;              // the out-projection's plane (may be the input plane)
+  float* kp;             // the out-projection's K-split workspace, or none
+  int64_t kp_floats;
+  int via = AV_MHA;
+  void choose() {
+    for (via = AV_PLANE; via < AV_MHA; ++via)
+      if (attn_form_for(knobs(), prec, clips, L, nh * dh, nh, via == AV_PLANE, bias, scale > 0.f) >= 0) return;
+  }
+};
+static int attn_sub(hipStream_t s, const AttnSub& A, const u16* in, int width, const ConvW& wqkv, const ConvW& wout,
+                    const float* res, float* out) {
+  const int I = A.nh * A.dh;
+  alcm_opconv_args q = plane_args(wqkv, in, A.B, A.T, 1, A.prec);
+  if (A.via == AV_PLANE) q.out_plane = A.qkv;
+  else q.out = A.qkv;
+  ALCM_TRY(plane_conv(s, q, width));
+  if (A.via == AV_MHA) {
+    const float scale = A.scale > 0.f ? A.scale : 1.0f / sqrtf((float)A.dh);
+    ALCM_TRY(mha(s, A.prec, A.clips, A.L, A.nh, A.dh, A.qkv, scale, A.bias, A.bld, A.S, A.O));
+    ALCM_TRY(to_planes(A.O, A.opl, (int64_t)A.clips * A.L, I, I, A.prec, s));
+  } else {
+    const bool pl = A.via == AV_PLANE;
+    ALCM_TRY(flash_attention(pl ? nullptr : A.qkv, nullptr, A.clips, A.L, I, A.nh, A.prec, s, A.opl, A.bias, A.bld,
+                             A.scale, pl ? A.qkv : nullptr));
+  }
+  alcm_opconv_args o = plane_args(wout, A.opl, A.B, A.T, 1, A.prec);
+  o.res = res; o.out = out;
+  o.ksplit_ws = A.kp; o.ksplit_ws_floats = A.kp_floats;  // K parts where the grid under-fills the chip (alcm_wconv.hip)
+  return plane_conv(s, o, I);
+}
+
 struct Bump {
   char* base;
   size_t cap, off = 0;
@@ -832,15 +889,6 @@ static DitWs plan_dit(const DitW& D, Bump& bp, int B, int T) {
   w.kp_floats = (int64_t)4 * B * L * H;
   w.kp = bp.take<float>((size_t)w.kp_floats);
   return w;
-}
-
-// attention core over a fused qkv buffer (B, L, 3H): O[b, t, h*dh + d] (new_attention.py:107-126)
-static int dit_attention(hipStream_t s, int split, const DitW& D, int B, int L, const float* qkv, float* S, float* O) {
-  const int H = D.hidden, nh = D.heads, dh = H / nh;
-  // single-rounding policies: fused kernel, scores never leave the chip (alcm_attn.hip)
-  if ((split == PREC_F16 || split == PREC_BF16) && dh <= 72 && dh % 4 == 0)
-    return flash_attention(qkv, O, B, L, H, nh, split, s);
-  return mha(s, split, B, L, nh, dh, qkv, 1.0f / sqrtf((float)dh), nullptr, 0, S, O);
 }
 
 static int dit_embed_context(alcm_model* m, const float* ctx, int B, float* cemb, void* ws, size_t wsb,
@@ -907,15 +955,8 @@ static int dit_forward(alcm_model* m, const float* x, const int64_t* t, const fl
     ConvOpts o;
     o.pad = D.pin_k / 2;
     o.res = Res{D.pos, 0, H, 1};
-    // the NCT latent as channels-last rows of cpad channels (zero padded) in w.o (free until the first block), so
-    // the conv reads whole vectors instead of a stride-T gather per element (ALCM_NCT_CL=0: the gather)
-    const int cp = D.proj_in.w.cpad;
-    const bool tcl = knobs().nct_cl && cp % 4 == 0 && (size_t)B * T * cp <= (size_t)B * L * H;
-    View xv{x, (int64_t)D.in_ch * T, 1, T, T, D.in_ch};
-    if (tcl) {
-      ALCM_TRY(nct_to_cl(x, B, D.in_ch, T, cp, w.o, s));
-      xv = View{w.o, (int64_t)T * cp, cp, 1, T, cp};
-    }
+    View xv;  // channels-last rows in w.o, which is free until the first block
+    ALCM_TRY(nct_view(s, x, B, D.in_ch, T, D.proj_in.w.cpad, w.o, (size_t)B * L * H, &xv));
     ALCM_TRY(conv(s, split, B, T, xv, D.proj_in, Out{w.h, (int64_t)L * H, H, 1, 1, E}, o));
   }
   const View uv = cl(w.u, L, H), ov = cl(w.o, L, H);
@@ -923,39 +964,30 @@ static int dit_forward(alcm_model* m, const float* x, const int64_t* t, const fl
   const Res ur{w.u, (int64_t)L * H, H, 1};
   // the TemporalTransformer 1x1 convs' split planes go to w.g, which is free outside the feed-forward
   u16* spl = reinterpret_cast<u16*>(w.g);
+  // and so do the attention sub-blocks' planes (LayerNorm, then to_out), where the fused attention takes the shape
+  u16 *pln = spl, *opl = pln + (size_t)B * L * H;
+  AttnSub at{pff, B, L, B, L, D.heads, H / D.heads, nullptr, 0, 0.f, w.qkv, w.S, w.o, opl, nullptr, 0};
+  at.choose();
+  const bool planes = at.via != AV_MHA;
   for (const DitBlock& blk : D.blocks) {
     // TemporalTransformer (concatDiT.py:159-171): GN32 -> 1x1 -> block -> 1x1 -> +x
     // (on split planes the GroupNorm affine is applied once, while the planes are written)
     ALCM_TRY(group_norm_affine(w.h, B, L, H, (int64_t)L * H, H, 32, 1e-6f, blk.gn.g, blk.gn.b, w.gsc, w.gsh, s));
     ALCM_TRY(conv_1x1(s, split, B, L, w.h, H, w.gsc, w.gsh, blk.proj_in, nullptr, w.u, spl));
     // BasicTransformerBlock (concatDiT.py:120-125)
-    const bool planes = (pff == PREC_F16 || pff == PREC_BF16) && (H / D.heads) <= 72 && (H / D.heads) % 4 == 0;
-    for (int a = 0; a < 2 && planes; ++a) {
-      // attention sub-block on operand planes: LayerNorm -> plane, fused q/k/v projection (k = 1 on the
-      // wide-layer kernel), flash attention writing the to_out operand plane, to_out + bias + residual in place
+    for (int a = 0; a < 2 && planes; ++a) {  // LayerNorm -> plane, the attention sub-block in place
       const NormW& ln = a ? blk.ln2 : blk.ln1;
-      u16* pln = reinterpret_cast<u16*>(w.g);  // w.g is free until the feed-forward below
-      u16* opl = pln + (size_t)B * L * H;
       ALCM_TRY(layer_norm_plane(w.u, B * L, H, H, 1e-5f, ln.g, ln.b, pln, pff, s));
-      alcm_opconv_args q = plane_args(a ? blk.qkv2 : blk.qkv1, pln, B, L, 1, pff);
-      // q / k / v as an operand plane (attention rounds them to pff anyway): half the bytes written and staged
-      const bool qp = q.N % 4 == 0 && L <= 512;
-      if (qp) q.out_plane = w.qkv;
-      else q.out = w.qkv;
-      ALCM_TRY(plane_conv(s, q, H));
-      if (qp) ALCM_TRY(flash_attention(nullptr, nullptr, B, L, H, D.heads, pff, s, opl, nullptr, 0, 0.f, w.qkv));
-      else ALCM_TRY(flash_attention(w.qkv, nullptr, B, L, H, D.heads, pff, s, opl));
-      alcm_opconv_args o = plane_args(a ? blk.out2 : blk.out1, opl, B, L, 1, pff);
-      o.res = w.u; o.out = w.u;
-      ALCM_TRY(plane_conv(s, o, H));
+      ALCM_TRY(attn_sub(s, at, pln, H, a ? blk.qkv2 : blk.qkv1, a ? blk.out2 : blk.out1, w.u, w.u));
     }
     for (int a = 0; a < 2 && !planes; ++a) {
+      // the two-GEMM attention over a fused qkv buffer (B, L, 3H): O[b, t, h*dh + d] (new_attention.py:107-126)
       const NormW& ln = a ? blk.ln2 : blk.ln1;
       ALCM_TRY(row_stats(w.u, B * L, H, H, 1e-5f, w.mean, w.rstd, s));
       ConvOpts oq;
       oq.pro = Pro{ln.g, ln.b, 0, w.mean, w.rstd, 0};
       ALCM_TRY(conv(s, pff, B, L, uv, a ? blk.qkv2 : blk.qkv1, ocl(w.qkv, L, 3 * H), oq));
-      ALCM_TRY(dit_attention(s, pff, D, B, L, w.qkv, w.S, w.o));
+      ALCM_TRY(mha(s, pff, B, L, at.nh, at.dh, w.qkv, 1.0f / sqrtf((float)at.dh), nullptr, 0, w.S, w.o));
       ConvOpts oo;
       oo.res = ur;
       ALCM_TRY(conv(s, pff, B, L, ov, a ? blk.out2 : blk.out1, uo, oo));
@@ -1470,14 +1502,8 @@ static int bigvgan_forward(alcm_model* m, const float* mel, float* wav, int B, i
   {
     ConvOpts o;
     o.pad = 3;
-    // the NCT mel as channels-last rows, read as whole vectors instead of a stride-M gather per element
-    // (ALCM_NCT_CL=0: the gather)
-    const int cp = G.pre.w.cpad;
-    View mv{mel, (int64_t)G.num_mels * M, 1, M, M, G.num_mels};
-    if (knobs().nct_cl && cp % 4 == 0) {
-      ALCM_TRY(nct_to_cl(mel, B, G.num_mels, M, cp, w.ch[1].t, s));
-      mv = View{w.ch[1].t, (int64_t)M * cp, cp, 1, M, cp};
-    }
+    View mv;  // channels-last rows in a chain buffer (voc_elems sizes it for them)
+    ALCM_TRY(nct_view(s, mel, B, G.num_mels, M, G.pre.w.cpad, w.ch[1].t, (size_t)B * voc_elems(G, M), &mv));
     ALCM_TRY(conv(s, split, B, M, mv, G.pre, ocl(w.x, M, G.c0), o));
   }
   int T = M;
@@ -1701,27 +1727,15 @@ static int text_encode(alcm_model* m, const int64_t* clap_ids, const int64_t* t5
   // an in-kernel conversion ran the text towers at 0.05 of the MFMA peak (profiles/r3z, bench components)
   const bool planes = (pl == PREC_F16 || pl == PREC_BF16) && H % 64 == 0 && D % 64 == 0 && TI % 64 == 0 &&
                       X.b_inter % 64 == 0 && X.t_ff % 64 == 0;
-  // attention of both towers in the fused kernel
-  const bool tflash = planes && L <= 512 && H / X.b_heads <= 72 && X.t_dkv <= 72 &&
-                      (H / X.b_heads) % 4 == 0 && X.t_dkv % 4 == 0;
+  // each tower's attention sub-block (its planes in w.pl, in place): BERT's scaled scores; T5's unscaled scores + the
+  // relative-position bias
+  AttnSub ba{pl, 1, R, B, L, X.b_heads, bdh, nullptr, 0, 0.f, w.qkv, w.S, w.O, w.pl, w.kp, w.kp_floats};
+  AttnSub ta{pl, 1, R, B, L, X.t_heads, X.t_dkv, X.t_bias, X.max_len, 1.0f, w.qkv, w.S, w.O, w.pl, w.kp, w.kp_floats};
+  ba.choose(), ta.choose();
   for (const BertLayerW& Ly : X.bl) {
     if (planes) {
       ALCM_TRY(to_planes(w.x, w.pl, R, H, H, pl, s));
-      alcm_opconv_args qkv = plane_args(Ly.qkv, w.pl, 1, R, 1, pl);
-      if (tflash) {  // q / k / v as a plane, fused attention writing the out-projection's plane (resident K / V)
-        qkv.out_plane = w.qkv;
-        ALCM_TRY(plane_conv(s, qkv, H));
-        ALCM_TRY(flash_attention(nullptr, nullptr, B, L, H, X.b_heads, pl, s, w.pl, nullptr, 0, 0.f, w.qkv));
-      } else {
-        qkv.out = w.qkv;
-        ALCM_TRY(plane_conv(s, qkv, H));
-        ALCM_TRY(mha(s, pl, B, L, X.b_heads, bdh, w.qkv, 1.0f / sqrtf((float)bdh), nullptr, 0, w.S, w.O));
-        ALCM_TRY(to_planes(w.O, w.pl, R, H, H, pl, s));
-      }
-      alcm_opconv_args ao = plane_args(Ly.ao, w.pl, 1, R, 1, pl);
-      ao.res = w.x; ao.out = w.tmp;
-      ao.ksplit_ws = w.kp; ao.ksplit_ws_floats = w.kp_floats;  // K parts: the grid under-fills the chip (alcm_wconv.hip)
-      ALCM_TRY(plane_conv(s, ao, H));
+      ALCM_TRY(attn_sub(s, ba, w.pl, H, Ly.qkv, Ly.ao, w.x, w.tmp));
       ALCM_TRY(layer_norm_plane(w.tmp, R, H, H, X.b_eps, Ly.ln1.g, Ly.ln1.b, w.pl, pl, s));
       ALCM_TRY(layer_norm(w.tmp, R, H, H, X.b_eps, Ly.ln1.g, Ly.ln1.b, nullptr, 0, w.x, H, s));
       alcm_opconv_args up = plane_args(Ly.inter, w.pl, 1, R, 1, pl);
@@ -1767,22 +1781,7 @@ static int text_encode(alcm_model* m, const int64_t* clap_ids, const int64_t* t5
   for (const T5BlockW& Bk : X.tb) {
     if (planes) {
       ALCM_TRY(rms_norm_plane(w.x, R, D, X.t_eps, Bk.ln0, w.pl, pl, s));
-      alcm_opconv_args qkv = plane_args(Bk.qkv, w.pl, 1, R, 1, pl);
-      if (tflash) {  // unscaled scores + the relative-position bias inside the fused kernel
-        qkv.out_plane = w.qkv;
-        ALCM_TRY(plane_conv(s, qkv, D));
-        ALCM_TRY(flash_attention(nullptr, nullptr, B, L, TI, X.t_heads, pl, s, w.pl, X.t_bias, X.max_len, 1.0f,
-                                 w.qkv));
-      } else {
-        qkv.out = w.qkv;
-        ALCM_TRY(plane_conv(s, qkv, D));
-        ALCM_TRY(mha(s, pl, B, L, X.t_heads, X.t_dkv, w.qkv, 1.0f, X.t_bias, X.max_len, w.S, w.O));
-        ALCM_TRY(to_planes(w.O, w.pl, R, TI, TI, pl, s));
-      }
-      alcm_opconv_args o = plane_args(Bk.o, w.pl, 1, R, 1, pl);
-      o.res = w.x; o.out = w.x;
-      o.ksplit_ws = w.kp; o.ksplit_ws_floats = w.kp_floats;
-      ALCM_TRY(plane_conv(s, o, TI));
+      ALCM_TRY(attn_sub(s, ta, w.pl, D, Bk.qkv, Bk.o, w.x, w.x));
       ALCM_TRY(rms_norm_plane(w.x, R, D, X.t_eps, Bk.ln1, w.pl, pl, s));
       alcm_opconv_args wi = plane_args(Bk.wi, w.pl, 1, R, 1, pl);
       wi.out = w.wi;

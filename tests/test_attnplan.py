@@ -55,8 +55,9 @@ def attn_form(B, L, heads, dh, prec, inp="fp32", out="fp32", bld=0, scale=0.0, *
     return d
 
 
-# the argument forms of the models (alcm_models.cpp): dit_attention, the DiT blocks' plane form (L <= 512) and fp32
-# form, the BERT tower and the T5 tower (position bias of pitch max_len, unscaled scores)
+# the argument forms of the models (alcm_models.cpp): dit_attention (fp32 in and out: a helper of the recorded build
+# that no forward reached, since removed), the DiT blocks' plane form (L <= 512) and fp32 form, the BERT tower and the
+# T5 tower (position bias of pitch max_len, unscaled scores)
 MODEL_FORMS = {
     "dit_attention": lambda B, L, prec: attn_form(B, L, 8, 72, prec),
     "dit_plane": lambda B, L, prec: attn_form(B, L, 8, 72, prec, "plane", "plane"),

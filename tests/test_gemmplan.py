@@ -10,7 +10,8 @@ its parameters and a patch of fields (load_table), each recorded under ALCM_PROF
 gemm_skinny_kernel row of tests/data/model_launches.json a call in the argument form of the models' conv / lin / mha
 helpers that the old dispatch gave exactly that row, (b) every family, tile, precision and switch, each condition of
 the window conv and of the skinny kernel failing alone, and (c) every rejection message, with pairs of defects that pin
-the order of the checks.
+the order of the checks.  The last ten cases (the rows of model_launches.json's two cut-down configurations, dit_dh144
+and text_dh96) were added later from the planner of commit 09c2a2d, checked against the rows the GPU recorded there.
 The GPU tests check that a real call of each family records exactly the profile row the planner names and computes the
 float64 restatement of the product.
 """

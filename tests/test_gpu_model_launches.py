@@ -11,7 +11,10 @@ Cases are the smallest shapes that reach every branch of the forwards: the two-G
 convs (split), plane q/k/v into flash attention and the plane linears (mixed, bf16), the DiT's fp32-qkv plane form
 (L > 512), the VAE's nin_shortcut blocks, both upsample forms and both AttnBlock scratch choices, T5 wo on hi / lo
 planes (mixed) and through lin (bf16), and the channels-last input copies switched off (ALCM_NCT_CL=0); two cases at
-the benchmarked batch add the K-split projections, which the planner takes only there.
+the benchmarked batch add the K-split projections, which the planner takes only there.  Two cases on cut-down
+configurations whose head dims the fused attention does not take (recorded the same way from 09c2a2d, the commit before
+the three forwards shared one attention sub-block) pin what no configured geometry reaches: the text towers' plane path
+with the two-GEMM attention, and a DiT whose attention runs through conv + mha while its feed-forward stays on planes.
 """
 import functools
 import hashlib
@@ -50,6 +53,14 @@ def _cases():
     # down-projection and of the text towers' out-projections
     c["dit-B32-T312-mixed-w"] = dict(model="dit", B=32, T=312, policy="mixed", w_cond=1)
     c["text-B32-L77-mixed"] = dict(model="text", B=32, T=77, policy="mixed")
+    # head dims the fused attention does not take (96 and 144 > 72), one layer each: the text towers stay on planes
+    # with the two-GEMM attention and to_planes between the plane linears; the DiT block's attention goes through
+    # conv + mha in fp16 while its feed-forward stays on planes
+    c["text_dh96-B1-L8-mixed"] = dict(model="text", B=1, T=8, policy="mixed", cfg=dict(
+        b_layers=1, t_layers=1, b_hidden=192, b_heads=2, b_inter=256, t_d=128, p_out=128, t_heads=2, t_dkv=96,
+        t_ff=128))
+    c["dit_dh144-B1-T8-mixed-w"] = dict(model="dit", B=1, T=8, policy="mixed", w_cond=1,
+                                        cfg=dict(depth=1, num_heads=4))
     return c
 
 
@@ -57,16 +68,18 @@ CASES = _cases()
 
 
 @functools.lru_cache(maxsize=None)
-def _model(kind):
+def _model(kind, cfg=()):
+    """The model of a case on the recipe's weights; cfg: (field, value) pairs that replace the configuration's."""
     from audiolcm_amd import models
     _hip.require_device(0)
+    cfg = dict(cfg)
     if kind == "dit":
-        return models.ConcatDiT2MLP.from_recipe(0)
+        return models.ConcatDiT2MLP(**cfg).load_state_dict(recipe.dit_state(0, recipe.DiTConfig(**cfg)))
     if kind == "vae":
         return models.AutoencoderKL().load_state_dict({**recipe.vae_state(0), **recipe.vae_encoder_state(0)})
     if kind == "text":
         from audiolcm_amd.text_encoder import CLAPT5TextEncoder
-        return CLAPT5TextEncoder.from_recipe(0)
+        return CLAPT5TextEncoder.from_recipe(0, cfg=recipe.TextConfig(**cfg))
     from audiolcm_amd.mel import MelNet
     return MelNet()
 
@@ -77,7 +90,7 @@ def run_case(c):
     gen = torch.Generator().manual_seed(1234)
     rnd = lambda *shape: torch.randn(*shape, generator=gen).cuda()
     kind = c["model"].split("_")[0]
-    m = _model(kind)
+    m = _model(kind, tuple(sorted(c.get("cfg", {}).items())))
     if kind == "dit":
         x, t, ctx = rnd(B, 20, T), torch.tensor([999, 499] * B)[:B].cuda(), recipe.synthetic_context(B).cuda()
         wc = rnd(B, 256) if c["w_cond"] else None
@@ -116,7 +129,7 @@ def load_table():
 
 
 def test_every_case_is_recorded():
-    assert set(load_table()["rows"]) == set(CASES) and len(CASES) == 25
+    assert set(load_table()["rows"]) == set(CASES) and len(CASES) == 27
 
 
 @pytest.mark.parametrize("cid", sorted(CASES))

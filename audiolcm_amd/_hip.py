@@ -150,10 +150,13 @@ _SIGS = [
                                            fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_lcm_step_ring", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, fp,
                                      fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_lcm_step_ring_edit", C.c_int, [fp, fp, fp, C.c_float, fp, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int,
+                                          fp, fp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_loop", C.c_int, [fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, vp]),
     ("alcm_latent_init", C.c_int, [fp, fp, fp, C.c_float, fp, fp, C.c_float, C.c_float, C.c_float, C.c_float, fp, fp,
                                    C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_paste", C.c_int, [fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_wave_paste_ring", C.c_int, [fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_resample", C.c_int, [fp, fp, C.c_int, i64, C.c_int, i64, C.c_int, C.c_int, fp, C.c_int, C.c_int, vp]),
     ("alcm_loudness_workspace_bytes", C.c_size_t, [C.c_int, i64, C.c_int]),
     ("alcm_loudness_hops", C.c_int, [fp, C.c_int, i64, i64, vp, C.c_int, vp, fp, vp, C.c_size_t, vp]),

@@ -2,7 +2,7 @@
 
 ``plan_edit`` is the one place that decides what an audio-conditioned request is (a variation, an inpainting of the
 cropped clip or, jointly denoised, of the whole one, a keep-original inpainting at 16 kHz or at the recording's own
-rate, or an extension of the recording) and the one place that refuses one; ``AudioLCMPipeline.run_edit`` turns its ``EditPlan`` into audio.  The command line and ``AudioLCMEditInfer`` are
+rate, an extension of the recording, or a loop made from it) and the one place that refuses one; ``AudioLCMPipeline.run_edit`` turns its ``EditPlan`` into audio.  The command line and ``AudioLCMEditInfer`` are
 callers of the two.  Importing this module does not touch the GPU (``kernels`` is imported where a file has to be
 resampled).
 """
@@ -223,7 +223,8 @@ def finish_output(wav16: torch.Tensor, out_sample_rate: Optional[int], level: Op
 @dataclass(frozen=True, eq=False)
 class EditPlan:
     """What ``plan_edit`` decided about one audio-conditioned request; ``AudioLCMPipeline.run_edit`` runs it."""
-    mode: str                                           # "variation", "inpaint", "keep_original" or "extend"
+    mode: str                                           # "variation", "inpaint", "keep_original", "extend",
+    #                                                     "loop_from" or "loop_vary"
     samples: np.ndarray                                 # mono float32 at `rate`, zero-padded to whole latent frames
     n_samples: int                                      # the sample count before padding
     rate: int                                           # the rate the edit runs at
@@ -240,6 +241,72 @@ class EditPlan:
     joint: bool = False                                 # denoise jointly (`edit_long(joint=True)`), the whole recording
     extend_frames: int = 0                              # extend: the latent frames generated after `samples`
     n_out: int = 0                                      # extend: the samples written
+    seam_frames: int = 0                                # loop_from: the frames made anew either side of the wrap
+    loop_fade: int = 0                                  # loop_vary: the seam fade of the decode, in output samples
+    dropped: int = 0                                    # loop_from, loop_vary: the samples trimmed at the recording's end
+
+
+def ring_spans_mask(spans: Sequence[Tuple[float, float]], n_frames: int) -> np.ndarray:
+    """(n_frames,) float32 mask of time spans on a loop's period of ``n_frames`` latent frames at 16 kHz: the whole
+    frames inside each span, as ``keep_original_mask`` takes them.  A span whose end is not after its start goes
+    across the wrap: (t0, t1) with t1 <= t0 is [t0, the period's end) and [0, t1)."""
+    end = (n_frames + 1) * FRAME_SAMPLES / SAMPLE_RATE      # past the period's end: ``spans_to_mask`` clips to it
+    parts = []
+    for t0, t1 in spans:
+        parts += [(t0, t1)] if t1 > t0 else [(t0, end), (0.0, t1)]
+    return spans_to_mask(parts, n_frames, inward=True)
+
+
+def plan_loop(init_audio: str, seam_s: float = 1.0, vary: bool = False,
+              mask_spans: Optional[Sequence[Tuple[float, float]]] = None, fade_ms: float = 32.0, resample: bool = False,
+              out_sample_rate: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
+              true_peak: bool = False, loop_fade_ms: float = 32.0) -> EditPlan:
+    """Reads the recording ``init_audio`` once and plans a loop made from it, or refuses with ValueError (the messages
+    name the arguments and the command line's flags).  The recording is trimmed at its end to L whole latent frames,
+    one period; ``dropped`` counts the samples that leaves out.  ``resample`` brings any input to 16 kHz first.
+
+    Mode "loop_from" (``vary`` false): ``AudioLCMPipeline.loop_from``.  Only the m = ceil(``seam_s`` * 16000 / 512)
+    frames either side of the wrap are made anew, and the whole frames inside ``mask_spans`` (``ring_spans_mask``: a
+    span may go across the wrap) besides; ``fade_ms`` is the paste's fade.  The file holds L * 512 samples at 16 kHz,
+    the recording's own outside the fades, so a level and an output rate are refused.  Needs L >= 2 and 2 m <= L.
+
+    Mode "loop_vary": ``AudioLCMPipeline.edit_loop`` without a mask, the whole ring regenerated from the recording as a
+    hint.  ``out_sample_rate``, the level and ``loop_fade_ms`` apply as for a loop from text, and L is trimmed further
+    to a multiple of ``loop_multiple(out_sample_rate)``."""
+    level = check_level(loudness, peak_dbfs, true_peak)
+    out_sample_rate = check_out_rate(out_sample_rate)
+    if not vary and (level is not None or out_sample_rate is not None):
+        raise ValueError("loop_from (--loop-from) keeps the recording's samples bit for bit at 16 kHz: loudness, "
+                         "peak_dbfs, true_peak and out_sample_rate (--loudness, --peak, --true-peak, "
+                         "--out-sample-rate) are used with loop_vary (--loop-vary)")
+    if vary and mask_spans:
+        raise ValueError("loop_vary (--loop-vary) regenerates the whole ring: it does not take mask_spans (--mask-spans)")
+    if loop_fade_ms < 0:
+        raise ValueError("loop_fade_ms (--loop-fade-ms) must not be negative")
+    x, rate, F = _read_mono(init_audio, resample)
+    out_rate = out_sample_rate or SAMPLE_RATE
+    L = x.size // F
+    if vary:
+        L -= L % loop_multiple(out_rate)
+    if L < 2:
+        raise ValueError(f"{init_audio}: loop_from (--loop-from) needs a recording of at least two latent frames "
+                         f"({2 * F} samples at {SAMPLE_RATE} Hz"
+                         + (f", a multiple of {loop_multiple(out_rate)} frames at {out_rate} Hz" if vary else "")
+                         + f"), got {x.size} samples")
+    samples = np.ascontiguousarray(x[:L * F])
+    if vary:
+        return EditPlan(mode="loop_vary", samples=samples, n_samples=samples.size, rate=rate, frame_samples=F,
+                        spans=None, mask=None, fade=0, out_rate=out_rate, resample_out=out_rate != rate,
+                        pcm_scale=32767.0, native=False, level=level,
+                        loop_fade=fade_samples_of(loop_fade_ms, out_rate), dropped=x.size - samples.size)
+    m = math.ceil(seam_s * SAMPLE_RATE / FRAME_SAMPLES) if seam_s == seam_s else 0     # NaN: refused below
+    if m < 1 or 2 * m > L:
+        raise ValueError(f"loop_seam_s (--loop-seam) {seam_s!r} is {m} latent frames either side of the wrap: a loop "
+                         f"from (--loop-from) a recording of {L} frames takes 1 <= frames and 2 * frames <= {L}")
+    mask = ring_spans_mask(mask_spans, L) if mask_spans else None
+    return EditPlan(mode="loop_from", samples=samples, n_samples=samples.size, rate=rate, frame_samples=F, spans=None,
+                    mask=mask, fade=fade_samples_of(fade_ms, rate), out_rate=rate, resample_out=False,
+                    pcm_scale=32768.0, native=False, seam_frames=m, dropped=x.size - samples.size)
 
 
 def extend_counts(n_samples: int, extend_s: float) -> Tuple[int, int, int]:
@@ -262,7 +329,8 @@ def extend_counts(n_samples: int, extend_s: float) -> Tuple[int, int, int]:
 def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]]] = None, keep_original: bool = False,
               fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
               max_frames: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-              true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None) -> EditPlan:
+              true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None, loop_from: bool = False,
+              loop_seam_s: float = 1.0, loop_vary: bool = False, loop_fade_ms: float = 32.0) -> EditPlan:
     """Reads ``init_audio`` once and decides the request, or refuses it with ValueError.  No ``mask_spans``: a
     variation; with them: an inpainting of the clip (both crop to ``max_frames`` latent frames here when given;
     ``run_edit`` crops to the DiT's limit in any case); ``keep_original``: the whole frames inside the spans are
@@ -272,7 +340,18 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
     is then made from the whole recording instead of a crop to the DiT's limit.  ``extend_s``: the recording is
     continued by that many seconds (``AudioLCMPipeline.extend``, ``extend_counts``) at 16 kHz; with ``resample`` any
     input is brought to 16 kHz first and the kept part is the resampled recording.  Refused with ``mask_spans`` and
-    ``keep_original``, with a level (it would scale the kept samples) and with ``out_sample_rate``."""
+    ``keep_original``, with a level (it would scale the kept samples) and with ``out_sample_rate``.
+    ``loop_from``: the recording is made to loop (``plan_loop``: modes "loop_from" and, with ``loop_vary``,
+    "loop_vary"; ``loop_seam_s`` and ``loop_fade_ms`` are its ``seam_s`` and ``loop_fade_ms``).  Refused with
+    ``keep_original`` and ``extend_s``; ``loop_vary`` alone is refused too."""
+    if loop_vary and not loop_from:
+        raise ValueError("loop_vary (--loop-vary) is used with loop_from (--loop-from)")
+    if loop_from:
+        if keep_original or extend_s is not None:
+            raise ValueError("loop_from (--loop-from) does not combine with keep_original (--keep-original) or extend_s "
+                             "(--extend): it keeps the recording by itself, and a continued recording does not loop")
+        return plan_loop(init_audio, loop_seam_s, loop_vary, mask_spans, fade_ms, resample, out_sample_rate, loudness,
+                         peak_dbfs, true_peak, loop_fade_ms)
     if extend_s is not None:
         if mask_spans or keep_original:
             raise ValueError("extend_s continues the recording: it does not combine with mask_spans or keep_original")

@@ -25,6 +25,16 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
     as it was read up to ``--fade-ms`` before the junction, and SECONDS of generated continuation.  It does not combine
     with ``--inpaint``, ``--mask-spans``, ``--keep-original``, ``--loop``, ``--duration``, the level options or
     ``--out-sample-rate``;
+  * ``--loop-from PATH`` makes the recording PATH loop.  It is trimmed at its end to L whole latent frames.  Alone, only
+    the frames within ``--loop-seam SECONDS`` (default 1.0, rounded up to whole frames) either side of the wrap are
+    generated (from pure noise: ``--strength`` defaults to 1.0 here), conditioned on the recording across the wrap, and
+    faded in over ``--fade-ms``; ``--mask-spans`` adds further spans (a span whose end is not after its start goes
+    across the wrap).  The file holds L * 512 samples at 16 kHz: the recording's own bits outside the fades and spans.
+    With ``--loop-vary`` the whole ring is regenerated from the recording as a hint at ``--strength`` (default 0.5),
+    and ``--out-sample-rate``, ``--loudness``, ``--peak``, ``--true-peak`` and ``--loop-fade-ms`` apply as for
+    ``--loop``.  ``--resample`` brings any input to 16 kHz first.  It does not combine with ``--loop``,
+    ``--init-audio``, ``--inpaint``, ``--keep-original``, ``--duration`` or ``--extend``, and without ``--loop-vary``
+    not with the level options or ``--out-sample-rate`` either;
   * ``--resample``: ``--init-audio`` may have any sample rate, 1 to 8 channels and PCM16, PCM24 or float32 samples; it
     is downmixed and resampled to 16 kHz on the GPU (alcm_resample; without the flag only 16 kHz mono PCM16 is read).
     With ``--keep-original`` the edit is done at the recording's own rate: mono, and a rate at which a latent frame is a
@@ -85,8 +95,9 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                    help="MFMA precision policy (DESIGN.md §3)")
     p.add_argument("--init-audio", type=str, default=None,
                    help="16 kHz mono PCM16 WAV every prompt starts from: a variation, or with --inpaint an inpainting")
-    p.add_argument("--strength", type=float, default=0.5,
-                   help="with --init-audio: how far the clip is noised before sampling, in (0, 1]")
+    p.add_argument("--strength", type=float, default=None,
+                   help="with --init-audio: how far the clip is noised before sampling, in (0, 1] (default 0.5; with "
+                        "--loop-from alone 1.0)")
     p.add_argument("--mask-spans", type=str, default=None,
                    help='with --inpaint: the time spans to regenerate, in seconds, e.g. "2.0-4.5,7-8"')
     p.add_argument("--keep-original", action="store_true",
@@ -117,8 +128,18 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                         "latent frames), or of --W frames without --duration (DESIGN.md §5)")
     p.add_argument("--loop-fade-ms", type=float, default=32.0,
                    help="with --loop: the fade that closes the seam at the start of the period")
+    p.add_argument("--loop-from", type=str, default=None, metavar="PATH",
+                   help="make the recording PATH loop: regenerate only the seam either side of the wrap and keep every "
+                        "other sample (DESIGN.md §5)")
+    p.add_argument("--loop-seam", type=float, default=1.0, metavar="SECONDS",
+                   help="with --loop-from: the audio made anew either side of the wrap, rounded up to whole frames")
+    p.add_argument("--loop-vary", action="store_true",
+                   help="with --loop-from: regenerate the whole ring from the recording as a hint at --strength")
     p.add_argument("--test-dataset-tsv", type=str, default=None, help="override the config's test_dataset tsv_path")
-    return p.parse_args(argv)
+    opt = p.parse_args(argv)
+    if opt.strength is None:
+        opt.strength = 1.0 if opt.loop_from and not opt.loop_vary else 0.5
+    return opt
 
 
 class GenSamples:
@@ -216,7 +237,30 @@ def loop_period(opt) -> int:
     return opt.W
 
 
+def check_loop_from(opt) -> None:
+    """The refusals of ``--loop-from`` that the flags alone decide; the file decides the rest (``audio_in.plan_loop``)."""
+    if opt.loop_vary and not opt.loop_from:
+        raise ValueError("--loop-vary is used with --loop-from")
+    if not opt.loop_from:
+        return
+    for flag, given in (("--loop", opt.loop), ("--init-audio", opt.init_audio), ("--inpaint", opt.inpaint),
+                        ("--keep-original", opt.keep_original), ("--duration", opt.duration is not None),
+                        ("--extend", opt.extend is not None)):
+        if given:
+            raise ValueError(f"--loop-from does not combine with {flag}: it takes its length from the recording, reads "
+                             "it itself and keeps every sample outside the seam")
+    if not opt.loop_vary:
+        for flag, given in (("--loudness", opt.loudness is not None), ("--peak", opt.peak is not None),
+                            ("--true-peak", opt.true_peak), ("--out-sample-rate", opt.out_sample_rate is not None)):
+            if given:
+                raise ValueError(f"--loop-from keeps the recording's samples bit for bit at 16 kHz: {flag} is used with "
+                                 "--loop-vary")
+    elif opt.mask_spans:
+        raise ValueError("--loop-from --loop-vary regenerates the whole ring: it does not take --mask-spans")
+
+
 def build(opt):
+    check_loop_from(opt)
     if opt.extend is not None:
         if not opt.init_audio:
             raise ValueError("--extend continues a recording: it needs --init-audio PATH")
@@ -251,13 +295,13 @@ def build(opt):
                                   "time spans to regenerate")
     if opt.keep_original and not opt.inpaint:
         raise ValueError("--keep-original is used with --inpaint")
-    if opt.mask_spans and not opt.inpaint:
+    if opt.mask_spans and not opt.inpaint and not opt.loop_from:
         raise ValueError("--mask-spans is used with --inpaint")
     if opt.init_audio and opt.duration is not None:
         raise ValueError("--init-audio and --duration do not combine")
     if opt.long_joint and opt.duration is None and not opt.loop and not opt.init_audio:
         raise ValueError("--long-joint is used with --duration or with --init-audio")
-    if opt.resample and not opt.init_audio:
+    if opt.resample and not opt.init_audio and not opt.loop_from:
         raise ValueError("--resample is used with --init-audio")
     check_out_rate(opt.out_sample_rate)
     check_level(opt.loudness, opt.peak, opt.true_peak)
@@ -265,6 +309,14 @@ def build(opt):
     plan = plan_edit(opt.init_audio, parse_spans(opt.mask_spans) if opt.inpaint else None, opt.keep_original,
                      opt.fade_ms, opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
                      true_peak=opt.true_peak, joint=opt.long_joint, extend_s=opt.extend) if opt.init_audio else None
+    if opt.loop_from:
+        plan = plan_edit(opt.loop_from, parse_spans(opt.mask_spans) if opt.mask_spans else None, False, opt.fade_ms,
+                         opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
+                         true_peak=opt.true_peak, loop_from=True, loop_seam_s=opt.loop_seam, loop_vary=opt.loop_vary,
+                         loop_fade_ms=opt.loop_fade_ms)
+        if plan.dropped:
+            print(f"--loop-from: the last {plan.dropped} samples of {opt.loop_from} are left out: the period is "
+                  f"{plan.samples.size // plan.frame_samples} whole latent frames")
     config = load_config(opt.base)
     split = {"split": True, "bf16": "bf16", "mixed": "mixed"}[opt.precision]
     if opt.synthetic_seed is None:

@@ -62,6 +62,10 @@ int lcm_step_joint_edit(const float* x, const float* eps, const float* eps_u, fl
 int lcm_step_ring(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
                   const float* coeffs, const int* starts, int K, const float* wn, float* prev, float* den, float* xw,
                   int B, int C, int L, int W, hipStream_t s);
+int lcm_step_ring_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                       const float* coeffs, const int* starts, int K, const float* wn, const float* z0,
+                       const float* mask, float* prev, float* den, float* xw, int B, int C, int L, int W,
+                       hipStream_t s);
 int wave_loop(const float* ext, const float* ramp, float* out, int B, int64_t Next, int64_t start, int64_t N, int R,
               hipStream_t s);
 int latent_init(const float* moments, const float* z0_in, const float* e0, float scale, const float* noise,
@@ -69,6 +73,8 @@ int latent_init(const float* moments, const float* z0_in, const float* e0, float
                 int C, int T, hipStream_t s);
 int wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
                int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s);
+int wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
+                    int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s);
 int fill_f32(float* p, int64_t n, float v, hipStream_t s);
 int nct_to_cl(const float* x, int B, int C, int T, int Cp, float* y, hipStream_t s);
 // fp32 rows [rows][C] -> operand planes [rows][Cp] in the format of `prec` (SPLIT: lo plane rows * Cp after hi)

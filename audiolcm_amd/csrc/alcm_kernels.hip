@@ -500,9 +500,14 @@ struct FVec<4> {
   __device__ void st(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
 };
 
-// m = 1 keeps the step's own value and m = 0 the known one, both bit for bit; in between the blend.
+// m = 1 keeps the step's own value and m = 0 the known one, both bit for bit; in between the blend, with both products
+// rounded on their own as lcm_renoise spells its roundings out: left to the compiler, the 16-byte instantiations rounded
+// both and the element ones fused the first into an fma, so a mask value whose product is inexact (0.625, not 0.25)
+// gave the two access widths different bits.
 __device__ __forceinline__ float mask_blend(float m, float regen, float keep) {
-  return m == 1.f ? regen : m == 0.f ? keep : m * regen + (1.f - m) * keep;
+#pragma clang fp contract(off)
+  const float a = m * regen, b = (1.f - m) * keep;
+  return m == 1.f ? regen : m == 0.f ? keep : a + b;
 }
 
 template <int V>
@@ -590,6 +595,7 @@ int lcm_step_edit(const float* x, const float* eps, const float* eps_u, float cf
 // Edit = true (lcm_step_joint_edit) blends the joint estimate with a known latent before the re-noise, as the edit step
 // does: d' = mask_blend(mask[b, t], d, z0[b, c, t]), den = d', prev = the re-noised d'.  The mask is read once per item
 // and the z0 rows with x and noise, ahead of the windows' loads; the other forms load nothing more than before.
+// Ring and Edit together (lcm_step_ring_edit) are the ring's chain followed by that blend: a loop made from a recording.
 constexpr int kJointMaxWin = 32;
 struct JointStarts {
   int s[kJointMaxWin];
@@ -704,14 +710,13 @@ __global__ __launch_bounds__(kEditBlock) void joint_gather_kernel(const float* _
 }
 
 // The host side of all forms.  `fn` names the entry in the errors; the open form's plan rules are those of
-// pipeline.joint_weights and the ring's those of pipeline.ring_weights, checked before any launch.  Edit: the open form
-// with z0 and mask; it has no gather-only form.
+// pipeline.joint_weights and the ring's those of pipeline.ring_weights, checked before any launch.  Edit: the line's or
+// the ring's form with z0 and mask; it has no gather-only form.
 template <bool Ring, bool Edit = false>
 static int step_windows(const char* fn, const float* x, const float* eps, const float* eps_u, float cfg,
                         const float* noise, const float* c, const int* starts, int K, const float* wn, const float* z0,
                         const float* mask, float* prev, float* den, float* xw, int B, int C, int L, int W,
                         hipStream_t s) {
-  static_assert(!(Ring && Edit), "the ring has no edit form yet");
   const std::string f = std::string(fn) + ": ";
   if (!x || !wn || !c || !starts) return set_error(ALCM_E_INVALID, f + "null x, wn, coeffs or starts");
   if (Edit && (!eps || !z0 || !mask)) return set_error(ALCM_E_INVALID, f + "null eps_cond, z0 or mask");
@@ -767,8 +772,9 @@ static int step_windows(const char* fn, const float* x, const float* eps, const 
   // frame and channel group; per window element the step (8) and one multiply-add
   const int cg = (C + kEditCh - 1) / kEditCh;
   prof_stop(tok, s,
-            Edit   ? (vec ? "alcm::lcm_step_joint_edit_kernel<4>" : "alcm::lcm_step_joint_edit_kernel<1>")
-            : Ring ? (vec ? "alcm::lcm_step_ring_kernel<4>" : "alcm::lcm_step_ring_kernel<1>")
+            Ring && Edit ? (vec ? "alcm::lcm_step_ring_edit_kernel<4>" : "alcm::lcm_step_ring_edit_kernel<1>")
+            : Edit       ? (vec ? "alcm::lcm_step_joint_edit_kernel<4>" : "alcm::lcm_step_joint_edit_kernel<1>")
+            : Ring       ? (vec ? "alcm::lcm_step_ring_kernel<4>" : "alcm::lcm_step_ring_kernel<1>")
                    : (vec ? "alcm::lcm_step_joint_kernel<4>" : "alcm::lcm_step_joint_kernel<1>"),
             10.0 * nw + (noise ? 3.0 * nl : 0.0),
             4.0 * (nl * (1 + (noise ? 1 : 0) + (prev ? 1 : 0) + (den ? 1 : 0) + (Edit ? 1 : 0)) +
@@ -797,6 +803,13 @@ int lcm_step_ring(const float* x, const float* eps, const float* eps_u, float cf
                   int W, hipStream_t s) {
   return step_windows<true>("lcm_step_ring", x, eps, eps_u, cfg, noise, c, starts, K, wn, nullptr, nullptr, prev, den, xw,
                             B, C, L, W, s);
+}
+
+int lcm_step_ring_edit(const float* x, const float* eps, const float* eps_u, float cfg, const float* noise,
+                       const float* c, const int* starts, int K, const float* wn, const float* z0, const float* mask,
+                       float* prev, float* den, float* xw, int B, int C, int L, int W, hipStream_t s) {
+  return step_windows<true, true>("lcm_step_ring_edit", x, eps, eps_u, cfg, noise, c, starts, K, wn, z0, mask, prev, den,
+                                  xw, B, C, L, W, s);
 }
 
 // z0 = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * e0) from the encoder's (B, 2C, T) moments (the posterior mode
@@ -888,14 +901,19 @@ int latent_init(const float* moments, const float* z0_in, const float* e0, float
 // the distance in frames to the nearest regenerated frame on the left and on the right, and moves V samples per thread
 // and pass (V = 4 with 16-byte accesses when the sizes and pointers allow, else 1).  In place (out == orig) a sample of
 // g = 0 is neither read nor written and a tile without any g > 0 ends after the mask.
+// Ring = true (wave_paste_ring): orig is one period of a loop, N = T * frame_samples exactly, the mask is circular and
+// gen holds the ring's samples (gen_start + i) mod N.  d is measured round the ring: the searches through s_reg index
+// frames modulo T, so a regenerated frame T - 1 fades into the first samples of frame 0 and a regenerated frame 0 into
+// the end of frame T - 1.  A tile's frames are f_first + i for i below f_end - f_first <= T, taken modulo T: in place
+// the frames gen covers, each once.
 constexpr int kPasteTile = 8;
 constexpr int kPasteHalo = 16;  // frames the ramp may reach past a regenerated frame: R <= kPasteHalo * frame_samples
 constexpr int kPasteBlock = 256;
 
-template <int V>
+template <int V, bool Ring>
 __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
     const float* orig, const float* __restrict__ gen, const float* __restrict__ mask, const float* __restrict__ ramp,
-    float* out, int64_t N, int64_t Ng, int64_t gen_start, int T, int fs, int R, int H, int f_first, int tiles,
+    float* out, int64_t N, int64_t Ng, int64_t gen_start, int T, int fs, int R, int H, int f_first, int f_end, int tiles,
     FastDiv fsdiv) {
   __shared__ int s_reg[kPasteTile + 2 * kPasteHalo];
   __shared__ int s_kl[kPasteTile], s_kr[kPasteTile];
@@ -903,7 +921,11 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
   const int f0 = f_first + (int)(blockIdx.x - (unsigned)b * tiles) * kPasteTile;
   const bool inplace = out == orig;
   for (int i = threadIdx.x; i < kPasteTile + 2 * H; i += kPasteBlock) {
-    const int f = f0 - H + i;
+    int f = f0 - H + i;
+    if constexpr (Ring) {
+      f %= T;  // H may exceed T: the search then goes round more than once
+      if (f < 0) f += T;
+    }
     s_reg[i] = (f >= 0 && f < T) ? (mask[(int64_t)b * T + f] > 0.f) : 0;
   }
   __syncthreads();
@@ -920,18 +942,26 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
   }
   if (!__syncthreads_or(live) && inplace) return;
 
-  const int64_t n0 = (int64_t)f0 * fs, row = (int64_t)b * N, grow = (int64_t)b * Ng - gen_start;
+  const int64_t n0 = (int64_t)f0 * fs, row = (int64_t)b * N;
   const uint32_t chunks = (uint32_t)kPasteTile * fs / V;
   for (uint32_t c = threadIdx.x; c < chunks; c += kPasteBlock) {
-    const int64_t n = n0 + (int64_t)c * V;
-    if (n >= N) break;
     uint32_t j, off;
     fsdiv.divmod(c * V, j, off);
+    int64_t n = n0 + (int64_t)c * V;
+    if constexpr (Ring) {
+      if (f0 + (int)j >= f_end) break;
+      if (n >= N) n -= N;  // f_end <= f_first + T < 2 T: one turn at most
+    } else {
+      if (n >= N) break;
+    }
     const int kl = s_kl[j], kr = s_kr[j];
     // kept frame: element i is dl + i samples past the last regenerated sample on the left, dr - i before the first on
     // the right (V = 4 only with frame_samples % 4 == 0: the elements of one access share their frame)
     const int64_t dl = off + (int64_t)(kl - 1) * fs + 1, dr = (int64_t)kr * fs - off;
-    const bool in_gen = n >= gen_start && n + V <= gen_start + Ng;
+    // the sample's place in gen; on a ring gen goes on across the wrap (V = 4: N, Ng and gen_start are multiples of 4)
+    int64_t gi = n - gen_start;
+    if (Ring && gi < 0) gi += N;
+    const bool in_gen = gi >= 0 && gi + V <= Ng;
     FVec<V> g;
     bool any = false;
 #pragma unroll
@@ -944,7 +974,7 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
       if (!inplace) FVec<V>::ld(orig + row + n).st(out + row + n);
       continue;
     }
-    const FVec<V> ov = FVec<V>::ld(orig + row + n), gv = FVec<V>::ld(gen + grow + n);
+    const FVec<V> ov = FVec<V>::ld(orig + row + n), gv = FVec<V>::ld(gen + (int64_t)b * Ng + gi);
     FVec<V> r;
 #pragma unroll
     for (int i = 0; i < V; ++i)
@@ -953,18 +983,25 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
   }
 }
 
-// The samples of g > 0 of one launch, from a host copy of the mask (taken only while profiling).
+// The samples of g > 0 of one launch, from a host copy of the mask (taken only while profiling).  Ring: the frames gen
+// covers go on past T and are looked up modulo T, as are their neighbours; a frame gen enters twice, at its end and
+// across the wrap at its start, counts both parts.
+template <bool Ring>
 static double wave_paste_blended(const std::vector<float>& m, int B, int64_t N, int64_t gen_start, int64_t Ng, int T,
                                  int fs, int R, int H) {
   double blended = 0;
   const int f_lo = (int)(gen_start / fs), f_hi = (int)((gen_start + Ng + fs - 1) / fs);
+  const auto reg = [&](int b, int f) {
+    if (Ring) f = ((f % T) + T) % T;
+    return f >= 0 && f < T && m[(size_t)b * T + f] > 0.f;
+  };
   for (int b = 0; b < B; ++b)
     for (int f = f_lo; f < f_hi; ++f) {
       int kl = 0, kr = 0;
-      while (kl <= H && !(f - kl >= 0 && m[(size_t)b * T + f - kl] > 0.f)) ++kl;
-      while (kr <= H && !(f + kr < T && m[(size_t)b * T + f + kr] > 0.f)) ++kr;
+      while (kl <= H && !reg(b, f - kl)) ++kl;
+      while (kr <= H && !reg(b, f + kr)) ++kr;
       const int64_t lo = std::max<int64_t>((int64_t)f * fs, gen_start);
-      const int64_t hi = std::min<int64_t>({(int64_t)(f + 1) * fs, gen_start + Ng, N});
+      const int64_t hi = std::min<int64_t>({(int64_t)(f + 1) * fs, gen_start + Ng, Ring ? 2 * N : N});
       // samples of the frame within R of the left neighbour, and of the right one
       const int64_t nl = std::clamp<int64_t>(R - 1 - (int64_t)(kl - 1) * fs, 0, fs);
       const int64_t nr = std::clamp<int64_t>(R - 1 - (int64_t)(kr - 1) * fs, 0, fs);
@@ -973,27 +1010,39 @@ static double wave_paste_blended(const std::vector<float>& m, int B, int64_t N, 
   return blended;
 }
 
-int wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
-               int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
-  if (!orig || !out || !mask) return set_error(ALCM_E_INVALID, "wave_paste: null orig, out or mask");
+// The host side of both forms.  On a line gen lies inside the clip; on a ring N is the period exactly, gen starts inside
+// it, is no longer than it and may go on across the wrap.
+template <bool Ring>
+static int paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
+                 int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
+  const std::string f = Ring ? "wave_paste_ring: " : "wave_paste: ";
+  if (!orig || !out || !mask) return set_error(ALCM_E_INVALID, f + "null orig, out or mask");
   if (B < 0 || N < 0 || Ng < 0 || gen_start < 0 || T < 0 || R < 0)
-    return set_error(ALCM_E_INVALID, "wave_paste: negative B, N, Ng, gen_start, T or R");
-  if (fs <= 0 || fs > (1 << 20)) return set_error(ALCM_E_INVALID, "wave_paste: frame_samples outside 1 .. 2^20");
-  if ((int64_t)T * fs < N) return set_error(ALCM_E_INVALID, "wave_paste: the mask's T * frame_samples is shorter than N");
-  if (gen_start + Ng > N) return set_error(ALCM_E_INVALID, "wave_paste: gen reaches past the clip");
-  if (R > (int64_t)kPasteHalo * fs) return set_error(ALCM_E_INVALID, "wave_paste: R exceeds 16 frames");
-  if ((Ng > 0 && !gen) || (R > 0 && !ramp)) return set_error(ALCM_E_INVALID, "wave_paste: null gen or ramp");
+    return set_error(ALCM_E_INVALID, f + "negative B, N, Ng, gen_start, T or R");
+  if (fs <= 0 || fs > (1 << 20)) return set_error(ALCM_E_INVALID, f + "frame_samples outside 1 .. 2^20");
+  if (Ring) {
+    if ((int64_t)T * fs != N) return set_error(ALCM_E_INVALID, f + "N must be the mask's T * frame_samples, one period");
+    if (Ng > N) return set_error(ALCM_E_INVALID, f + "gen is longer than the ring");
+    if (N > 0 && gen_start >= N) return set_error(ALCM_E_INVALID, f + "gen starts past the ring");
+  } else {
+    if ((int64_t)T * fs < N) return set_error(ALCM_E_INVALID, f + "the mask's T * frame_samples is shorter than N");
+    if (gen_start + Ng > N) return set_error(ALCM_E_INVALID, f + "gen reaches past the clip");
+  }
+  if (R > (int64_t)kPasteHalo * fs) return set_error(ALCM_E_INVALID, f + "R exceeds 16 frames");
+  if ((Ng > 0 && !gen) || (R > 0 && !ramp)) return set_error(ALCM_E_INVALID, f + "null gen or ramp");
   if (B == 0 || N == 0) return 0;
   const bool inplace = out == orig;
   if (Ng == 0) {  // nothing to blend: no launch
     if (!inplace) ALCM_HIP(hipMemcpyAsync(out, orig, sizeof(float) * B * N, hipMemcpyDeviceToDevice, s));
     return 0;
   }
-  // in place only the frames gen covers can change; out of place every frame is at least copied
+  // in place only the frames gen covers can change (on a ring counted on past T, each frame once); out of place every
+  // frame is at least copied
   const int64_t fa = inplace ? gen_start / fs : 0;
-  const int64_t fb = inplace ? (gen_start + Ng + fs - 1) / fs : (N + fs - 1) / fs;
+  int64_t fb = inplace ? (gen_start + Ng + fs - 1) / fs : (N + fs - 1) / fs;
+  if (Ring) fb = std::min<int64_t>(fb, fa + T);
   const int64_t tiles = (fb - fa + kPasteTile - 1) / kPasteTile;
-  if (tiles * B >= (1ll << 31)) return set_error(ALCM_E_INVALID, "wave_paste: problem too large");
+  if (tiles * B >= (1ll << 31) || fb >= (1ll << 31)) return set_error(ALCM_E_INVALID, f + "problem too large");
   const int H = (R + fs - 1) / fs;
   const bool vec = fs % 4 == 0 && N % 4 == 0 && Ng % 4 == 0 && gen_start % 4 == 0 && aligned16({orig, gen, out});
   double blended = 0;
@@ -1001,20 +1050,35 @@ int wave_paste(const float* orig, const float* gen, const float* mask, const flo
     std::vector<float> m((size_t)B * T);
     ALCM_HIP(hipMemcpyAsync(m.data(), mask, sizeof(float) * m.size(), hipMemcpyDeviceToHost, s));
     ALCM_HIP(hipStreamSynchronize(s));
-    blended = wave_paste_blended(m, B, N, gen_start, Ng, T, fs, R, H);
+    blended = wave_paste_blended<Ring>(m, B, N, gen_start, Ng, T, fs, R, H);
   }
   void* tok = prof_start(s);
   if (vec)
-    hipLaunchKernelGGL(wave_paste_kernel<4>, dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen, mask, ramp,
-                       out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)tiles, FastDiv((uint32_t)fs));
+    hipLaunchKernelGGL((wave_paste_kernel<4, Ring>), dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen,
+                       mask, ramp, out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)fb, (int)tiles,
+                       FastDiv((uint32_t)fs));
   else
-    hipLaunchKernelGGL(wave_paste_kernel<1>, dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen, mask, ramp,
-                       out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)tiles, FastDiv((uint32_t)fs));
+    hipLaunchKernelGGL((wave_paste_kernel<1, Ring>), dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen,
+                       mask, ramp, out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)fb, (int)tiles,
+                       FastDiv((uint32_t)fs));
   // per sample of g > 0: orig and gen in, out out; of g = 0: a copy out of place, nothing in place; the mask per frame
-  prof_stop(tok, s, vec ? "alcm::wave_paste_kernel<4>" : "alcm::wave_paste_kernel<1>", 3.0 * blended,
+  prof_stop(tok, s,
+            Ring ? (vec ? "alcm::wave_paste_ring_kernel<4>" : "alcm::wave_paste_ring_kernel<1>")
+                 : (vec ? "alcm::wave_paste_kernel<4>" : "alcm::wave_paste_kernel<1>"),
+            3.0 * blended,
             4.0 * (3.0 * blended + (inplace ? 0.0 : 2.0 * ((double)B * N - blended)) + (double)tiles * B * kPasteTile));
   ALCM_HIP(hipGetLastError());
   return 0;
+}
+
+int wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
+               int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
+  return paste<false>(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, fs, R, s);
+}
+
+int wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
+                    int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
+  return paste<true>(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, fs, R, s);
 }
 
 // ---------------------------------------------------------------- loop crop and seam close
@@ -1218,6 +1282,14 @@ extern "C" int alcm_lcm_step_ring(const float* x, const float* eps_cond, const f
   return alcm::lcm_step_ring(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, prev_out, denoised_out,
                              xw_out, B, C, L, W, (hipStream_t)stream);
 }
+extern "C" int alcm_lcm_step_ring_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                                       const float* noise, const float* coeffs, const int* starts, int K,
+                                       const float* wn, const float* z0, const float* mask, float* prev_out,
+                                       float* denoised_out, float* xw_out, int B, int C, int L, int W,
+                                       alcm_stream_t stream) {
+  return alcm::lcm_step_ring_edit(x, eps_cond, eps_uncond, cfg_scale, noise, coeffs, starts, K, wn, z0, mask, prev_out,
+                                  denoised_out, xw_out, B, C, L, W, (hipStream_t)stream);
+}
 extern "C" int alcm_wave_loop(const float* ext, const float* ramp, float* out, int B, int64_t row_len, int64_t start,
                               int64_t N, int R, alcm_stream_t stream) {
   return alcm::wave_loop(ext, ramp, out, B, row_len, start, N, R, (hipStream_t)stream);
@@ -1232,6 +1304,12 @@ extern "C" int alcm_wave_paste(const float* orig, const float* gen, const float*
                                int B, int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R,
                                alcm_stream_t stream) {
   return alcm::wave_paste(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, frame_samples, R, (hipStream_t)stream);
+}
+extern "C" int alcm_wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp,
+                                    float* out, int B, int64_t N, int64_t gen_start, int64_t Ng, int T,
+                                    int frame_samples, int R, alcm_stream_t stream) {
+  return alcm::wave_paste_ring(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, frame_samples, R,
+                               (hipStream_t)stream);
 }
 extern "C" int alcm_sincos_embedding(const float* v, float vscale, const float* freqs, int B, int half,
                                      int cos_first, float* out, alcm_stream_t stream) {

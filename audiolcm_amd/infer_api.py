@@ -178,15 +178,17 @@ def _seed_list(seed: Optional[int], n: int):
     return None if seed is None else list(range(seed, seed + n))
 
 
-def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
+def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: Optional[float] = None,
                       mask_spans: Optional[Sequence[Tuple[float, float]]] = None,
                       config_path: str = "configs/audiolcm.yaml", model_path: str = "./model/000184.ckpt",
                       vocoder_path: str = "./model/vocoder", synthetic_seed: Optional[int] = None, split: bool = True,
                       outpath: str = "results/test", seed: Optional[int] = None, keep_original: bool = False,
                       fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
                       loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-                      true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None) -> str:
-    """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength``, or, with ``mask_spans``
+                      true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None,
+                      loop_from: bool = False, loop_seam_s: float = 1.0, loop_vary: bool = False,
+                      loop_fade_ms: float = 32.0) -> str:
+    """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength`` (default 0.5), or, with ``mask_spans``
     ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
     clip is synthesised again from the latent, cropped to the DiT's 845 frames.  ``keep_original`` (needs
     ``mask_spans``): the clip is not cropped, only the whole frames inside the spans are regenerated
@@ -206,11 +208,23 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: float = 0.5,
     holds n + round(extend_s * 16000) samples, n the recording's; the recording comes back as it was read up to
     ``fade_ms`` before the junction at frame n // 512 (the samples of a last partial frame are generated again).
     ``resample`` brings any input to 16 kHz first.  Refused with ``mask_spans``, ``keep_original``, a level and
-    ``out_sample_rate``, and for a recording shorter than one latent frame.  Returns the
-    WAV path (``<prompt-with-dashes>_0.wav``)."""
+    ``out_sample_rate``, and for a recording shorter than one latent frame.
+    ``loop_from``: the recording is made to loop (``AudioLCMPipeline.loop_from``).  It is trimmed at its end to L whole
+    latent frames; only the frames within ``loop_seam_s`` seconds (rounded up to whole frames) either side of the wrap
+    are generated, from pure noise by default (``strength`` 1.0 here), conditioned on the recording across the wrap,
+    and faded in over ``fade_ms``; ``mask_spans`` adds further spans, and a span whose end is not after its start goes
+    across the wrap.  The file holds L * 512 samples at 16 kHz: the recording's own outside the fades and spans.
+    With ``loop_vary`` the whole ring is regenerated from the recording as a hint at ``strength`` (0.5) instead
+    (``AudioLCMPipeline.edit_loop``), and ``out_sample_rate``, the level and ``loop_fade_ms`` apply as for
+    ``AudioLCMLongInfer(loop=True)``.  ``loop_from`` is refused with ``keep_original`` and ``extend_s``, without
+    ``loop_vary`` also with a level or ``out_sample_rate``, for a recording shorter than two frames and for a seam
+    of more than half the recording.  Returns the WAV path (``<prompt-with-dashes>_0.wav``)."""
     from .pipeline import AudioLCMPipeline
+    if strength is None:
+        strength = 1.0 if loop_from and not loop_vary else 0.5
     plan = plan_edit(init_audio, mask_spans, keep_original, fade_ms, resample, out_sample_rate, loudness=loudness,
-                     peak_dbfs=peak_dbfs, true_peak=true_peak, joint=joint, extend_s=extend_s)  # before any model
+                     peak_dbfs=peak_dbfs, true_peak=true_peak, joint=joint, extend_s=extend_s, loop_from=loop_from,
+                     loop_seam_s=loop_seam_s, loop_vary=loop_vary, loop_fade_ms=loop_fade_ms)  # before any model
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  encoder=True)
     pipe = AudioLCMPipeline(model, vocoder.generator, steps=2, original_inference_steps=orig_steps,

@@ -355,12 +355,22 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
     when that is below W, and ``wn`` is the ring's table.
     ``z0`` and ``mask``: the known latent ``z0`` (B, C, L) is blended into the joint estimate per frame, as
     ``lcm_step_edit`` does for one window: ``mask`` (B, L) in [0, 1], 1 = take the joint step's value, 0 = keep z0
-    (alcm_lcm_step_joint_edit).  ``eps`` is required then, and a ring cannot take them (ValueError)."""
+    (alcm_lcm_step_joint_edit).  ``eps`` is required then, and a ring cannot take them here (ValueError): the ring's edit
+    form is ``lcm_step_ring_edit``."""
+    if ring and z0 is not None:
+        raise ValueError("a ring cannot take `z0`: joint editing exists on a line only (the ring's form is "
+                         "lcm_step_ring_edit)")
+    return _step_windows(x, eps, noise, coeffs, starts, wn, eps_uncond, cfg_scale, want_prev, want_den, want_xw, prev,
+                         den, xw, ring, z0, mask)
+
+
+def _step_windows(x, eps, noise, coeffs, starts, wn, eps_uncond=None, cfg_scale=1.0, want_prev=True, want_den=True,
+                  want_xw=True, prev=None, den=None, xw=None, ring=False, z0=None, mask=None):
+    """The one launch behind ``lcm_step_joint`` and ``lcm_step_ring_edit``: the entry follows from ``ring`` and from
+    whether ``z0`` is given."""
     B, Cc, L = x.shape
     K, W = wn.shape
     edit = z0 is not None
-    if ring and edit:
-        raise ValueError("a ring cannot take `z0`: joint editing exists on a line only")
     assert len(starts) == K and x.is_contiguous() and wn.is_contiguous()
     assert edit == (mask is not None) and not (edit and eps is None)
     if eps is None:
@@ -379,7 +389,8 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
         xw = torch.empty((K * B, Cc, W), device=x.device, dtype=torch.float32)
     arr = (C.c_float * 6)(*[float(c) for c in coeffs])
     st = (C.c_int * K)(*[int(s) for s in starts])
-    name = "lcm_step_joint_edit" if edit else "lcm_step_ring" if ring else "lcm_step_joint"
+    name = ("lcm_step_ring_edit" if ring else "lcm_step_joint_edit") if edit else \
+        "lcm_step_ring" if ring else "lcm_step_joint"
     known = (ptr(z0), ptr(mask)) if edit else ()
     check(getattr(lib(), "alcm_" + name)(ptr(x), ptr(eps), ptr(eps_uncond), float(cfg_scale), ptr(noise), arr, st, K,
                                          ptr(wn), *known, ptr(prev), ptr(den), ptr(xw), B, Cc, L, W, stream_handle()),
@@ -390,6 +401,14 @@ def lcm_step_joint(x: torch.Tensor, eps: Optional[torch.Tensor], noise: Optional
 def lcm_step_joint_edit(x, eps, noise, coeffs, starts, wn, z0: torch.Tensor, mask: torch.Tensor, **kw):
     """``lcm_step_joint`` in its edit form, ``z0`` and ``mask`` required."""
     return lcm_step_joint(x, eps, noise, coeffs, starts, wn, z0=z0, mask=mask, **kw)
+
+
+def lcm_step_ring_edit(x, eps, noise, coeffs, starts, wn, z0: torch.Tensor, mask: torch.Tensor, **kw):
+    """``lcm_step_joint_edit`` on a ring of L frames (alcm_lcm_step_ring_edit): the ring's offsets, chain and table
+    ``wn``, then the blend with ``z0`` under ``mask`` per frame; xw is prev gathered with the wrap.  ``kw`` are
+    ``lcm_step_joint``'s further arguments (not ``ring``)."""
+    assert z0 is not None and mask is not None and "ring" not in kw
+    return _step_windows(x, eps, noise, coeffs, starts, wn, ring=True, z0=z0, mask=mask, **kw)
 
 
 def latent_init(noise: Optional[torch.Tensor], keep=(1.0, 0.0), regen=(0.0, 1.0), moments: Optional[torch.Tensor] = None,
@@ -436,6 +455,20 @@ def wave_paste(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_st
     inside a regenerated frame, a raised-cosine fade over the ``fade_samples`` samples either side of one, orig bit for
     bit further away and outside gen (alcm_wave_paste).  ``out`` None: a new tensor; ``out=orig`` pastes in place and
     touches only what changes.  One launch."""
+    return _paste("wave_paste", orig, gen, mask, gen_start, fade_samples, frame_samples, out)
+
+
+def wave_paste_ring(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_start: int, fade_samples: int,
+                    frame_samples: int = 512, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``wave_paste`` on one period of a loop (alcm_wave_paste_ring): ``orig`` (B, N) with N = T * ``frame_samples``
+    exactly, ``mask`` (B, T) circular, and ``gen`` (B, Ng), 0 < Ng <= N, the ring's samples (gen_start + i) mod N with
+    0 <= gen_start < N, so gen may go on across the wrap.  Distances are measured round the ring: a regenerated last
+    frame fades into the first samples of frame 0, and a regenerated frame 0 into the end of the last frame.  In place
+    only the frames gen covers are visited.  One launch."""
+    return _paste("wave_paste_ring", orig, gen, mask, gen_start, fade_samples, frame_samples, out)
+
+
+def _paste(name, orig, gen, mask, gen_start, fade_samples, frame_samples, out):
     B, N = orig.shape
     assert orig.is_contiguous() and gen.is_contiguous() and mask.is_contiguous()
     assert gen.shape[0] == B and mask.shape[0] == B and gen.dim() == 2 and mask.dim() == 2
@@ -443,9 +476,9 @@ def wave_paste(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_st
         out = torch.empty_like(orig)
     assert out.shape == orig.shape and out.is_contiguous()
     ramp = paste_ramp(fade_samples, orig.device) if 0 < fade_samples <= PASTE_MAX_FADE_FRAMES * frame_samples else None
-    check(lib().alcm_wave_paste(ptr(orig), ptr(gen), ptr(mask), ptr(ramp), ptr(out), B, N, int(gen_start),
-                                gen.shape[1], mask.shape[1], int(frame_samples), int(fade_samples), stream_handle()),
-          "wave_paste")
+    check(getattr(lib(), "alcm_" + name)(ptr(orig), ptr(gen), ptr(mask), ptr(ramp), ptr(out), B, N, int(gen_start),
+                                         gen.shape[1], mask.shape[1], int(frame_samples), int(fade_samples),
+                                         stream_handle()), name)
     return out
 
 

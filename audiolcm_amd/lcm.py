@@ -16,6 +16,7 @@ Differences from the reference that are deliberate and documented in DESIGN.md:
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -352,8 +353,46 @@ class LCMSampler:
         one alcm_lcm_step_joint_edit, which blends the joint estimate with z0 per frame: frames of mask 0 keep z0
         exactly.  Without a mask every frame is regenerated and the step is the open entry, as ``sample_edit``'s is the
         plain one.  With one window the result is ``sample_edit``'s bit for bit.  ``x_T`` is not used, and a ring
-        cannot take ``init`` (ValueError): that kernel form does not exist yet.
+        cannot take ``init`` here (ValueError): joint editing on a ring is ``sample_ring_edit``.
         Returns (denoised, last sample) like ``sample``."""
+        if ring and init is not None:
+            raise ValueError("a ring cannot take `init` here: joint editing on a ring is `sample_ring_edit`")
+        return self._sample_windows(S, conditioning, length, starts, window, overlap, seeds, x_T, noise, guidance_scale,
+                                    original_inference_steps, unconditional_conditioning,
+                                    unconditional_guidance_scale, clips_per_call, ring, init, mask, strength,
+                                    init_noise, posterior_noise, sample_posterior)
+
+    @torch.no_grad()
+    def sample_ring_edit(self, S, conditioning, init, starts: Sequence[int], window: int, overlap: int, mask=None,
+                         strength: float = 1.0, seeds: Optional[Sequence[int]] = None,
+                         noise: Optional[torch.Tensor] = None, init_noise: Optional[torch.Tensor] = None,
+                         posterior_noise: Optional[torch.Tensor] = None, sample_posterior: bool = True,
+                         guidance_scale=5., original_inference_steps=50,
+                         unconditional_conditioning: Optional[torch.Tensor] = None,
+                         unconditional_guidance_scale: float = 1.0,
+                         clips_per_call: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Joint denoising from a known latent on a ring: ``sample_joint(init=...)`` with the frames of ``init`` (the
+        encoder's ``DiagonalGaussianDistribution`` or a scaled (B, C, L) latent) closed into a ring of L frames, a loop
+        made from a recording.  The plan is the ring's (``windows.loop_windows``; ``window_weights(..., ring=True)``),
+        the start is ``sample_joint(init=...)``'s one alcm_latent_init on the long latent with the draws of
+        ``recipe.edit_noise(seeds, S', C, L)``, the DiT calls are grouped as there, and every step is one
+        alcm_lcm_step_ring_edit: the ring's weighted chain blended with z0 per frame, so frames of mask 0 keep z0
+        exactly and the frames either side of the wrap are denoised as the neighbours they are.  Without a mask every
+        frame is regenerated and the step is alcm_lcm_step_ring, as the line uses its open entry; at strength 1 that
+        is ``sample_joint(ring=True)`` from ``init_noise``.  Returns (denoised, last sample) like ``sample``."""
+        if isinstance(init, DiagonalGaussianDistribution):
+            L = init.parameters.shape[2]
+        else:
+            L = init.shape[-1]
+        return self._sample_windows(S, conditioning, L, starts, window, overlap, seeds, None, noise, guidance_scale,
+                                    original_inference_steps, unconditional_conditioning,
+                                    unconditional_guidance_scale, clips_per_call, True, init, mask, strength,
+                                    init_noise, posterior_noise, sample_posterior)
+
+    def _sample_windows(self, S, conditioning, length, starts, window, overlap, seeds, x_T, noise, guidance_scale,
+                        original_inference_steps, unconditional_conditioning, unconditional_guidance_scale,
+                        clips_per_call, ring, init, mask, strength, init_noise, posterior_noise, sample_posterior):
+        """The body of ``sample_joint`` and ``sample_ring_edit``: a line or a ring, from noise or from ``init``."""
         self.make_schedule(verbose=False)
         dev = torch.device("cuda")
         dit: ConcatDiT2MLP = self.model.unet.diffusion_model
@@ -365,8 +404,6 @@ class LCMSampler:
         B, Cc = cond.shape[0], dit.cfg.in_channels
         z0 = None
         if init is not None:
-            if ring:
-                raise ValueError("a ring cannot take `init`: joint editing exists on a line only")
             if x_T is not None:
                 raise ValueError("`x_T` is not used with `init`: pass `init_noise`")
             plan, img, z0, noise, mask = self._edit_start(S, init, mask, strength, seeds, noise, init_noise,
@@ -397,6 +434,10 @@ class LCMSampler:
         ec = torch.empty_like(xw)
         eu = torch.empty_like(xw) if cfg else None
         kernels.lcm_step_joint(img, None, None, plan[0]["coeffs"], starts, wn, xw=xw, ring=ring)   # the first windows
+        if ring and z0 is not None:
+            step = functools.partial(kernels.lcm_step_ring_edit, z0=z0, mask=mask)
+        else:
+            step = functools.partial(kernels.lcm_step_joint, ring=ring, z0=z0, mask=mask)
         outs = [torch.empty_like(img), torch.empty_like(img)]   # never write into the caller's x_T
         denoised = torch.empty_like(img)
         for i, p in enumerate(plan):
@@ -413,9 +454,9 @@ class LCMSampler:
                 if cfg or not whole:
                     ec.view(K, B, Cc, W)[:, b0:b1] = e[-n:].view(K, b1 - b0, Cc, W)
             last = i + 1 == len(plan)
-            kernels.lcm_step_joint(img, ec, noise[i] if p["add_noise"] else None, p["coeffs"], starts, wn, eps_uncond=eu,
-                                   cfg_scale=float(unconditional_guidance_scale), prev=outs[i % 2], den=denoised,
-                                   xw=None if last else xw, want_xw=not last, ring=ring, z0=z0, mask=mask)
+            step(img, ec, noise[i] if p["add_noise"] else None, p["coeffs"], starts, wn, eps_uncond=eu,
+                 cfg_scale=float(unconditional_guidance_scale), prev=outs[i % 2], den=denoised,
+                 xw=None if last else xw, want_xw=not last)
             img = outs[i % 2]
         return denoised, img
 

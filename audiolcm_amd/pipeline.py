@@ -211,15 +211,32 @@ class AudioLCMPipeline:
         """``wav16`` (B, L * 512) on the device -> the scaled latent z (B, C, L) of the whole recording: the posterior's
         sample with e0 = ``recipe.edit_noise(seeds, S, C, L)[2]`` (the global device RNG without seeds), or its mode
         without ``sample_posterior``."""
+        return self._posterior_latent(self._encode(wav16).parameters, seeds, S, sample_posterior)
+
+    def _posterior_latent(self, moments, seeds, S, sample_posterior=True):
+        """The scaled latent z (B, C, L) of the encoder's ``moments`` (B, 2C, L), as ``_encode_latent`` states it."""
         from . import kernels
-        post = self._encode(wav16)
         e0 = None
         if sample_posterior:
-            B, Cc, L = wav16.shape[0], post.parameters.shape[1] // 2, wav16.shape[1] // FRAME_SAMPLES
-            e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(wav16.device) if seeds is not None
-                  else torch.randn((B, Cc, L), device=wav16.device))
-        return kernels.latent_init(None, moments=post.parameters.float().contiguous(), e0=e0,
+            B, Cc, L = moments.shape[0], moments.shape[1] // 2, moments.shape[2]
+            e0 = (recipe.edit_noise(seeds, S, Cc, L)[2].to(moments.device) if seeds is not None
+                  else torch.randn((B, Cc, L), device=moments.device))
+        return kernels.latent_init(None, moments=moments.float().contiguous(), e0=e0,
                                    scale=float(self.model.scale_factor), want_x=False)[0]
+
+    def _encode_ring(self, wav16, seeds, S, sample_posterior=True, halo_frames: int = 32):
+        """``_encode_latent`` of a recording that is about to loop: ``wav16`` (B, L * 512) is encoded as the periodic
+        signal it becomes, cat(wav[:, -he * 512:], wav, wav[:, :he * 512]) with he = min(``halo_frames``, L), and the
+        moments of the centre L frames are kept, so that the encoder's zero padding at a clip's edges stays he frames
+        away from the wrap: the mirror of ``generate_loop``'s circular decode halo.  e0 is
+        ``recipe.edit_noise(seeds, S, C, L)[2]``, drawn at the ring's length.  The 32 frames are the same choice as
+        there, not a measurement (no trained weights here to listen to)."""
+        L = wav16.shape[1] // FRAME_SAMPLES
+        he = min(int(halo_frames), L)
+        n = he * FRAME_SAMPLES
+        padded = torch.cat([wav16[:, wav16.shape[1] - n:], wav16, wav16[:, :n]], 1).contiguous()
+        moments = self._encode(padded).parameters[:, :, he:he + L]
+        return self._posterior_latent(moments, seeds, S, sample_posterior)
 
     def _joint_region(self, z, m, region, r, cond, seeds, S, overlap, strength, clips_per_call, **kw):
         """Denoises ``region`` = (a, b, starts, W) of the latent ``z`` (B, C, L) jointly, in place: one ``sample_joint``
@@ -287,13 +304,24 @@ class AudioLCMPipeline:
         (``audio_in.finish_output``).  Keep-original: ``edit_long`` at the plan's rate on the whole recording, cropped
         to the input's sample count; no whole-clip mel is decoded.  With ``plan.joint`` the frames to regenerate are
         denoised jointly, and a variation or an inpainting is ``edit_long(joint=True)`` on the whole recording instead
-        of a crop.  Extend: ``extend`` on the recording's whole frames, cropped to the plan's sample count."""
+        of a crop.  Extend: ``extend`` on the recording's whole frames, cropped to the plan's sample count.  Loops from
+        the recording: ``loop_from`` on the plan's seam (and spans), or for "loop_vary" ``edit_loop`` without a mask at
+        the plan's output rate, level and seam fade; one period each."""
         B = cond.shape[0]
 
         def span_mask(T):
             return None if plan.spans is None else torch.from_numpy(spans_to_mask(plan.spans, T)).expand(B, T)
-        if plan.mode in ("extend", "keep_original") or plan.joint:      # the whole recording, once per clip
+        # the whole recording, once per clip
+        if plan.mode in ("extend", "keep_original", "loop_from", "loop_vary") or plan.joint:
             wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
+            if plan.mode == "loop_from":
+                mask = None if plan.mask is None else np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
+                out = self.loop_from(cond, seeds, wav, plan.seam_frames, strength, mask, fade_samples=plan.fade)
+                return out["wav"], plan.out_rate, None
+            if plan.mode == "loop_vary":
+                out = self.edit_loop(cond, seeds, wav=wav, strength=strength, level=plan.level,
+                                     out_sample_rate=plan.out_rate, loop_fade_samples=plan.loop_fade)
+                return out["wav"], out["rate"], out["mel"]
             if plan.mode == "extend":
                 out = self.extend(cond, seeds, wav, plan.extend_frames, fade_samples=plan.fade)
                 return out["wav"][:, :plan.n_out], plan.out_rate, None
@@ -369,6 +397,147 @@ class AudioLCMPipeline:
         kernels.wave_paste(out, gen, m, gen_start=h0 * FRAME_SAMPLES, fade_samples=fade, out=out)
         return dict(latent=z, wav=out, region=(a, L))
 
+    @torch.no_grad()
+    def edit_loop(self, cond: torch.Tensor, seeds: Optional[Sequence[int]], wav=None,
+                  latent: Optional[torch.Tensor] = None, mask=None, strength: float = 0.5,
+                  window: Optional[int] = None, overlap: Optional[int] = None, keep_original: bool = False,
+                  fade_samples: Optional[int] = None, halo_frames: int = 32, out_sample_rate: Optional[int] = None,
+                  level=None, loop_fade_samples: Optional[int] = None, sample_posterior: bool = True,
+                  steps: Optional[int] = None, unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
+                  joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
+        """A loop from a recording: ``edit_long(joint=True)`` on a ring.  The input is exactly one of ``wav`` (B, N) at
+        16 kHz, N = L * 512, encoded as the periodic signal it is about to become (``_encode_ring``), and ``latent``
+        (B, C, L); its L >= 2 frames are one period, frame L - 1 the left neighbour of frame 0.  ``mask`` (B, L), 1 =
+        regenerate; None = all ones, a variation of the whole ring at ``strength``.
+
+        The latent follows ``windows.ring_edit_regions`` on the batch's union mask (W = min(``window`` or
+        latent_shape[1], L), ``overlap`` = W // 2 by default).  A line region ("line", a, R, starts, W), which may lie
+        across the wrap, is gathered as z[:, :, (a + arange(R)) % L], denoised by ``edit_long(joint=True)``'s own
+        ``sample_joint(init=..., mask=...)`` call with the seeds ``recipe.window_seed(seed, r)`` and scattered back:
+        the new frames either side of the wrap are conditioned on both neighbours.  When the regions cover the ring,
+        the one entry ("ring", ...) is one ``sample_ring_edit`` call on the whole ring (r = 0).  Frames of mask 0
+        keep the input latent exactly; S DiT calls per region and clip.
+
+        ``keep_original=False``: the ring is decoded exactly as ``generate_loop`` decodes its latent (circular halo
+        min(``halo_frames``, L), ``out_sample_rate``, ``kernels.wave_loop`` with ``loop_fade_samples``, ``level``), and L
+        must be a multiple of ``audio_in.loop_multiple(rate)``; returns latent, mel, wav, rate and ext.
+
+        ``keep_original=True`` (needs ``wav``; 16 kHz only, so ``out_sample_rate``, ``level`` and ``loop_fade_samples``
+        are refused as ``edit_long`` refuses a rate): per entry of ``windows.ring_paste_regions(union, halo_frames)``
+        the frames (a + j) mod L, j < n, are decoded in one call and blended into a copy of ``wav`` by one in-place
+        ``kernels.wave_paste_ring`` with gen_start = a * 512; for ("ring",) the ring is cut open at frame a =
+        ``windows.ring_paste_cut(union, ceil(fade_samples / 512))`` and decoded from there once round,
+        z[:, :, (arange(L + 2h) + a - h) % L] with the circular halo h = min(``halo_frames``, L) either side, and the
+        centre N samples are pasted at gen_start = a * 512: every sample of gen has h frames of context.  a is the
+        middle of the longest run of kept frames when that leaves the fade's reach of kept frames either side of the
+        cut: the paste then does not use the decode where its two ends meet, and the samples either side of the
+        wrap are consecutive samples of the one decode, as they are for a region.  Without such a run (every frame
+        regenerated, or only short gaps) a = 0: the centre N samples at gen_start = 0, whose two ends meet at the
+        wrap as two renderings that agree to the halo's accuracy.  Samples further than ``fade_samples`` (default 512) from a
+        regenerated frame, measured round the ring, keep the input's bits.  ``halo_frames`` * 512 >= ``fade_samples``
+        always: a ring has no clip end that would exempt a region.  Returns latent, wav (B, N) and regions."""
+        from . import kernels
+        if (wav is None) == (latent is None):
+            raise ValueError("pass exactly one of `wav` and `latent`")
+        if keep_original and wav is None:
+            raise ValueError("keep_original needs the input waveform `wav`")
+        if keep_original and (out_sample_rate is not None or level is not None or loop_fade_samples is not None):
+            raise ValueError("`out_sample_rate`, `level` and `loop_fade_samples` are used without keep_original: a kept "
+                             "recording stays at 16 kHz and at its own level")
+        dev = torch.device("cuda")
+        S = steps or self.steps
+        if wav is not None:
+            wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
+            if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES:
+                raise ValueError(f"`wav` is (B, N) with N a multiple of {FRAME_SAMPLES}")
+            B, L = wav.shape[0], wav.shape[1] // FRAME_SAMPLES
+        else:
+            B, L = latent.shape[0], latent.shape[2]
+        if L < 2:
+            raise ValueError(f"a loop has at least 2 latent frames, got {L}")
+        halo = int(halo_frames)
+        if keep_original:
+            fade = FRAME_SAMPLES if fade_samples is None else int(fade_samples)
+            self._check_fade(fade, FRAME_SAMPLES, halo, fade, True)
+        else:
+            tail = self._loop_tail_plan(L, min(halo, L), loop_fade_samples, out_sample_rate)
+        if mask is None:
+            union = [True] * L
+        else:
+            mask = torch.as_tensor(mask, dtype=torch.float32)
+            if tuple(mask.shape) != (B, L):
+                raise ValueError(f"mask must be (B, L) = {(B, L)}, got {tuple(mask.shape)}")
+            union = (mask > 0).any(0).tolist()
+        W = min(window or self.latent_shape[1], L)
+        ov = W // 2 if overlap is None else overlap
+        plan = windows.ring_edit_regions(union, W, ov)
+        regions = windows.ring_paste_regions(union, halo) if keep_original else None
+
+        if wav is not None:
+            z = self._encode_ring(wav, seeds, S, sample_posterior, halo)
+        else:
+            z = latent.to(dev).float().clone()
+        kw = dict(guidance_scale=self.guidance_scale, original_inference_steps=self.original_inference_steps,
+                  unconditional_conditioning=unconditional, unconditional_guidance_scale=cfg_scale)
+        m = torch.ones((B, L)) if mask is None else mask.cpu()
+        for r, entry in enumerate(plan):
+            if entry[0] == "ring":
+                _, starts, Wr, ovr = entry
+                rseeds = None if seeds is None else [recipe.window_seed(sd, r) for sd in seeds]
+                z, _ = self.sampler.sample_ring_edit(S=S, conditioning=cond, init=z, starts=starts, window=Wr,
+                                                     overlap=ovr, mask=None if mask is None else m,
+                                                     strength=strength, seeds=rseeds,
+                                                     clips_per_call=joint_clips_per_call, **kw)
+            else:
+                _, a, R, starts, Wr = entry
+                idx = (a + torch.arange(R)) % L
+                zr = z[:, :, idx.to(dev)].contiguous()
+                self._joint_region(zr, m[:, idx], (0, R, starts, Wr), r, cond, seeds, S, ov, strength,
+                                   joint_clips_per_call, **kw)
+                z[:, :, idx.to(dev)] = zr
+        if not keep_original:
+            return dict(latent=z, **self._decode_loop(z, *tail, level))
+
+        out = wav.clone()
+        pm = m.to(dev).contiguous()
+        for region in regions:
+            if region == ("ring",):
+                # the ring is cut open at frame a, among kept frames where it has them, and decoded from there once
+                # round with the circular halo either side: every sample of gen has h frames of context
+                h = min(halo, L)
+                a = windows.ring_paste_cut(union, -(-fade // FRAME_SAMPLES))
+                idx = (torch.arange(L + 2 * h, device=dev) + a - h) % L
+                gen = self.decode(z[:, :, idx].contiguous())["wav"][:, h * FRAME_SAMPLES:(h + L) * FRAME_SAMPLES]
+            else:
+                a, n = region
+                gen = self.decode(z[:, :, ((a + torch.arange(n, device=dev)) % L)].contiguous())["wav"]
+            kernels.wave_paste_ring(out, gen.contiguous(), pm, gen_start=a * FRAME_SAMPLES, fade_samples=fade,
+                                    out=out)
+        return dict(latent=z, wav=out, regions=regions)
+
+    @torch.no_grad()
+    def loop_from(self, cond: torch.Tensor, seeds: Optional[Sequence[int]], wav, seam_frames: int = 32,
+                  strength: float = 1.0, mask=None, **kw) -> Dict[str, torch.Tensor]:
+        """Makes a recording loop: ``edit_loop(keep_original=True)`` under ``windows.seam_mask(L, seam_frames)``, OR-ed
+        with ``mask`` (B, L) when one is given.  Only the ``seam_frames`` frames either side of the wrap are made anew,
+        conditioned on the recording across the wrap on both sides; every other sample is the recording's own, bit for
+        bit, up to the paste's fade.  The defaults are choices, not measurements (no trained weights here to listen
+        to): a seam of 32 frames, about 1 s either side, and strength 1.0, so the seam frames start from pure noise.
+        ``kw`` are ``edit_loop``'s further arguments.  ValueError unless 1 <= seam_frames and 2 * seam_frames <= L."""
+        wav = torch.as_tensor(wav, dtype=torch.float32)
+        if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES:
+            raise ValueError(f"`wav` is (B, N) with N a multiple of {FRAME_SAMPLES}")
+        B, L = wav.shape[0], wav.shape[1] // FRAME_SAMPLES
+        if L < 2:
+            raise ValueError(f"a loop has at least 2 latent frames, got {L}")
+        m = torch.from_numpy(windows.seam_mask(L, seam_frames)).float().expand(B, L)
+        if mask is not None:
+            mask = torch.as_tensor(mask, dtype=torch.float32).cpu()
+            if tuple(mask.shape) != (B, L):
+                raise ValueError(f"mask must be (B, L) = {(B, L)}, got {tuple(mask.shape)}")
+            m = torch.maximum(m, mask)
+        return self.edit_loop(cond, seeds, wav=wav, mask=m.contiguous(), strength=strength, keep_original=True, **kw)
+
     def long_windows(self, latent_len: int, window: Optional[int] = None, overlap: Optional[int] = None):
         """``windows.long_windows``, the plan of ``generate_long``; ``window`` defaults to latent_shape[1]."""
         return windows.long_windows(latent_len, window or self.latent_shape[1], overlap)
@@ -439,9 +608,22 @@ class AudioLCMPipeline:
         125 / gcd(125, rate) (``audio_in.loop_multiple``; ValueError for L otherwise).  ``x_T`` (B, C, L) and ``noise``
         (S - 1, B, C, L) replace ``recipe.prompt_noise(seeds, S, C, L)``.  Returns latent (B, C, L), mel (the centre 2L
         frames), wav (B, N), rate, and ext, the extended waveform at that rate that wav was cut from."""
-        from . import kernels
-        from .audio_in import fade_samples_of, loop_multiple
         L = int(latent_len)
+        tail = self._loop_tail_plan(L, halo_frames, fade_samples, out_sample_rate)
+        starts, W, ov = self.loop_windows(L, window, overlap)
+        z, _ = self.sampler.sample_joint(S=steps or self.steps, conditioning=cond, length=L, starts=starts, window=W,
+                                         overlap=ov, seeds=seeds, x_T=x_T, noise=noise,
+                                         guidance_scale=self.guidance_scale,
+                                         original_inference_steps=self.original_inference_steps,
+                                         clips_per_call=joint_clips_per_call, ring=True)
+        return dict(latent=z, **self._decode_loop(z, *tail, level))
+
+    @staticmethod
+    def _loop_tail_plan(L: int, halo_frames, fade_samples, out_sample_rate):
+        """(rate, h, fade) of a loop's decode, checked before any GPU work: the output rate, the circular halo in
+        frames rounded up to ``audio_in.loop_multiple(rate)`` and the seam fade in output samples; ValueError as
+        ``generate_loop`` states them."""
+        from .audio_in import fade_samples_of, loop_multiple
         rate = SAMPLE_RATE if out_sample_rate is None else int(out_sample_rate)
         mult = loop_multiple(rate)
         if L < 2 or L % mult:
@@ -455,12 +637,15 @@ class AudioLCMPipeline:
         fade = fade_samples_of(32.0, rate) if fade_samples is None else int(fade_samples)
         if not 0 <= fade <= min(per_frame(h), per_frame(L)):
             raise ValueError(f"fade_samples must be in 0 .. {min(per_frame(h), per_frame(L))}: the halo's {h} frames")
-        starts, W, ov = self.loop_windows(L, window, overlap)
-        z, _ = self.sampler.sample_joint(S=steps or self.steps, conditioning=cond, length=L, starts=starts, window=W,
-                                         overlap=ov, seeds=seeds, x_T=x_T, noise=noise,
-                                         guidance_scale=self.guidance_scale,
-                                         original_inference_steps=self.original_inference_steps,
-                                         clips_per_call=joint_clips_per_call, ring=True)
+        return rate, h, fade
+
+    def _decode_loop(self, z, rate: int, h: int, fade: int, level=None):
+        """The tail of ``generate_loop`` and of ``edit_loop``: the ring latent z (B, C, L) decoded with a circular halo
+        of h frames in one ``decode`` call, resampled to ``rate`` as one signal, the period cut and its seam closed by
+        ``kernels.wave_loop`` and brought to ``level``: mel, wav, rate and ext."""
+        from . import kernels
+        L = z.shape[2]
+        per_frame = lambda n: n * FRAME_SAMPLES * rate // SAMPLE_RATE   # noqa: E731
         idx = (torch.arange(L + 2 * h, device=z.device) - h) % L
         dec = self.decode(z[:, :, idx].contiguous())
         ext = dec["wav"].contiguous()
@@ -471,7 +656,7 @@ class AudioLCMPipeline:
         wav = kernels.wave_loop(ext, per_frame(h), per_frame(L), fade)
         if level is not None:
             wav = kernels.normalize_loudness(wav, rate, level.loudness, level.peak_dbfs, level.true_peak)["wav"]
-        return dict(latent=z, mel=dec["mel"][..., 2 * h:2 * (h + L)], wav=wav, rate=rate, ext=ext)
+        return dict(mel=dec["mel"][..., 2 * h:2 * (h + L)], wav=wav, rate=rate, ext=ext)
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -124,6 +124,110 @@ def joint_edit_regions(union, window: int, overlap: Optional[int] = None):
     return plan
 
 
+def _ring_runs(union, widen: int):
+    """The maximal runs of true frames of the circular ``union``, each widened by ``widen`` frames either side, with
+    touching or overlapping runs merged round the ring: a list of (a, n), the frames (a + j) mod L for j < n, in
+    ascending a; or None when they cover the whole ring."""
+    todo = [bool(v) for v in union]
+    L = len(todo)
+    if not any(todo):
+        return []
+    if all(todo):
+        return None
+    p = todo.index(False)       # no run crosses a kept frame: the ring is walked from p + 1 to p + L, unwrapped
+    runs, t = [], p + 1
+    while t < p + L:
+        if not todo[t % L]:
+            t += 1
+            continue
+        hi = t
+        while todo[hi % L]:
+            hi += 1
+        a, b = t - widen, hi + widen
+        if runs and a <= runs[-1][1]:
+            runs[-1][1] = b
+        else:
+            runs.append([a, b])
+        t = hi
+    while len(runs) > 1 and runs[-1][1] >= runs[0][0] + L:      # the last run reaches the first across the wrap
+        runs[-1][1] = max(runs[-1][1], runs[0][1] + L)
+        runs.pop(0)
+    if sum(b - a for a, b in runs) >= L:
+        return None
+    return sorted((a % L, b - a) for a, b in runs)
+
+
+def ring_edit_regions(union, window: int, overlap: Optional[int] = None):
+    """The host plan of ``edit_loop`` for a ring of L = len(union) latent frames, ``union[t]`` true where any clip of
+    the batch regenerates frame t.  The maximal runs of regenerated frames are found circularly (a run may cross the
+    wrap), widened by ``overlap`` frames of known context either side and merged where they touch or overlap, also
+    across the wrap.  If what is left covers the whole ring the plan is one entry ("ring", starts, W, overlap) =
+    ("ring", *loop_windows(L, window, overlap)): the ring is denoised as a ring.  Otherwise every region is
+    ("line", a, R, starts, W): the frames (a + j) mod L, j < R, gathered into a line that is denoised jointly on
+    ``long_windows(R, window, overlap)``'s plan, in ascending a.  ``overlap`` defaults to min(window, L) // 2.  An
+    empty union gives [].  ValueError for a region of more than ``JOINT_MAX_WINDOWS`` windows."""
+    L = len(union)
+    overlap = min(window, L) // 2 if overlap is None else overlap
+    if not 0 < overlap < window:
+        raise ValueError("need 0 < overlap < window")
+    runs = _ring_runs(union, overlap)
+    if runs is None:
+        return [("ring", *loop_windows(L, window, overlap))]
+    plan = []
+    for a, R in runs:
+        spans, W = long_windows(R, window, overlap)
+        check_region_windows(a, a + R, len(spans), W)
+        plan.append(("line", a, R, [s for s, _ in spans], W))
+    return plan
+
+
+def ring_paste_regions(union, halo: int):
+    """The latent-frame regions ``edit_loop(keep_original=True)`` decodes: the circular runs of regenerated frames
+    widened by ``halo`` frames either side and merged round the ring, a list of (a, n), the frames (a + j) mod L for
+    j < n, in ascending a; [("ring",)] when they cover the whole ring."""
+    runs = _ring_runs(union, halo)
+    return [("ring",)] if runs is None else runs
+
+
+def ring_paste_cut(union, fade_frames: int) -> int:
+    """Where ``edit_loop(keep_original=True)`` cuts the ring open when its paste regions cover it: the frame a at which
+    the decoded ring starts and, L frames on, ends.  The two ends are two renderings of neighbouring frames, so the cut
+    belongs where the paste does not use the decode: a is the middle of the longest circular run of kept frames of
+    ``union`` (the first such run among equals), provided both sides of the cut are then at least ``fade_frames`` kept
+    frames away from a regenerated one (n // 2 >= fade_frames for a run of n, and n >= 2), so that g = 0 either side of
+    it.  Without such a run (every frame regenerated, or only short gaps) a = 0: the cut is the wrap itself, the
+    period's own first and last sample."""
+    todo = [bool(v) for v in union]
+    L = len(todo)
+    if all(todo) or not any(todo):
+        return 0
+    p = todo.index(True)
+    best, t = (0, 0), p + 1
+    while t < p + L:
+        if todo[t % L]:
+            t += 1
+            continue
+        hi = t
+        while not todo[hi % L]:
+            hi += 1
+        if hi - t > best[1]:
+            best = (t, hi - t)
+        t = hi
+    s, n = best
+    return (s + n // 2) % L if n >= 2 and n // 2 >= fade_frames else 0
+
+
+def seam_mask(L: int, seam_frames: int) -> np.ndarray:
+    """The mask of ``loop_from``: a bool array of L frames, true on the m = ``seam_frames`` frames either side of the
+    wrap, [L - m, L) and [0, m).  ValueError unless 1 <= m and 2 * m <= L."""
+    L, m = int(L), int(seam_frames)
+    if m < 1 or 2 * m > L:
+        raise ValueError(f"the seam takes 1 <= seam_frames and 2 * seam_frames <= the ring's {L} frames, got {m}")
+    mask = np.zeros(L, dtype=bool)
+    mask[:m] = mask[L - m:] = True
+    return mask
+
+
 @functools.lru_cache(maxsize=None)
 def _window_weights(starts: tuple, W: int, L: int, overlap: int, ring: bool) -> np.ndarray:
     K, least = len(starts), 2 if ring else 1

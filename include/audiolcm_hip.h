@@ -353,7 +353,7 @@ int alcm_lcm_step_joint(const float* x, const float* eps_cond, const float* eps_
  * atomics: an element's bits do not depend on B, the grid or the access width.  16-byte accesses under
  * alcm_lcm_step_joint's conditions with z0 and mask 16-byte aligned too, element accesses otherwise.
  * ALCM_E_INVALID for everything alcm_lcm_step_joint refuses and for a null eps_cond, z0 or mask.  B, C, L or W of 0: no
- * launch.  A ring form does not exist yet. */
+ * launch.  The ring's form is alcm_lcm_step_ring_edit. */
 int alcm_lcm_step_joint_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
                              const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
                              const float* z0, const float* mask, float* prev_out, float* denoised_out,
@@ -371,6 +371,24 @@ int alcm_lcm_step_ring(const float* x, const float* eps_cond, const float* eps_u
                        const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
                        float* prev_out, float* denoised_out, float* xw_out, int B, int C, int L, int W,
                        alcm_stream_t stream);
+/* alcm_lcm_step_ring_edit: alcm_lcm_step_ring with a known latent blended in, as alcm_lcm_step_joint_edit does on a
+ * line (a loop made from a recording; the same kernel body; no reference counterpart: the reference generates one
+ * window, LCMSampler.step, scheduling_lcm.py:465-486).  The arguments are alcm_lcm_step_ring's plus z0 (B, C, L) and
+ * mask (B, L) in [0, 1], 1 = regenerate.  Per element (b, c, t):
+ *   d  = alcm_lcm_step_ring's value, bit for bit (offsets modulo L, the chain over the covering windows in ascending k,
+ *        wn the ring's table);
+ *   d' = m * d + (1 - m) * z0[b, c, t] with m = mask[b, t]  (m = 1 gives d and m = 0 gives z0, bit for bit);
+ *   denoised_out = d',  prev_out = noise ? sqrt_a_prev * d' + sqrt_b_prev * noise : d',
+ *   xw_out = prev gathered with the wrap: at the offset (t - starts[k]) mod L of every covering window k.
+ * On a plan no window of which wraps (starts[K - 1] + W == L) the outputs are alcm_lcm_step_joint_edit's bits.  Any
+ * output may be NULL, not all three.  There is no gather-only form: the first DiT input comes from alcm_lcm_step_ring
+ * with eps_cond = NULL.  16-byte accesses under alcm_lcm_step_ring's conditions with z0 and mask 16-byte aligned too.
+ * ALCM_E_INVALID for everything alcm_lcm_step_ring refuses and for a null eps_cond, z0 or mask.  B, C, L or W of 0: no
+ * launch. */
+int alcm_lcm_step_ring_edit(const float* x, const float* eps_cond, const float* eps_uncond, float cfg_scale,
+                            const float* noise, const float* coeffs, const int* starts, int K, const float* wn,
+                            const float* z0, const float* mask, float* prev_out, float* denoised_out, float* xw_out,
+                            int B, int C, int L, int W, alcm_stream_t stream);
 /* alcm_wave_loop: one period of a looping clip cut from a longer decode of the same ring, with the seam closed, one
  * launch (no reference counterpart).
  *   ext (B, row_len): the decode of the ring's latent padded circularly; out (B, N); ramp (R entries, device):
@@ -411,6 +429,22 @@ int alcm_latent_init(const float* moments, const float* z0_in, const float* e0, 
  * launch (Ng = 0 out of place copies orig). */
 int alcm_wave_paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
                     int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R, alcm_stream_t stream);
+/* alcm_wave_paste_ring: alcm_wave_paste on one period of a loop, one launch (the same kernel body; no reference
+ * counterpart: the reference has no edit path).
+ *   orig, out (B, N) with N = T * frame_samples exactly; mask (B, T) is circular; gen (B, Ng), 0 <= Ng <= N, holds the
+ *   ring's samples (gen_start + i) mod N, i = 0 .. Ng - 1, 0 <= gen_start < N: it may go on across the wrap.
+ *   d is measured round the ring: frame T - 1 is the left neighbour of frame 0, so a regenerated frame T - 1 fades into
+ *   the first samples of frame 0 and a regenerated frame 0 into the last samples of frame T - 1.  g and out are
+ *   alcm_wave_paste's: g = 1 at d = 0, ramp[d] for 0 < d < R, 0 from R on and outside gen; out = orig where g = 0 and
+ *   gen where g = 1, both bit for bit, else the same fmaf(g, gen - orig, orig).
+ * In place (out == orig) only the frames gen covers are visited, modulo T.  16-byte accesses under alcm_wave_paste's
+ * conditions.
+ * ALCM_E_INVALID for a null orig, out or mask (gen with Ng > 0, ramp with R > 0), a negative size, frame_samples
+ * outside 1 .. 2^20, N != T * frame_samples, Ng > N, gen_start >= N, or R > 16 * frame_samples.  B, N or Ng of 0: no
+ * launch (Ng = 0 out of place copies orig). */
+int alcm_wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
+                         int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R,
+                         alcm_stream_t stream);
 /* alcm_resample: band-limited rational resampling of a batch of clips with the mean over the channels folded into
  * the read, one launch (no reference counterpart: the reference labels its 16 kHz samples with any rate it is given).
  *   x (B, N_in, channels), interleaved as a WAV file stores it; y (B, N_out), N_out = ceil(N_in * up / down);

@@ -12,6 +12,7 @@ Used to A/B kernel variants in one process and as the target of 
     python scripts/microbench.py longjoint  # 30 s long-form clip: chained windows vs windows denoised jointly
     python scripts/microbench.py editjoint  # 30 s recording: edit_long window by window vs jointly; extend
     python scripts/microbench.py loop       # 10 s and 30 s seamless loops vs open clips of the same length
+    python scripts/microbench.py loopfrom   # 10 s and 30 s recordings made into loops: seam repair and variation
 """
 import os
 import sys
@@ -752,9 +753,49 @@ def bench_loop(reps=7):
                       f"({r['launches']} launches)  {r['bytes'] / r['launches'] / 1e6:6.2f} MB per launch", flush=True)
 
 
+def bench_loopfrom(reps=7):
+    """A 10 s and a 30 s recording (312 and 936 frames, mixed policy) made into a loop at B = 1: ``loop_from`` (the seam
+    of 32 frames either side of the wrap, the rest kept) and the variation of the whole ring (``edit_loop`` without a
+    mask), beside ``generate_loop`` and ``edit_long(joint=True)`` (a variation of the same recording on a line) of
+    the same length, alternating in one process, median of 7 calls after 2 warm-ups, host clock around a device
+    synchronise; then the two ring kernels by the library's per-launch events"""
+    from audiolcm_amd import recipe
+    from audiolcm_amd.pipeline import AudioLCMPipeline
+    pipe = AudioLCMPipeline.from_recipe(0, split=True, encoder=True)
+    pipe.set_split("mixed")
+    ctx, seeds = recipe.synthetic_context(1).cuda(), [0]
+    for L in (312, 936):
+        wav = (torch.rand((1, L * 512), generator=torch.Generator().manual_seed(L)) - 0.5).cuda()
+        forms = {"generate_loop": lambda: pipe.generate_loop(ctx, seeds, L),
+                 "edit_long(joint=True)": lambda: pipe.edit_long(ctx, seeds, wav=wav, joint=True),
+                 "loop_from": lambda: pipe.loop_from(ctx, seeds, wav),
+                 "edit_loop (vary)": lambda: pipe.edit_loop(ctx, seeds, wav=wav)}
+        times = {k: [] for k in forms}
+        for i in range(2 + reps):
+            for k, fn in forms.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                if i >= 2:
+                    times[k].append((time.perf_counter() - t0) * 1e3)
+        for k in forms:
+            t = sorted(times[k])
+            print(f"loopfrom L={L} B=1 {k:22s}: median {t[len(t) // 2]:7.2f} ms  min {t[0]:7.2f}  max {t[-1]:7.2f} "
+                  f"({len(t)} calls)", flush=True)
+        _hip.profile_begin()
+        for _ in range(reps):
+            pipe.loop_from(ctx, seeds, wav)
+            pipe.edit_loop(ctx, seeds, wav=wav, mask=torch.ones((1, L)))
+        for r in _hip.profile_end():
+            if "ring" in r["name"] or "lcm_step_joint" in r["name"] or "joint_gather" in r["name"]:
+                print(f"loopfrom L={L} B=1 {r['name']}: {r['total_ms'] / r['launches'] * 1e3:6.1f} us by events "
+                      f"({r['launches']} launches)  {r['bytes'] / r['launches'] / 1e6:6.2f} MB per launch", flush=True)
+
+
 if __name__ == "__main__":
     _hip.require_device(0)
     which = sys.argv[1:] or ["op", "conv", "act"]
     spin(float(os.environ.get("SPIN", "3")))
     for w in which:
-        {"resample": bench_resample, "loudness": bench_loudness, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "editjoint": bench_editjoint, "loop": bench_loop, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()
+        {"resample": bench_resample, "loudness": bench_loudness, "paste": bench_paste, "editlong": bench_editlong, "longjoint": bench_longjoint, "editjoint": bench_editjoint, "loop": bench_loop, "loopfrom": bench_loopfrom, "tres": bench_tres, "tphase": bench_tphase, "xp": bench_xp, "h16": bench_h16, "text": bench_text, "tail1d": bench_tail1d, "tconv": bench_tconv, "tail1": bench_tail1, "attn": bench_attn, "act1": bench_act1, "wone": bench_wone, "op": bench_op, "op1": bench_op1, "conv": bench_conv, "wconv": bench_wconv, "tail": bench_tail, "ffn": bench_ffn, "act": bench_act, "conv1": bench_conv_one}[w]()

@@ -162,6 +162,9 @@ _SIGS = [
     ("alcm_loudness_hops", C.c_int, [fp, C.c_int, i64, i64, vp, C.c_int, vp, fp, vp, C.c_size_t, vp]),
     ("alcm_loudness_gain", C.c_int, [vp, fp, C.c_int, i64, C.c_int, C.c_float, C.c_float, fp, fp, vp]),
     ("alcm_wave_gain", C.c_int, [fp, fp, fp, C.c_int, i64, i64, i64, vp]),
+    ("alcm_limiter_workspace_bytes", C.c_size_t, [C.c_int, i64, C.c_int]),
+    ("alcm_limiter", C.c_int, [fp, fp, C.c_int, fp, fp, C.c_int, i64, i64, i64, i64, C.c_float, C.c_int, C.c_double,
+                               vp, C.c_size_t, vp]),
     ("alcm_sincos_embedding", C.c_int, [fp, C.c_float, fp, C.c_int, C.c_int, C.c_int, fp, vp]),
     ("alcm_model_create", C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(NamedTensor), C.c_int, C.c_int,
                                     C.POINTER(vp)]),

@@ -185,37 +185,57 @@ class Level:
     loudness: Optional[float]   # target integrated loudness in LUFS, None: none
     peak_dbfs: Optional[float]  # peak ceiling in dBFS, None: none
     true_peak: bool             # the ceiling acts on the 4x oversampled peak estimate
+    limiter: bool = False       # the ceiling is kept by the look-ahead limiter, not by a smaller static gain
+    lookahead_ms: float = 5.0   # the limiter's look-ahead
+    release_ms: float = 100.0   # the limiter's release time
 
 
 def check_level(loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-                true_peak: bool = False) -> Optional[Level]:
+                true_peak: bool = False, limiter: bool = False, limiter_lookahead_ms: float = 5.0,
+                limiter_release_ms: float = 100.0) -> Optional[Level]:
     """Validates the level options; None when none is given (the output is then written as it is).  A target is
     within -70 .. 0 LUFS, a ceiling is at most 0 dBFS, ``true_peak`` needs one of them, and a target alone implies a
-    ceiling of -1 dBFS, so that a normalised file never clips."""
+    ceiling of -1 dBFS, so that a normalised file never clips.  ``limiter`` needs one of them too: the ceiling is then
+    kept by the look-ahead limiter (``audiolcm_amd/limiter.py``), whose times must be a look-ahead of at least 0 ms
+    and a release above 0 ms; whether the look-ahead fits the kernel's 1024 samples is known at the rate that is
+    written (``finish_output``)."""
     from .loudness import ABS_GATE, DEFAULT_CEILING_DBFS
     if loudness is None and peak_dbfs is None:
         if true_peak:
             raise ValueError("true_peak says how the peak is measured: give it with loudness or peak_dbfs")
+        if limiter:
+            raise ValueError("limiter (--limiter) keeps a ceiling: give it with loudness or peak_dbfs (--loudness, "
+                             "--peak)")
         return None
+    if limiter:
+        from .limiter import check_times
+        check_times(limiter_lookahead_ms, limiter_release_ms)
     if loudness is not None and not (ABS_GATE <= float(loudness) <= 0.0):   # refuses NaN too
         raise ValueError(f"loudness must lie within {ABS_GATE:g} .. 0 LUFS, got {loudness!r}")
     if peak_dbfs is not None and not (-math.inf < float(peak_dbfs) <= 0.0):
         raise ValueError(f"peak_dbfs must be a finite ceiling of at most 0 dBFS, got {peak_dbfs!r}")
     return Level(None if loudness is None else float(loudness),
-                 DEFAULT_CEILING_DBFS if peak_dbfs is None else float(peak_dbfs), bool(true_peak))
+                 DEFAULT_CEILING_DBFS if peak_dbfs is None else float(peak_dbfs), bool(true_peak), bool(limiter),
+                 float(limiter_lookahead_ms), float(limiter_release_ms))
 
 
 def finish_output(wav16: torch.Tensor, out_sample_rate: Optional[int], level: Optional[Level] = None,
                   n_out: Optional[int] = None) -> Tuple[torch.Tensor, int]:
     """The output stage: (B, L) at 16 kHz on the device -> (what is written, its rate).  ``to_out_rate``, then a crop
     to ``n_out`` samples when given, then with ``level`` the normalisation of exactly those samples at that rate
-    (``kernels.normalize_loudness``).  ``level`` None launches nothing more than ``to_out_rate``."""
+    (``kernels.normalize_loudness``), with ``level.limiter`` through the limiter planned for them
+    (``limiter.plan``).  ``level`` None launches nothing more than ``to_out_rate``."""
     wav, rate = to_out_rate(wav16, out_sample_rate)
     if n_out is not None:
         wav = wav[:, :n_out]
     if level is not None:
         from . import kernels
-        wav = kernels.normalize_loudness(wav, rate, level.loudness, level.peak_dbfs, level.true_peak)["wav"]
+        lim = None
+        if level.limiter:
+            from . import limiter as _lm
+            lim = _lm.plan(rate, wav.shape[1], level.lookahead_ms, level.release_ms)
+        wav = kernels.normalize_loudness(wav, rate, level.loudness, level.peak_dbfs, level.true_peak,
+                                         limiter=lim)["wav"]
     return wav, rate
 
 
@@ -260,7 +280,7 @@ def ring_spans_mask(spans: Sequence[Tuple[float, float]], n_frames: int) -> np.n
 def plan_loop(init_audio: str, seam_s: float = 1.0, vary: bool = False,
               mask_spans: Optional[Sequence[Tuple[float, float]]] = None, fade_ms: float = 32.0, resample: bool = False,
               out_sample_rate: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-              true_peak: bool = False, loop_fade_ms: float = 32.0) -> EditPlan:
+              true_peak: bool = False, loop_fade_ms: float = 32.0, limiter: bool = False) -> EditPlan:
     """Reads the recording ``init_audio`` once and plans a loop made from it, or refuses with ValueError (the messages
     name the arguments and the command line's flags).  The recording is trimmed at its end to L whole latent frames,
     one period; ``dropped`` counts the samples that leaves out.  ``resample`` brings any input to 16 kHz first.
@@ -272,7 +292,12 @@ def plan_loop(init_audio: str, seam_s: float = 1.0, vary: bool = False,
 
     Mode "loop_vary": ``AudioLCMPipeline.edit_loop`` without a mask, the whole ring regenerated from the recording as a
     hint.  ``out_sample_rate``, the level and ``loop_fade_ms`` apply as for a loop from text, and L is trimmed further
-    to a multiple of ``loop_multiple(out_sample_rate)``."""
+    to a multiple of ``loop_multiple(out_sample_rate)``.  ``limiter`` is refused in both modes: its gain varies in
+    time and starts from 1 at the first sample, which would break the period that a static gain keeps."""
+    if limiter:
+        raise ValueError("limiter (--limiter) does not combine with loop_from (--loop-from), with or without loop_vary "
+                         "(--loop-vary): a gain that varies in time and starts from 1 at the first sample would break "
+                         "the period")
     level = check_level(loudness, peak_dbfs, true_peak)
     out_sample_rate = check_out_rate(out_sample_rate)
     if not vary and (level is not None or out_sample_rate is not None):
@@ -330,12 +355,14 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
               fade_ms: float = 32.0, resample: bool = False, out_sample_rate: Optional[int] = None,
               max_frames: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
               true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None, loop_from: bool = False,
-              loop_seam_s: float = 1.0, loop_vary: bool = False, loop_fade_ms: float = 32.0) -> EditPlan:
+              loop_seam_s: float = 1.0, loop_vary: bool = False, loop_fade_ms: float = 32.0, limiter: bool = False,
+              limiter_lookahead_ms: float = 5.0, limiter_release_ms: float = 100.0) -> EditPlan:
     """Reads ``init_audio`` once and decides the request, or refuses it with ValueError.  No ``mask_spans``: a
     variation; with them: an inpainting of the clip (both crop to ``max_frames`` latent frames here when given;
     ``run_edit`` crops to the DiT's limit in any case); ``keep_original``: the whole frames inside the spans are
     regenerated in a clip of any length, at 16 kHz or, with ``resample``, at the recording's own rate.  ``loudness``,
-    ``peak_dbfs``, ``true_peak``: the level of the output (``check_level``); refused with ``keep_original``.
+    ``peak_dbfs``, ``true_peak``, ``limiter``, ``limiter_lookahead_ms``, ``limiter_release_ms``: the level of the output
+    (``check_level``); refused with ``keep_original``, and the limiter wherever a level is and with every loop.
     ``joint``: the frames to regenerate are denoised jointly (``edit_long(joint=True)``); a variation or an inpainting
     is then made from the whole recording instead of a crop to the DiT's limit.  ``extend_s``: the recording is
     continued by that many seconds (``AudioLCMPipeline.extend``, ``extend_counts``) at 16 kHz; with ``resample`` any
@@ -351,13 +378,16 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
             raise ValueError("loop_from (--loop-from) does not combine with keep_original (--keep-original) or extend_s "
                              "(--extend): it keeps the recording by itself, and a continued recording does not loop")
         return plan_loop(init_audio, loop_seam_s, loop_vary, mask_spans, fade_ms, resample, out_sample_rate, loudness,
-                         peak_dbfs, true_peak, loop_fade_ms)
+                         peak_dbfs, true_peak, loop_fade_ms, limiter)
     if extend_s is not None:
         if mask_spans or keep_original:
             raise ValueError("extend_s continues the recording: it does not combine with mask_spans or keep_original")
         if loudness is not None or peak_dbfs is not None or true_peak:
             raise ValueError("extend_s keeps the recording's samples bit for bit; loudness, peak_dbfs and true_peak "
                              "would scale them")
+        if limiter:
+            raise ValueError("extend_s (--extend) keeps the recording's samples bit for bit; limiter (--limiter) would "
+                             "scale them")
         if out_sample_rate is not None:
             raise ValueError(f"extend_s writes {SAMPLE_RATE} Hz, the rate it keeps the recording at, not "
                              f"out_sample_rate {out_sample_rate}")
@@ -367,7 +397,10 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
                         fade_samples_of(fade_ms, rate), rate, False, 32768.0, False, None, True, frames, n_out)
     if keep_original and not mask_spans:
         raise ValueError("keep_original needs mask_spans: the time spans to regenerate")
-    level = check_level(loudness, peak_dbfs, true_peak)
+    if keep_original and limiter:
+        raise ValueError("keep_original (--keep-original) keeps the input's samples bit for bit outside the spans; "
+                         "limiter (--limiter) would scale them")
+    level = check_level(loudness, peak_dbfs, true_peak, limiter, limiter_lookahead_ms, limiter_release_ms)
     if keep_original and level is not None:
         raise ValueError("keep_original keeps the input's samples bit for bit outside the spans; loudness, peak_dbfs and "
                          "true_peak would scale them")

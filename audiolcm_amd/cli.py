@@ -46,6 +46,10 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
     samples that are written; ``--peak DBFS`` scales a clip down where its peak would pass that ceiling (-1 dBFS when
     only ``--loudness`` is given); ``--true-peak`` lets the ceiling act on the 4x oversampled peak estimate.  Refused
     with ``--keep-original``, whose kept samples they would scale;
+  * ``--limiter`` (with ``--loudness`` or ``--peak``) keeps the ceiling with a look-ahead peak limiter on the GPU
+    instead of a smaller gain for the whole clip, so that a clip with short loud peaks still reaches ``--loudness``;
+    ``--limiter-lookahead-ms`` (5) and ``--limiter-release-ms`` (100) are its times.  Refused wherever a level is, and
+    with ``--loop`` and ``--loop-from``: a gain that varies in time would break the period;
   * ``--synthetic-seed N`` runs on the seeded recipe weights (no checkpoints offline).
 """
 from __future__ import annotations
@@ -116,6 +120,13 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                    help="peak ceiling of every output in dBFS, at most 0 (default with --loudness: -1)")
     p.add_argument("--true-peak", action="store_true",
                    help="with --loudness or --peak: the ceiling acts on the 4x oversampled peak estimate")
+    p.add_argument("--limiter", action="store_true",
+                   help="with --loudness or --peak: keep the ceiling with a look-ahead limiter on the GPU instead of a "
+                        "smaller gain for the whole clip, so that the clip still reaches --loudness (DESIGN.md §5)")
+    p.add_argument("--limiter-lookahead-ms", type=float, default=5.0, metavar="MS",
+                   help="with --limiter: the look-ahead, at most 1024 samples at the rate written (default 5)")
+    p.add_argument("--limiter-release-ms", type=float, default=100.0, metavar="MS",
+                   help="with --limiter: the release time, above 0 (default 100)")
     p.add_argument("--duration", type=float, default=None,
                    help="clip length in seconds, generated by windowed continuation (default: one window of --W frames)")
     p.add_argument("--long-joint", action="store_true",
@@ -155,7 +166,8 @@ class GenSamples:
         self.channel_dim = model.channels
         self.original_inference_steps = original_inference_steps
         self.plan = plan
-        self.level = check_level(opt.loudness, opt.peak, opt.true_peak)
+        self.level = check_level(opt.loudness, opt.peak, opt.true_peak, opt.limiter, opt.limiter_lookahead_ms,
+                                 opt.limiter_release_ms)
 
     @functools.cached_property
     def pipeline(self):
@@ -243,6 +255,9 @@ def check_loop_from(opt) -> None:
         raise ValueError("--loop-vary is used with --loop-from")
     if not opt.loop_from:
         return
+    if opt.limiter:
+        raise ValueError("--limiter does not combine with --loop-from, with or without --loop-vary: a gain that varies "
+                         "in time and starts from 1 at the first sample would break the period")
     for flag, given in (("--loop", opt.loop), ("--init-audio", opt.init_audio), ("--inpaint", opt.inpaint),
                         ("--keep-original", opt.keep_original), ("--duration", opt.duration is not None),
                         ("--extend", opt.extend is not None)):
@@ -274,6 +289,8 @@ def build(opt):
         if opt.loudness is not None or opt.peak is not None or opt.true_peak:
             raise ValueError("--extend keeps the recording's samples bit for bit; --loudness, --peak and --true-peak "
                              "would scale them")
+        if opt.limiter:
+            raise ValueError("--extend keeps the recording's samples bit for bit; --limiter would scale them")
         if opt.out_sample_rate is not None:
             raise ValueError("--extend writes 16 kHz, the rate it keeps the recording at: it does not combine with "
                              "--out-sample-rate")
@@ -283,6 +300,9 @@ def build(opt):
                              "--keep-original")
         if opt.loop_fade_ms < 0:
             raise ValueError("--loop-fade-ms must not be negative")
+        if opt.limiter:
+            raise ValueError("--limiter does not combine with --loop: a gain that varies in time and starts from 1 at "
+                             "the first sample would break the period that a static gain keeps")
         mult = loop_multiple(check_out_rate(opt.out_sample_rate) or SAMPLE_RATE)
         if loop_period(opt) < 2 or loop_period(opt) % mult:
             raise ValueError(f"--loop without --duration: the period of --W {opt.W} frames must be at least 2 and, at "
@@ -304,11 +324,20 @@ def build(opt):
     if opt.resample and not opt.init_audio and not opt.loop_from:
         raise ValueError("--resample is used with --init-audio")
     check_out_rate(opt.out_sample_rate)
-    check_level(opt.loudness, opt.peak, opt.true_peak)
+    if opt.limiter and opt.keep_original:
+        raise ValueError("--keep-original keeps the input's samples bit for bit outside the spans; --limiter would "
+                         "scale them")
+    level = check_level(opt.loudness, opt.peak, opt.true_peak, opt.limiter, opt.limiter_lookahead_ms,
+                        opt.limiter_release_ms)
+    if level is not None and level.limiter:   # the look-ahead must fit the kernel at the rate that is written
+        from . import limiter as _lm
+        _lm.plan(check_out_rate(opt.out_sample_rate) or SAMPLE_RATE, 0, level.lookahead_ms, level.release_ms)
     # the file and the flags decide: a refused request fails before the models are built
     plan = plan_edit(opt.init_audio, parse_spans(opt.mask_spans) if opt.inpaint else None, opt.keep_original,
                      opt.fade_ms, opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
-                     true_peak=opt.true_peak, joint=opt.long_joint, extend_s=opt.extend) if opt.init_audio else None
+                     true_peak=opt.true_peak, joint=opt.long_joint, extend_s=opt.extend, limiter=opt.limiter,
+                     limiter_lookahead_ms=opt.limiter_lookahead_ms,
+                     limiter_release_ms=opt.limiter_release_ms) if opt.init_audio else None
     if opt.loop_from:
         plan = plan_edit(opt.loop_from, parse_spans(opt.mask_spans) if opt.mask_spans else None, False, opt.fade_ms,
                          opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,

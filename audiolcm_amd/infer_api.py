@@ -57,10 +57,11 @@ class GenSamples:
     def __init__(self, sampler: LCMSampler, model: LCM_audio, outpath: str, vocoder=None, save_mel=True,
                  save_wav=True, original_inference_steps=None, steps: int = 2, guidance_scale: float = 5.0,
                  out_sample_rate: Optional[int] = None, loudness: Optional[float] = None,
-                 peak_dbfs: Optional[float] = None, true_peak: bool = False):
+                 peak_dbfs: Optional[float] = None, true_peak: bool = False, limiter: bool = False,
+                 limiter_lookahead_ms: float = 5.0, limiter_release_ms: float = 100.0):
         self.sampler, self.model, self.outpath = sampler, model, outpath
         self.out_sample_rate = check_out_rate(out_sample_rate)
-        self.level = check_level(loudness, peak_dbfs, true_peak)
+        self.level = check_level(loudness, peak_dbfs, true_peak, limiter, limiter_lookahead_ms, limiter_release_ms)
         if save_wav:
             assert vocoder is not None
         self.vocoder = vocoder
@@ -128,13 +129,21 @@ def _build(config_path, model_path, vocoder_path, synthetic_seed, split, synthet
     return model, sampler, vocoder, steps_cfg
 
 
+def _check_limiter_rate(out_sample_rate: Optional[int], limiter: bool, lookahead_ms: float, release_ms: float) -> None:
+    """Refuses, before any model is built, limiter times that do not fit the rate that is written."""
+    if limiter:
+        from .limiter import plan
+        plan(out_sample_rate or SAMPLE_RATE, 0, lookahead_ms, release_ms)
+
+
 def AudioLCMBatchInfer(ori_prompts: List[str], config_path: str = "configs/audiolcm.yaml",
                        model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
                        batch_size: int = 32, synthetic_seed: Optional[int] = None, split: bool = True,
                        outpath: str = "results/test", seed: Optional[int] = None,
                        synthetic_tokenizer: bool = False, out_sample_rate: Optional[int] = None,
                        loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-                       true_peak: bool = False) -> str:
+                       true_peak: bool = False, limiter: bool = False, limiter_lookahead_ms: float = 5.0,
+                       limiter_release_ms: float = 100.0) -> str:
     """InferAPI.py:135-166. Returns the path of the last prompt's WAV.  ``seed``: per-prompt RNG seeds
     seed + i (default None: the global device RNG, as the reference).  ``synthetic_tokenizer``: run checkpoint
     weights on the hash-id tokenizer stand-in when the tokenizer directories are absent (tests only).
@@ -142,16 +151,22 @@ def AudioLCMBatchInfer(ori_prompts: List[str], config_path: str = "configs/audio
     ``loudness``: bring each clip to that ITU-R BS.1770 integrated loudness in LUFS (-70 .. 0), measured on the GPU on
     the samples that are written; ``peak_dbfs``: scale a clip down where its peak would pass that ceiling (at most 0
     dBFS; -1 when only ``loudness`` is given, so a normalised file never clips); ``true_peak``: the ceiling acts on the
-    4x oversampled peak estimate.  Without the three the samples are written as generated."""
+    4x oversampled peak estimate.  Without the three the samples are written as generated.  ``limiter`` (with
+    ``loudness`` or ``peak_dbfs``): the ceiling is kept by a look-ahead limiter on the GPU (``audiolcm_amd/limiter.py``)
+    instead of a smaller gain for the whole clip, so a clip with a binding ceiling still reaches ``loudness``;
+    ``limiter_lookahead_ms`` (at most 1024 samples at the rate written) and ``limiter_release_ms`` (above 0) are its
+    times, 5 and 100 ms by choice, not by a listening test."""
     check_out_rate(out_sample_rate)
-    check_level(loudness, peak_dbfs, true_peak)
+    check_level(loudness, peak_dbfs, true_peak, limiter, limiter_lookahead_ms, limiter_release_ms)
+    _check_limiter_rate(out_sample_rate, limiter, limiter_lookahead_ms, limiter_release_ms)
     prompts = [dict(ori_caption=p, struct_caption=struct_caption(p)) for p in ori_prompts]
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  synthetic_tokenizer)
     os.makedirs(outpath, exist_ok=True)
     gen = GenSamples(sampler, model, outpath, vocoder, save_mel=False, save_wav=True,
                      original_inference_steps=orig_steps, out_sample_rate=out_sample_rate, loudness=loudness,
-                     peak_dbfs=peak_dbfs, true_peak=true_peak)
+                     peak_dbfs=peak_dbfs, true_peak=true_peak, limiter=limiter,
+                     limiter_lookahead_ms=limiter_lookahead_ms, limiter_release_ms=limiter_release_ms)
     names = [wav_name_for(p["ori_caption"]) for p in prompts]
     with torch.no_grad():
         for lo in range(0, len(prompts), batch_size):
@@ -166,11 +181,14 @@ def AudioLCMInfer(ori_prompt: str, config_path: str = "configs/audiolcm.yaml",
                   model_path: str = "./model/000184.ckpt", vocoder_path: str = "./model/vocoder",
                   synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
                   seed: Optional[int] = None, out_sample_rate: Optional[int] = None,
-                  loudness: Optional[float] = None, peak_dbfs: Optional[float] = None, true_peak: bool = False) -> str:
-    """InferAPI.py:103-133.  ``loudness``, ``peak_dbfs``, ``true_peak``: as ``AudioLCMBatchInfer``."""
+                  loudness: Optional[float] = None, peak_dbfs: Optional[float] = None, true_peak: bool = False,
+                  limiter: bool = False, limiter_lookahead_ms: float = 5.0, limiter_release_ms: float = 100.0) -> str:
+    """InferAPI.py:103-133.  ``loudness``, ``peak_dbfs``, ``true_peak`` and the limiter's three: as
+    ``AudioLCMBatchInfer``."""
     return AudioLCMBatchInfer([ori_prompt], config_path, model_path, vocoder_path, 1, synthetic_seed, split, outpath,
                               seed, out_sample_rate=out_sample_rate, loudness=loudness, peak_dbfs=peak_dbfs,
-                              true_peak=true_peak)
+                              true_peak=true_peak, limiter=limiter, limiter_lookahead_ms=limiter_lookahead_ms,
+                              limiter_release_ms=limiter_release_ms)
 
 
 # ---------------------------------------------------------------------------- audio-conditioned generation
@@ -187,7 +205,8 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: Optional[float
                       loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
                       true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None,
                       loop_from: bool = False, loop_seam_s: float = 1.0, loop_vary: bool = False,
-                      loop_fade_ms: float = 32.0) -> str:
+                      loop_fade_ms: float = 32.0, limiter: bool = False, limiter_lookahead_ms: float = 5.0,
+                      limiter_release_ms: float = 100.0) -> str:
     """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength`` (default 0.5), or, with ``mask_spans``
     ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
     clip is synthesised again from the latent, cropped to the DiT's 845 frames.  ``keep_original`` (needs
@@ -201,6 +220,8 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: Optional[float
     ``out_sample_rate``: the output is resampled from 16 kHz to that rate on the GPU and written under it (with
     ``keep_original`` it may only name the input's rate).  ``loudness``, ``peak_dbfs``, ``true_peak``: the level of the
     output, as ``AudioLCMBatchInfer``; refused with ``keep_original``, whose kept samples they would scale.
+    ``limiter``, ``limiter_lookahead_ms``, ``limiter_release_ms``: as ``AudioLCMBatchInfer``; refused wherever a level
+    is, and with ``loop_from`` in both its modes: its time-varying gain would break the period.
     ``joint``: the frames to regenerate are denoised jointly (``edit_long(joint=True)``: S DiT calls per region of
     regenerated frames instead of S per window); a variation or an inpainting without ``keep_original`` is then made
     from the whole recording, not from a crop to 845 frames.
@@ -224,7 +245,11 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: Optional[float
         strength = 1.0 if loop_from and not loop_vary else 0.5
     plan = plan_edit(init_audio, mask_spans, keep_original, fade_ms, resample, out_sample_rate, loudness=loudness,
                      peak_dbfs=peak_dbfs, true_peak=true_peak, joint=joint, extend_s=extend_s, loop_from=loop_from,
-                     loop_seam_s=loop_seam_s, loop_vary=loop_vary, loop_fade_ms=loop_fade_ms)  # before any model
+                     loop_seam_s=loop_seam_s, loop_vary=loop_vary, loop_fade_ms=loop_fade_ms, limiter=limiter,
+                     limiter_lookahead_ms=limiter_lookahead_ms,
+                     limiter_release_ms=limiter_release_ms)  # before any model
+    _check_limiter_rate(None if plan.out_rate == SAMPLE_RATE else plan.out_rate, limiter, limiter_lookahead_ms,
+                        limiter_release_ms)
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,
                                                  encoder=True)
     pipe = AudioLCMPipeline(model, vocoder.generator, steps=2, original_inference_steps=orig_steps,
@@ -243,7 +268,8 @@ def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: st
                       synthetic_seed: Optional[int] = None, split: bool = True, outpath: str = "results/test",
                       seed: Optional[int] = None, out_sample_rate: Optional[int] = None, joint: bool = False,
                       loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-                      true_peak: bool = False, loop: bool = False, loop_fade_ms: float = 32.0) -> str:
+                      true_peak: bool = False, loop: bool = False, loop_fade_ms: float = 32.0, limiter: bool = False,
+                      limiter_lookahead_ms: float = 5.0, limiter_release_ms: float = 100.0) -> str:
     """A clip of ceil(duration_s * 16000 / 512) latent frames by long-form continuation
     (``AudioLCMPipeline.generate_long``).  ``seed`` None draws the clip's base seed from the global RNG.
     ``joint``: the windows are denoised jointly, one DiT call per LCM step (``generate_long(joint=True)``).
@@ -256,10 +282,16 @@ def AudioLCMLongInfer(ori_prompt: str, duration_s: float = 30.0, config_path: st
     period is ``audio_in.loop_frames(duration_s, out_sample_rate)`` latent frames: ``duration_s`` rounded up to whole
     frames, and to a multiple of 5 frames at 44.1 and 22.05 kHz.  The file holds exactly one period at the output rate
     and is never cropped to ``duration_s``: a crop would cut the seam.  ``joint`` is then redundant.
+    ``limiter``, ``limiter_lookahead_ms``, ``limiter_release_ms``: as ``AudioLCMBatchInfer``; refused with ``loop``: a
+    gain that varies in time and starts from 1 at the first sample would break the period that a static gain keeps.
     Returns the WAV path."""
     from .pipeline import AudioLCMPipeline
+    if loop and limiter:
+        raise ValueError("limiter (--limiter) does not combine with loop (--loop): a gain that varies in time and "
+                         "starts from 1 at the first sample would break the period that a static gain keeps")
     check_out_rate(out_sample_rate)
-    level = check_level(loudness, peak_dbfs, true_peak)
+    level = check_level(loudness, peak_dbfs, true_peak, limiter, limiter_lookahead_ms, limiter_release_ms)
+    _check_limiter_rate(out_sample_rate, limiter, limiter_lookahead_ms, limiter_release_ms)
     if loop and loop_fade_ms < 0:
         raise ValueError("loop_fade_ms must not be negative")
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split)

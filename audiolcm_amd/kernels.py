@@ -575,12 +575,15 @@ def _loudness_pass(wav: torch.Tensor, coef: Optional[torch.Tensor], hop: int, wa
 
 
 def _measure(wav: torch.Tensor, rate: int, true_peak: bool):
+    """(plan, hop sums, peak, the 4x oversampled copy the peak was taken from or None)."""
     from . import loudness as _ld
     pl = _ld.plan(rate, wav.shape[1])
     sums, peak = _loudness_pass(wav, loudness_coef(rate, wav.device), pl.hop, True, not true_peak)
+    over = None
     if true_peak:
-        peak = _loudness_pass(resample(wav.contiguous(), rate, 4 * int(rate)), None, pl.hop, False, True)[1]
-    return pl, sums, peak
+        over = resample(wav.contiguous(), rate, 4 * int(rate))
+        peak = _loudness_pass(over, None, pl.hop, False, True)[1]
+    return pl, sums, peak, over
 
 
 def _loudness_gain(pl, sums, peak, target: float, ceiling: float, want_lufs: bool, want_gain: bool):
@@ -598,29 +601,93 @@ def loudness(wav: torch.Tensor, rate: int, true_peak: bool = False):
     ``resample(wav, rate, 4 * rate)``; hop_sums (B, N // hop) float64), all on the device and without a host
     synchronisation (alcm_loudness_hops, alcm_loudness_gain; the plan: ``audiolcm_amd/loudness.py``).  ValueError for a
     clip under 400 ms."""
-    pl, sums, peak = _measure(wav, rate, true_peak)
+    pl, sums, peak, _ = _measure(wav, rate, true_peak)
     lufs, _ = _loudness_gain(pl, sums, peak, float("nan"), 0.0, True, False)
     return lufs, peak, sums
 
 
+def limit(wav: torch.Tensor, gain: torch.Tensor, ceiling: float, lookahead: int, release_coef: float,
+          env: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The look-ahead peak limiter (alcm_limiter; the definition and the plan: ``audiolcm_amd/limiter.py``): each clip
+    of wav (B, N) times its ``gain`` (B,) device fp32, turned down around the samples that would pass the linear
+    ``ceiling`` so that no |out| exceeds fp32(ceiling).  ``lookahead`` in samples (0 .. 1024), ``release_coef`` =
+    exp(-1 / (release_s * rate)) in [0, 1).  ``env`` (B, N) or (B, 4 N): an oversampled copy of the clip whose peaks
+    count too.  ``out`` None: a new tensor; ``out=wav`` limits in place, same bits.  No host synchronisation."""
+    B, N = wav.shape
+    assert gain.is_cuda and gain.dtype == torch.float32 and gain.is_contiguous() and gain.numel() == B
+    if out is None:
+        out = torch.empty(wav.shape, device=wav.device, dtype=torch.float32)
+    assert out.shape == wav.shape
+    os_, ld_env = 1, 0
+    if env is not None:
+        if env.shape[0] != B or env.shape[1] not in (N, 4 * N) or (N == 0 and env.shape[1] != 0):
+            raise ValueError(f"env must be (B, N) or (B, 4 N) = ({B}, {N}) or ({B}, {4 * N}), got {tuple(env.shape)}")
+        os_, ld_env = (4 if env.shape[1] == 4 * N and N > 0 else 1), _row_stride(env)
+    nbytes = lib().alcm_limiter_workspace_bytes(B, N, int(lookahead))
+    ws = torch.empty((max(nbytes, 8) + 7) // 8, device=wav.device, dtype=torch.float64)
+    check(lib().alcm_limiter(ptr(wav), ptr(env), os_, ptr(gain), ptr(out), B, N, _row_stride(wav), ld_env,
+                             _row_stride(out), float(ceiling), int(lookahead), float(release_coef), ptr(ws),
+                             ws.numel() * 8, stream_handle()), "limiter")
+    return out
+
+
 def normalize_loudness(wav: torch.Tensor, rate: int, target: Optional[float] = None,
                        peak_dbfs: Optional[float] = None, true_peak: bool = False,
-                       out: Optional[torch.Tensor] = None) -> dict:
+                       out: Optional[torch.Tensor] = None, limiter=None, passes: int = 3,
+                       report: bool = False) -> dict:
     """Scale each clip of wav (B, N) to ``target`` LUFS, and by less where its peak would pass ``peak_dbfs``: ->
     dict(wav, lufs (the input's), gain, peak (the input's)), device tensors.  ``target`` None: only the ceiling acts;
     ``peak_dbfs`` None: no ceiling.  The ceiling holds exactly for the sample peak: no |out| exceeds
     fp32(10^(peak_dbfs / 20)); with ``true_peak`` the peak is the 4x oversampled estimate and the ceiling holds for
-    it up to rounding.  ``out`` None: a new tensor; ``out=wav`` scales in place.  A gain of 1 returns the input's bits."""
-    pl, sums, peak = _measure(wav, rate, true_peak)
+    it up to rounding.  ``out`` None: a new tensor; ``out=wav`` scales in place.  A gain of 1 returns the input's bits.
+
+    ``limiter`` (a ``limiter.LimiterPlan``; needs ``peak_dbfs``): the ceiling is kept by ``limit`` instead of a smaller
+    static gain, so a clip with a binding ceiling still reaches the target.  The pre-gain is the gain to the target
+    with no ceiling (1 without a target).  Limiting lowers the loudness a little, so with a target and ``passes`` > 1
+    the limited clip is measured again and the pre-gain of the clips whose peak passes the ceiling (fl(peak g0) >
+    ceiling) is multiplied by the gain that measurement asks for, and the original is limited again: ``passes`` runs of
+    the limiter in all.  A clip whose peak never passes the ceiling is limited once with y = 1 and gets the bytes it
+    gets without a limiter.  With ``true_peak`` the limiter also sees ``resample(wav, rate, 4 * rate)``, the copy the peak
+    was measured on.  ``gain`` is
+    then the last pre-gain.  ``report``: the dict gains ``lufs_out``, the loudness of what is returned (one more
+    measurement).  Nothing synchronises with the host."""
+    pl, sums, peak, env = _measure(wav, rate, true_peak)
     ceiling = 0.0 if peak_dbfs is None else 10.0 ** (float(peak_dbfs) / 20.0)
-    lufs, gain = _loudness_gain(pl, sums, peak, float("nan") if target is None else float(target), ceiling, True, True)
-    if out is None:
-        out = torch.empty(wav.shape, device=wav.device, dtype=torch.float32)
-    assert out.shape == wav.shape
-    B, N = wav.shape
-    check(lib().alcm_wave_gain(ptr(wav), ptr(gain), ptr(out), B, N, _row_stride(wav), _row_stride(out), stream_handle()),
-          "wave_gain")
-    return dict(wav=out, lufs=lufs, gain=gain, peak=peak)
+    tgt = float("nan") if target is None else float(target)
+    if limiter is None:
+        lufs, gain = _loudness_gain(pl, sums, peak, tgt, ceiling, True, True)
+        if out is None:
+            out = torch.empty(wav.shape, device=wav.device, dtype=torch.float32)
+        assert out.shape == wav.shape
+        B, N = wav.shape
+        check(lib().alcm_wave_gain(ptr(wav), ptr(gain), ptr(out), B, N, _row_stride(wav), _row_stride(out),
+                                   stream_handle()), "wave_gain")
+    else:
+        if peak_dbfs is None:
+            raise ValueError("a limiter needs a ceiling: give peak_dbfs")
+        if int(passes) < 1:
+            raise ValueError(f"passes must be at least 1, got {passes!r}")
+        assert (limiter.rate, limiter.n) == (int(rate), wav.shape[1]), "the limiter's plan is for another clip"
+        if out is not None and out.data_ptr() == wav.data_ptr() and target is not None and int(passes) > 1:
+            raise ValueError("with a limiter and more than one pass the original is read again: out must not be wav")
+        lufs, gain = _loudness_gain(pl, sums, peak, tgt, 0.0, True, True)
+        binds = peak * gain > ceiling_f32(ceiling)
+        out = limit(wav, gain, ceiling, limiter.lookahead, limiter.release_coef, env, out)
+        for _ in range(int(passes) - 1 if target is not None else 0):
+            sums_k = _loudness_pass(out, loudness_coef(rate, wav.device), pl.hop, True, False)[0]
+            step = _loudness_gain(pl, sums_k, None, tgt, 0.0, False, True)[1]
+            gain = torch.where(binds, gain * step, gain)
+            out = limit(wav, gain, ceiling, limiter.lookahead, limiter.release_coef, env, out)
+    res = dict(wav=out, lufs=lufs, gain=gain, peak=peak)
+    if report:
+        sums_o = _loudness_pass(out, loudness_coef(rate, wav.device), pl.hop, True, False)[0]
+        res["lufs_out"] = _loudness_gain(pl, sums_o, None, float("nan"), 0.0, True, False)[0]
+    return res
+
+
+def ceiling_f32(ceiling: float) -> float:
+    """The linear ceiling as the kernels compare against it: rounded to fp32."""
+    return float(torch.tensor(float(ceiling), dtype=torch.float32))
 
 
 def sincos_embedding(v: torch.Tensor, freqs: torch.Tensor, scale: float, cos_first: bool) -> torch.Tensor:

@@ -655,6 +655,9 @@ class AudioLCMPipeline:
             raise RuntimeError(f"the extended waveform has {ext.shape[1]} samples, not {per_frame(L + 2 * h)}")
         wav = kernels.wave_loop(ext, per_frame(h), per_frame(L), fade)
         if level is not None:
+            if level.limiter:
+                raise ValueError("a loop takes a static gain only: the limiter's gain varies in time and starts from 1 "
+                                 "at the first sample, which would break the period")
             wav = kernels.normalize_loudness(wav, rate, level.loudness, level.peak_dbfs, level.true_peak)["wav"]
         return dict(mel=dec["mel"][..., 2 * h:2 * (h + L)], wav=wav, rate=rate, ext=ext)
 

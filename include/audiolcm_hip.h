@@ -498,6 +498,36 @@ int alcm_loudness_gain(const double* hop_sums, const float* peak, int B, int64_t
  * ALCM_E_INVALID for a null x, gain or y, a negative B or N, or a stride < N.  B or N of 0: no launch. */
 int alcm_wave_gain(const float* x, const float* gain, float* y, int B, int64_t N, int64_t ldx, int64_t ldy,
                    alcm_stream_t stream);
+/* alcm_limiter: a look-ahead peak limiter over a batch of mono clips (no reference counterpart), from the pre-gain
+ * gain[b] (device), the linear ceiling c, the look-ahead La = lookahead samples and the release coefficient
+ * a = release_coef = exp(-1 / (release_s * rate)).  Per clip, on x[0 .. N):
+ *   1. u[n] = fl32(x[n] * gain), the rounding of alcm_wave_gain;
+ *   2. e[n] = |u[n]|; with env (B, N * os) fp32, row stride ld_env, an oversampled copy of the clip, os 1 or 4:
+ *      e[n] = max(|u[n]|, max over k < os of |fl32(env[n * os + k] * gain)|);
+ *   3. r[n] = c / e[n] where e[n] > c, else 1; r = 1 outside [0, N);
+ *   4. the hold: m[j] = min r[j .. j + La], j = -La .. N - 1;
+ *   5. the attack: s[n] = mean m[n - La .. n]: every m of that window covers r[n], so s[n] <= r[n], and the gain
+ *      reaches what a peak needs exactly at the peak after a linear ramp of La samples;
+ *   6. the release: y[n] = min(s[n], a y[n-1] + (1 - a) s[n]), y[-1] = 1;
+ *   7. out[n] = copysign(min(|fl32(u[n] * fl32(y[n]))|, c), u[n]): no |out| exceeds c whatever the rounding.
+ * Steps 3 to 6 are fp64.  Two launches, no atomics, no host synchronisation.  A thread per 8 samples, a workgroup per
+ * 2048 with La samples of halo either side in LDS: the hold is a sliding maximum of e by doubling (c / e is
+ * monotone), the attack a prefix sum over the tile, and the release, whose steps y -> min(C, A y + D) are closed
+ * under composition, a scan of three doubles per chunk in the workgroup and a fold of the workgroups' maps in rising
+ * order.  s goes through ws, so the second launch reads only the samples it writes: y may be x itself and gives the
+ * bits of the out-of-place call.  A clip's bits depend on neither B, the strides nor the other clips; a clip none of
+ * whose e exceeds c gets alcm_wave_gain's bits.  Index arithmetic is 64-bit; 16-byte accesses to x (and y) when the
+ * pointers are 16-byte aligned and the strides multiples of 4, to env with os = 4 likewise; element accesses
+ * otherwise, same values.  env may be NULL: it is not read and os is ignored.
+ * ws: alcm_limiter_workspace_bytes(B, N, lookahead) bytes of device memory, 8-byte aligned (0 for an empty or
+ * invalid problem).  ALCM_E_INVALID, before any HIP call, for a null x, gain or y, os not 1 or 4 with an env, a
+ * negative B or N, ldx or ldy < N, ld_env < N * os, a ceiling that is not finite and positive, lookahead outside
+ * 0 .. 1024 (5 ms at 192 kHz), release_coef outside [0, 1), or a workspace that is null, misaligned or too small.
+ * B or N of 0: no launch. */
+size_t alcm_limiter_workspace_bytes(int B, int64_t N, int lookahead);
+int alcm_limiter(const float* x, const float* env, int os, const float* gain, float* y, int B, int64_t N, int64_t ldx,
+                 int64_t ld_env, int64_t ldy, float ceiling, int lookahead, double release_coef, void* ws,
+                 size_t ws_bytes, alcm_stream_t stream);
 /* out[b] = [f(v[b]*vscale*freqs[i]) ...]: cos_first ? [cos | sin] (TimestepEmbedder, concatDiT.py:49-67)
  *                                                   : [sin | cos] (get_guidance_scale_embedding, w*1000).
  * freqs: the reference's fp32 frequency table (half entries, device pointer) */

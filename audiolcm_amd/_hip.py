@@ -157,6 +157,10 @@ _SIGS = [
                                    C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_paste", C.c_int, [fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
     ("alcm_wave_paste_ring", C.c_int, [fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
+    ("alcm_seam_stats", C.c_int, [fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, vp,
+                                  vp]),
+    ("alcm_wave_paste_law", C.c_int, [fp, fp, fp, fp, fp, fp, fp, C.c_int, i64, i64, i64, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, vp]),
     ("alcm_resample", C.c_int, [fp, fp, C.c_int, i64, C.c_int, i64, C.c_int, C.c_int, fp, C.c_int, C.c_int, vp]),
     ("alcm_loudness_workspace_bytes", C.c_size_t, [C.c_int, i64, C.c_int]),
     ("alcm_loudness_hops", C.c_int, [fp, C.c_int, i64, i64, vp, C.c_int, vp, fp, vp, C.c_size_t, vp]),

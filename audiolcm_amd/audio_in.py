@@ -264,6 +264,22 @@ class EditPlan:
     seam_frames: int = 0                                # loop_from: the frames made anew either side of the wrap
     loop_fade: int = 0                                  # loop_vary: the seam fade of the decode, in output samples
     dropped: int = 0                                    # loop_from, loop_vary: the samples trimmed at the recording's end
+    fade_law: str = "linear"                            # the paste's fade law: "linear", "equal-power" or "matched"
+    match_gain: bool = False                            # the paste scales each regenerated run to the recording's level
+
+
+FADE_LAWS = ("linear", "equal-power", "matched")
+
+
+def check_fade_law(fade_law: str, match_gain: bool, pastes: bool, why: str = "") -> None:
+    """ValueError unless ``fade_law`` is one of ``FADE_LAWS`` and, where the request pastes nothing into a recording
+    (``pastes`` false; ``why`` says so in the message), both options are at their defaults."""
+    if fade_law not in FADE_LAWS:
+        raise ValueError(f"fade_law (--fade-law) must be one of {', '.join(FADE_LAWS)}, got {fade_law!r}")
+    if not pastes and (fade_law != "linear" or match_gain):
+        raise ValueError("fade_law and match_gain (--fade-law, --match-gain) act where regenerated audio is pasted into "
+                         "a recording: with keep_original, extend_s or loop_from (--keep-original, --extend, "
+                         "--loop-from)" + why)
 
 
 def ring_spans_mask(spans: Sequence[Tuple[float, float]], n_frames: int) -> np.ndarray:
@@ -280,7 +296,8 @@ def ring_spans_mask(spans: Sequence[Tuple[float, float]], n_frames: int) -> np.n
 def plan_loop(init_audio: str, seam_s: float = 1.0, vary: bool = False,
               mask_spans: Optional[Sequence[Tuple[float, float]]] = None, fade_ms: float = 32.0, resample: bool = False,
               out_sample_rate: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
-              true_peak: bool = False, loop_fade_ms: float = 32.0, limiter: bool = False) -> EditPlan:
+              true_peak: bool = False, loop_fade_ms: float = 32.0, limiter: bool = False, fade_law: str = "linear",
+              match_gain: bool = False) -> EditPlan:
     """Reads the recording ``init_audio`` once and plans a loop made from it, or refuses with ValueError (the messages
     name the arguments and the command line's flags).  The recording is trimmed at its end to L whole latent frames,
     one period; ``dropped`` counts the samples that leaves out.  ``resample`` brings any input to 16 kHz first.
@@ -293,7 +310,9 @@ def plan_loop(init_audio: str, seam_s: float = 1.0, vary: bool = False,
     Mode "loop_vary": ``AudioLCMPipeline.edit_loop`` without a mask, the whole ring regenerated from the recording as a
     hint.  ``out_sample_rate``, the level and ``loop_fade_ms`` apply as for a loop from text, and L is trimmed further
     to a multiple of ``loop_multiple(out_sample_rate)``.  ``limiter`` is refused in both modes: its gain varies in
-    time and starts from 1 at the first sample, which would break the period that a static gain keeps."""
+    time and starts from 1 at the first sample, which would break the period that a static gain keeps.
+    ``fade_law`` and ``match_gain`` are the paste's (``check_fade_law``): refused with ``vary``, which pastes nothing."""
+    check_fade_law(fade_law, match_gain, not vary, "; loop_vary (--loop-vary) decodes the whole ring and pastes nothing")
     if limiter:
         raise ValueError("limiter (--limiter) does not combine with loop_from (--loop-from), with or without loop_vary "
                          "(--loop-vary): a gain that varies in time and starts from 1 at the first sample would break "
@@ -331,7 +350,8 @@ def plan_loop(init_audio: str, seam_s: float = 1.0, vary: bool = False,
     mask = ring_spans_mask(mask_spans, L) if mask_spans else None
     return EditPlan(mode="loop_from", samples=samples, n_samples=samples.size, rate=rate, frame_samples=F, spans=None,
                     mask=mask, fade=fade_samples_of(fade_ms, rate), out_rate=rate, resample_out=False,
-                    pcm_scale=32768.0, native=False, seam_frames=m, dropped=x.size - samples.size)
+                    pcm_scale=32768.0, native=False, seam_frames=m, dropped=x.size - samples.size, fade_law=fade_law,
+                    match_gain=bool(match_gain))
 
 
 def extend_counts(n_samples: int, extend_s: float) -> Tuple[int, int, int]:
@@ -356,7 +376,8 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
               max_frames: Optional[int] = None, loudness: Optional[float] = None, peak_dbfs: Optional[float] = None,
               true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None, loop_from: bool = False,
               loop_seam_s: float = 1.0, loop_vary: bool = False, loop_fade_ms: float = 32.0, limiter: bool = False,
-              limiter_lookahead_ms: float = 5.0, limiter_release_ms: float = 100.0) -> EditPlan:
+              limiter_lookahead_ms: float = 5.0, limiter_release_ms: float = 100.0, fade_law: str = "linear",
+              match_gain: bool = False) -> EditPlan:
     """Reads ``init_audio`` once and decides the request, or refuses it with ValueError.  No ``mask_spans``: a
     variation; with them: an inpainting of the clip (both crop to ``max_frames`` latent frames here when given;
     ``run_edit`` crops to the DiT's limit in any case); ``keep_original``: the whole frames inside the spans are
@@ -370,7 +391,11 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
     ``keep_original``, with a level (it would scale the kept samples) and with ``out_sample_rate``.
     ``loop_from``: the recording is made to loop (``plan_loop``: modes "loop_from" and, with ``loop_vary``,
     "loop_vary"; ``loop_seam_s`` and ``loop_fade_ms`` are its ``seam_s`` and ``loop_fade_ms``).  Refused with
-    ``keep_original`` and ``extend_s``; ``loop_vary`` alone is refused too."""
+    ``keep_original`` and ``extend_s``; ``loop_vary`` alone is refused too.
+    ``fade_law`` ("linear", "equal-power", "matched") and ``match_gain``: the fade law and the gain alignment of the
+    paste (``kernels.paste``); refused (``check_fade_law``) wherever nothing is pasted: without ``keep_original``,
+    ``extend_s`` or ``loop_from``, and with ``loop_vary``."""
+    check_fade_law(fade_law, match_gain, bool(keep_original or extend_s is not None or loop_from))
     if loop_vary and not loop_from:
         raise ValueError("loop_vary (--loop-vary) is used with loop_from (--loop-from)")
     if loop_from:
@@ -378,7 +403,7 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
             raise ValueError("loop_from (--loop-from) does not combine with keep_original (--keep-original) or extend_s "
                              "(--extend): it keeps the recording by itself, and a continued recording does not loop")
         return plan_loop(init_audio, loop_seam_s, loop_vary, mask_spans, fade_ms, resample, out_sample_rate, loudness,
-                         peak_dbfs, true_peak, loop_fade_ms, limiter)
+                         peak_dbfs, true_peak, loop_fade_ms, limiter, fade_law, match_gain)
     if extend_s is not None:
         if mask_spans or keep_original:
             raise ValueError("extend_s continues the recording: it does not combine with mask_spans or keep_original")
@@ -394,7 +419,8 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
         x, rate, F = _read_mono(init_audio, resample)
         J, frames, n_out = extend_counts(x.size, extend_s)
         return EditPlan("extend", np.ascontiguousarray(x[:J * F]), x.size, rate, F, None, None,
-                        fade_samples_of(fade_ms, rate), rate, False, 32768.0, False, None, True, frames, n_out)
+                        fade_samples_of(fade_ms, rate), rate, False, 32768.0, False, None, True, frames, n_out,
+                        fade_law=fade_law, match_gain=bool(match_gain))
     if keep_original and not mask_spans:
         raise ValueError("keep_original needs mask_spans: the time spans to regenerate")
     if keep_original and limiter:
@@ -417,4 +443,4 @@ def plan_edit(init_audio: str, mask_spans: Optional[Sequence[Tuple[float, float]
     out_rate = rate if keep_original else out_sample_rate or SAMPLE_RATE
     return EditPlan(mode, samples, x.size, rate, F, spans, mask, fade_samples_of(fade_ms, rate), out_rate,
                     out_rate != rate, 32768.0 if keep_original else 32767.0, keep_original and resample, level,
-                    bool(joint))
+                    bool(joint), fade_law=fade_law, match_gain=bool(match_gain))

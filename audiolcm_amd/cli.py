@@ -35,6 +35,10 @@ output names and ``result.csv`` — with every model stage in libaudiolcm_hip.  
     ``--loop``.  ``--resample`` brings any input to 16 kHz first.  It does not combine with ``--loop``,
     ``--init-audio``, ``--inpaint``, ``--keep-original``, ``--duration`` or ``--extend``, and without ``--loop-vary``
     not with the level options or ``--out-sample-rate`` either;
+  * ``--fade-law {linear,equal-power,matched}`` and ``--match-gain`` (with ``--keep-original``, ``--extend`` or
+    ``--loop-from``; refused elsewhere and with ``--loop-vary``): the law of that fade, the linear crossfade, one that
+    keeps the power of uncorrelated signals, or of signals with the correlation measured at each junction on the GPU;
+    and each regenerated run scaled to the recording's level at its junctions (DESIGN.md §5, Fade laws);
   * ``--resample``: ``--init-audio`` may have any sample rate, 1 to 8 channels and PCM16, PCM24 or float32 samples; it
     is downmixed and resampled to 16 kHz on the GPU (alcm_resample; without the flag only 16 kHz mono PCM16 is read).
     With ``--keep-original`` the edit is done at the recording's own rate: mono, and a rate at which a latent frame is a
@@ -108,6 +112,13 @@ def parse_args(argv: Optional[Sequence[str]] = None):
                    help="with --inpaint: any clip length; keep the input waveform outside the spans bit for bit")
     p.add_argument("--fade-ms", type=float, default=32.0,
                    help="with --keep-original: the fade between the input and the regenerated audio, either side")
+    p.add_argument("--fade-law", type=str, default="linear", choices=["linear", "equal-power", "matched"],
+                   help="with --keep-original, --extend or --loop-from: the law of that fade: the linear crossfade, one "
+                        "that keeps the power of uncorrelated signals, or of signals with the correlation measured at "
+                        "each junction on the GPU (DESIGN.md §5)")
+    p.add_argument("--match-gain", action="store_true",
+                   help="with --keep-original, --extend or --loop-from: scale each regenerated run to the level of the "
+                        "recording, measured at the run's junctions on the GPU (DESIGN.md §5)")
     p.add_argument("--resample", action="store_true",
                    help="with --init-audio: read any rate, 1-8 channels, PCM16/PCM24/float32; resample to 16 kHz on "
                         "the GPU (with --keep-original: edit at the recording's own rate)")
@@ -274,8 +285,21 @@ def check_loop_from(opt) -> None:
         raise ValueError("--loop-from --loop-vary regenerates the whole ring: it does not take --mask-spans")
 
 
+def check_fade_law_flags(opt) -> None:
+    """``--fade-law`` and ``--match-gain`` are refused wherever nothing is pasted into a recording."""
+    if opt.fade_law == "linear" and not opt.match_gain:
+        return
+    if opt.loop_from and opt.loop_vary:
+        raise ValueError("--fade-law and --match-gain do not combine with --loop-from --loop-vary: the whole ring is "
+                         "decoded and nothing is pasted")
+    if not (opt.keep_original or opt.extend is not None or opt.loop_from):
+        raise ValueError("--fade-law and --match-gain act where regenerated audio is pasted into a recording: they are "
+                         "used with --keep-original, --extend or --loop-from")
+
+
 def build(opt):
     check_loop_from(opt)
+    check_fade_law_flags(opt)
     if opt.extend is not None:
         if not opt.init_audio:
             raise ValueError("--extend continues a recording: it needs --init-audio PATH")
@@ -336,13 +360,13 @@ def build(opt):
     plan = plan_edit(opt.init_audio, parse_spans(opt.mask_spans) if opt.inpaint else None, opt.keep_original,
                      opt.fade_ms, opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
                      true_peak=opt.true_peak, joint=opt.long_joint, extend_s=opt.extend, limiter=opt.limiter,
-                     limiter_lookahead_ms=opt.limiter_lookahead_ms,
-                     limiter_release_ms=opt.limiter_release_ms) if opt.init_audio else None
+                     limiter_lookahead_ms=opt.limiter_lookahead_ms, limiter_release_ms=opt.limiter_release_ms,
+                     fade_law=opt.fade_law, match_gain=opt.match_gain) if opt.init_audio else None
     if opt.loop_from:
         plan = plan_edit(opt.loop_from, parse_spans(opt.mask_spans) if opt.mask_spans else None, False, opt.fade_ms,
                          opt.resample, opt.out_sample_rate, loudness=opt.loudness, peak_dbfs=opt.peak,
                          true_peak=opt.true_peak, loop_from=True, loop_seam_s=opt.loop_seam, loop_vary=opt.loop_vary,
-                         loop_fade_ms=opt.loop_fade_ms)
+                         loop_fade_ms=opt.loop_fade_ms, fade_law=opt.fade_law, match_gain=opt.match_gain)
         if plan.dropped:
             print(f"--loop-from: the last {plan.dropped} samples of {opt.loop_from} are left out: the period is "
                   f"{plan.samples.size // plan.frame_samples} whole latent frames")

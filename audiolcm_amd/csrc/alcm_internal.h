@@ -75,6 +75,11 @@ int wave_paste(const float* orig, const float* gen, const float* mask, const flo
                int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s);
 int wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
                     int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s);
+int wave_paste_law(const float* orig, const float* gen, const float* mask, const float* ramp, const float* rho,
+                   const float* gam, float* out, int B, int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R,
+                   int ring, hipStream_t s);
+int seam_stats(const float* orig, const float* gen, const float* mask, int B, int64_t N, int64_t gen_start, int64_t Ng,
+               int T, int fs, int R, int ring, float* rho, float* gam, double* sums, hipStream_t s);
 int fill_f32(float* p, int64_t n, float v, hipStream_t s);
 int nct_to_cl(const float* x, int B, int C, int T, int Cp, float* y, hipStream_t s);
 // fp32 rows [rows][C] -> operand planes [rows][Cp] in the format of `prec` (SPLIT: lo plane rows * Cp after hi)

@@ -910,13 +910,45 @@ constexpr int kPasteTile = 8;
 constexpr int kPasteHalo = 16;  // frames the ramp may reach past a regenerated frame: R <= kPasteHalo * frame_samples
 constexpr int kPasteBlock = 256;
 
-template <int V, bool Ring>
+//
+// Law = true (wave_paste_law): the same tiling, mask search and in-place rules with another blend.  rho (B, T + 1) per
+// frame edge and gam (B, T) per regenerated frame are seam_stats' tables (rho NULL: 0 everywhere; gam NULL: 1).  A
+// sample of 0 < d < R takes the rho of the edge its d is measured from and the gam of the regenerated frame at that
+// edge (dl + i < dr - i: the run on the left, else the one on the right); a sample of d = 0 takes its own frame's
+// gam.  The thread that searches a frame's neighbours also reads their table entries into LDS.  The blend itself is
+// paste_law_blend, one rounding per operation in the order written there, shared by both access widths.
+__device__ __forceinline__ float paste_law_gain(float gam, float y) {
+#pragma clang fp contract(off)
+  return gam * y;
+}
+__device__ __forceinline__ float paste_law_blend(float g, float o, float y, float rho) {
+#pragma clang fp contract(off)
+  const float a = 1.f - g;
+  const float ao = a * o, gy = g * y;
+  const float s = ao + gy;
+  const float aa = a * a, gg = g * g;
+  const float q = aa + gg;
+  const float a2 = a + a;
+  const float c0 = a2 * g;
+  const float c = c0 * rho;
+  const float p = q + c;
+  const float n = 1.f / sqrtf(p);
+  return n * s;
+}
+
+// Tab: no further argument (wave_paste, wave_paste_ring) or the two tables rho and gam (wave_paste_law)
+template <int V, bool Ring, class... Tab>
 __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
     const float* orig, const float* __restrict__ gen, const float* __restrict__ mask, const float* __restrict__ ramp,
     float* out, int64_t N, int64_t Ng, int64_t gen_start, int T, int fs, int R, int H, int f_first, int f_end, int tiles,
-    FastDiv fsdiv) {
+    FastDiv fsdiv, Tab... tab) {
+  constexpr bool Law = sizeof...(Tab) != 0;
+  const float* const tabs[] = {tab..., nullptr, nullptr};
+  const float* const rho = tabs[0];
+  const float* const gam = tabs[1];
   __shared__ int s_reg[kPasteTile + 2 * kPasteHalo];
   __shared__ int s_kl[kPasteTile], s_kr[kPasteTile];
+  __shared__ float s_rho[Law ? 2 : 1][kPasteTile], s_gam[Law ? 2 : 1][kPasteTile];  // [0]: the left run's, [1]: the right
   const int b = blockIdx.x / tiles;
   const int f0 = f_first + (int)(blockIdx.x - (unsigned)b * tiles) * kPasteTile;
   const bool inplace = out == orig;
@@ -939,6 +971,25 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
     s_kl[threadIdx.x] = kl;
     s_kr[threadIdx.x] = kr;
     live = kl == 0 || (int64_t)(kl - 1) * fs + 1 < R || (int64_t)(kr - 1) * fs + 1 < R;
+    if constexpr (Law) {
+      // the entries of the nearest regenerated frame either side (kl = 0: the frame's own gam) and of the edge it ends at
+      float rl = 0.f, rr = 0.f, gl = 1.f, gr = 1.f;
+      int fl = f0 + (int)threadIdx.x - kl, fr = f0 + (int)threadIdx.x + kr;
+      if constexpr (Ring) {
+        fl %= T, fr %= T;
+        if (fl < 0) fl += T;
+      }
+      if (kl <= H && fl >= 0 && fl < T) {
+        if (gam) gl = gam[(int64_t)b * T + fl];
+        if (rho) rl = rho[(int64_t)b * (T + 1) + fl + 1];  // on a ring edge T holds edge 0's value
+      }
+      if (kr <= H && fr >= 0 && fr < T) {
+        if (gam) gr = gam[(int64_t)b * T + fr];
+        if (rho) rr = rho[(int64_t)b * (T + 1) + fr];
+      }
+      s_rho[0][threadIdx.x] = rl, s_rho[1][threadIdx.x] = rr;
+      s_gam[0][threadIdx.x] = gl, s_gam[1][threadIdx.x] = gr;
+    }
   }
   if (!__syncthreads_or(live) && inplace) return;
 
@@ -964,11 +1015,13 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
     const bool in_gen = gi >= 0 && gi + V <= Ng;
     FVec<V> g;
     bool any = false;
+    int right[V];  // Law: the element's d is measured from the run on the right
 #pragma unroll
     for (int i = 0; i < V; ++i) {
       const int64_t d = kl == 0 ? 0 : dl + i < dr - i ? dl + i : dr - i;
       g.v[i] = !in_gen ? 0.f : d == 0 ? 1.f : d < R ? ramp[d] : 0.f;
       any |= g.v[i] != 0.f;
+      if constexpr (Law) right[i] = kl != 0 && !(dl + i < dr - i);
     }
     if (!any) {
       if (!inplace) FVec<V>::ld(orig + row + n).st(out + row + n);
@@ -976,9 +1029,17 @@ __global__ __launch_bounds__(kPasteBlock) void wave_paste_kernel(
     }
     const FVec<V> ov = FVec<V>::ld(orig + row + n), gv = FVec<V>::ld(gen + (int64_t)b * Ng + gi);
     FVec<V> r;
+    if constexpr (Law) {
 #pragma unroll
-    for (int i = 0; i < V; ++i)
-      r.v[i] = g.v[i] == 1.f ? gv.v[i] : g.v[i] == 0.f ? ov.v[i] : fmaf(g.v[i], gv.v[i] - ov.v[i], ov.v[i]);
+      for (int i = 0; i < V; ++i) {
+        const float y = gam ? paste_law_gain(s_gam[right[i]][j], gv.v[i]) : gv.v[i];
+        r.v[i] = g.v[i] == 1.f ? y : g.v[i] == 0.f ? ov.v[i] : paste_law_blend(g.v[i], ov.v[i], y, s_rho[right[i]][j]);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < V; ++i)
+        r.v[i] = g.v[i] == 1.f ? gv.v[i] : g.v[i] == 0.f ? ov.v[i] : fmaf(g.v[i], gv.v[i] - ov.v[i], ov.v[i]);
+    }
     r.st(out + row + n);
   }
 }
@@ -1010,12 +1071,11 @@ static double wave_paste_blended(const std::vector<float>& m, int B, int64_t N, 
   return blended;
 }
 
-// The host side of both forms.  On a line gen lies inside the clip; on a ring N is the period exactly, gen starts inside
-// it, is no longer than it and may go on across the wrap.
+// The argument checks of every paste and of seam_stats, under the caller's name f.  On a line gen lies inside the clip;
+// on a ring N is the period exactly, gen starts inside it, is no longer than it and may go on across the wrap.
 template <bool Ring>
-static int paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
-                 int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
-  const std::string f = Ring ? "wave_paste_ring: " : "wave_paste: ";
+static int paste_check(const std::string& f, const float* orig, const float* gen, const float* mask, bool has_ramp,
+                       const float* out, int B, int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R) {
   if (!orig || !out || !mask) return set_error(ALCM_E_INVALID, f + "null orig, out or mask");
   if (B < 0 || N < 0 || Ng < 0 || gen_start < 0 || T < 0 || R < 0)
     return set_error(ALCM_E_INVALID, f + "negative B, N, Ng, gen_start, T or R");
@@ -1029,7 +1089,17 @@ static int paste(const float* orig, const float* gen, const float* mask, const f
     if (gen_start + Ng > N) return set_error(ALCM_E_INVALID, f + "gen reaches past the clip");
   }
   if (R > (int64_t)kPasteHalo * fs) return set_error(ALCM_E_INVALID, f + "R exceeds 16 frames");
-  if ((Ng > 0 && !gen) || (R > 0 && !ramp)) return set_error(ALCM_E_INVALID, f + "null gen or ramp");
+  if ((Ng > 0 && !gen) || (R > 0 && !has_ramp)) return set_error(ALCM_E_INVALID, f + "null gen or ramp");
+  return 0;
+}
+
+// The host side of every form.  law: wave_paste_law's kernel with the tables rho and gam (either may be null).
+template <bool Ring>
+static int paste(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B, int64_t N,
+                 int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s, bool law = false,
+                 const float* rho = nullptr, const float* gam = nullptr) {
+  const std::string f = law ? "wave_paste_law: " : Ring ? "wave_paste_ring: " : "wave_paste: ";
+  if (const int rc = paste_check<Ring>(f, orig, gen, mask, ramp != nullptr, out, B, N, gen_start, Ng, T, fs, R)) return rc;
   if (B == 0 || N == 0) return 0;
   const bool inplace = out == orig;
   if (Ng == 0) {  // nothing to blend: no launch
@@ -1053,19 +1123,27 @@ static int paste(const float* orig, const float* gen, const float* mask, const f
     blended = wave_paste_blended<Ring>(m, B, N, gen_start, Ng, T, fs, R, H);
   }
   void* tok = prof_start(s);
-  if (vec)
-    hipLaunchKernelGGL((wave_paste_kernel<4, Ring>), dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen,
-                       mask, ramp, out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)fb, (int)tiles,
-                       FastDiv((uint32_t)fs));
+  const dim3 grid((unsigned)(tiles * B)), block(kPasteBlock);
+  const FastDiv fsdiv((uint32_t)fs);
+  if (law && vec)
+    hipLaunchKernelGGL((wave_paste_kernel<4, Ring, const float*, const float*>), grid, block, 0, s, orig, gen, mask, ramp, out, N, Ng, gen_start,
+                       T, fs, R, H, (int)fa, (int)fb, (int)tiles, fsdiv, rho, gam);
+  else if (law)
+    hipLaunchKernelGGL((wave_paste_kernel<1, Ring, const float*, const float*>), grid, block, 0, s, orig, gen, mask, ramp, out, N, Ng, gen_start,
+                       T, fs, R, H, (int)fa, (int)fb, (int)tiles, fsdiv, rho, gam);
+  else if (vec)
+    hipLaunchKernelGGL((wave_paste_kernel<4, Ring>), grid, block, 0, s, orig, gen, mask, ramp, out, N, Ng, gen_start, T,
+                       fs, R, H, (int)fa, (int)fb, (int)tiles, fsdiv);
   else
-    hipLaunchKernelGGL((wave_paste_kernel<1, Ring>), dim3((unsigned)(tiles * B)), dim3(kPasteBlock), 0, s, orig, gen,
-                       mask, ramp, out, N, Ng, gen_start, T, fs, R, H, (int)fa, (int)fb, (int)tiles,
-                       FastDiv((uint32_t)fs));
+    hipLaunchKernelGGL((wave_paste_kernel<1, Ring>), grid, block, 0, s, orig, gen, mask, ramp, out, N, Ng, gen_start, T,
+                       fs, R, H, (int)fa, (int)fb, (int)tiles, fsdiv);
   // per sample of g > 0: orig and gen in, out out; of g = 0: a copy out of place, nothing in place; the mask per frame
   prof_stop(tok, s,
-            Ring ? (vec ? "alcm::wave_paste_ring_kernel<4>" : "alcm::wave_paste_ring_kernel<1>")
-                 : (vec ? "alcm::wave_paste_kernel<4>" : "alcm::wave_paste_kernel<1>"),
-            3.0 * blended,
+            law    ? (Ring ? (vec ? "alcm::wave_paste_law_ring_kernel<4>" : "alcm::wave_paste_law_ring_kernel<1>")
+                           : (vec ? "alcm::wave_paste_law_kernel<4>" : "alcm::wave_paste_law_kernel<1>"))
+            : Ring ? (vec ? "alcm::wave_paste_ring_kernel<4>" : "alcm::wave_paste_ring_kernel<1>")
+                   : (vec ? "alcm::wave_paste_kernel<4>" : "alcm::wave_paste_kernel<1>"),
+            (law ? 16.0 : 3.0) * blended,
             4.0 * (3.0 * blended + (inplace ? 0.0 : 2.0 * ((double)B * N - blended)) + (double)tiles * B * kPasteTile));
   ALCM_HIP(hipGetLastError());
   return 0;
@@ -1079,6 +1157,212 @@ int wave_paste(const float* orig, const float* gen, const float* mask, const flo
 int wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
                     int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R, hipStream_t s) {
   return paste<true>(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, fs, R, s);
+}
+
+int wave_paste_law(const float* orig, const float* gen, const float* mask, const float* ramp, const float* rho,
+                   const float* gam, float* out, int B, int64_t N, int64_t gen_start, int64_t Ng, int T, int fs, int R,
+                   int ring, hipStream_t s) {
+  return ring ? paste<true>(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, fs, R, s, true, rho, gam)
+              : paste<false>(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, fs, R, s, true, rho, gam);
+}
+
+// ---------------------------------------------------------------- seam statistics
+// What wave_paste_law blends by, measured where it blends (the definitions are in include/audiolcm_hip.h).  A junction
+// is a frame edge e with exactly one of the frames e - 1 and e regenerated (frames outside 0 .. T count as kept on a
+// line and are taken modulo T on a ring); its zone is the samples of 0 < d < R inside gen whose d the paste measures
+// from that edge.  With G the samples of the kept gap the zone lies in, the paste's tie rule (dl < dr goes left, a tie
+// right) gives the junction after a run d <= G / 2 and the junction before a run d <= (G + 1) / 2, both rounded down.
+//   seam_sums_kernel  a workgroup per clip and edge.  The gap is searched for over ceil(2 R / frame_samples) frames:
+//                     a longer one does not shorten the zone.  Thread t sums the samples d = 1 + t, 1 + t + 256, ... in
+//                     rising order in fp64 (the fp32 products are exact there), a tree over LDS sums the threads in a
+//                     fixed order, and thread 0 writes Sxx, Syy, Sxy and rho.  On a ring edge T is edge 0: the
+//                     workgroup of edge 0 writes both.
+//   seam_gain_kernel  a workgroup per clip.  Thread t takes the frames t C .. (t + 1) C - 1, C = ceil(T / 256): it
+//                     notes the first and last kept frame of its segment, finds the nearest kept frame before and
+//                     after the segment from the other threads' notes (round the wrap on a ring), and walks its
+//                     segment once more: every regenerated frame of a run gets gam from the sums at the run's two
+//                     edges, whichever segments the run spans.
+// No atomics and nothing read back on the host; a clip's values depend on its own rows alone.
+constexpr int kSeamBlock = 256;
+
+template <bool Ring>
+__global__ __launch_bounds__(kSeamBlock) void seam_sums_kernel(const float* __restrict__ orig,
+                                                               const float* __restrict__ gen,
+                                                               const float* __restrict__ mask, int64_t N, int64_t Ng,
+                                                               int64_t gen_start, int T, int fs, int R, int reach,
+                                                               float* __restrict__ rho, double* __restrict__ sums) {
+  __shared__ double s_acc[3][kSeamBlock];
+  const int E = T + 1;
+  const int b = blockIdx.x / E, e = blockIdx.x - b * E;
+  if (Ring && e == T) return;
+  const float* mrow = mask + (int64_t)b * T;
+  const auto reg = [&](int f) {
+    if constexpr (Ring) {
+      f %= T;
+      if (f < 0) f += T;
+    }
+    return f >= 0 && f < T && mrow[f] > 0.f;
+  };
+  const bool run_left = reg(e - 1), run_right = reg(e);
+  const int t = threadIdx.x;
+  float* rrow = rho + (int64_t)b * E;
+  double* srow = sums + (int64_t)b * E * 3;
+  if (run_left == run_right) {  // no junction
+    if (t == 0) {
+      rrow[e] = 1.f, srow[3 * e] = srow[3 * e + 1] = srow[3 * e + 2] = 0.0;
+      if (Ring && e == 0) rrow[T] = 1.f, srow[3 * T] = srow[3 * T + 1] = srow[3 * T + 2] = 0.0;
+    }
+    return;
+  }
+  int k = 0;  // kept frames from the edge on, away from the run
+  if (run_left)
+    while (k < reach && !reg(e + k)) ++k;
+  else
+    while (k < reach && !reg(e - 1 - k)) ++k;
+  const int64_t G = (int64_t)k * fs;  // k = reach: none found, G >= 2 R
+  const int64_t half = run_left ? G / 2 : (G + 1) / 2;
+  const int64_t dmax = half < R - 1 ? half : R - 1;
+  const int64_t edge = (int64_t)e * fs;
+  const float* ob = orig + (int64_t)b * N;
+  const float* gb = gen + (int64_t)b * Ng;
+  double sxx = 0.0, syy = 0.0, sxy = 0.0;
+  for (int64_t d = 1 + t; d <= dmax; d += kSeamBlock) {
+    int64_t n = run_left ? edge + d - 1 : edge - d;
+    if constexpr (Ring) {  // d <= G / 2 + 1 <= N: one turn at most
+      if (n >= N) n -= N;
+      if (n < 0) n += N;
+    }
+    if (n < 0 || n >= N) continue;
+    int64_t gi = n - gen_start;
+    if (Ring && gi < 0) gi += N;
+    if (gi < 0 || gi >= Ng) continue;
+    const double x = (double)ob[n], y = (double)gb[gi];
+    sxx += x * x, syy += y * y, sxy += x * y;
+  }
+  s_acc[0][t] = sxx, s_acc[1][t] = syy, s_acc[2][t] = sxy;
+  for (int w = kSeamBlock / 2; w > 0; w >>= 1) {
+    __syncthreads();
+    if (t < w) {
+      s_acc[0][t] += s_acc[0][t + w];
+      s_acc[1][t] += s_acc[1][t + w];
+      s_acc[2][t] += s_acc[2][t + w];
+    }
+  }
+  if (t == 0) {
+    sxx = s_acc[0][0], syy = s_acc[1][0], sxy = s_acc[2][0];
+    double r = 1.0;
+    if (sxx > 0.0 && syy > 0.0) {
+      r = sxy / (sqrt(sxx) * sqrt(syy));
+      r = r < 0.0 ? 0.0 : r > 1.0 ? 1.0 : r;
+    }
+    rrow[e] = (float)r, srow[3 * e] = sxx, srow[3 * e + 1] = syy, srow[3 * e + 2] = sxy;
+    if (Ring && e == 0) rrow[T] = (float)r, srow[3 * T] = sxx, srow[3 * T + 1] = syy, srow[3 * T + 2] = sxy;
+  }
+}
+
+template <bool Ring>
+__global__ __launch_bounds__(kSeamBlock) void seam_gain_kernel(const float* __restrict__ mask,
+                                                               const double* __restrict__ sums, int T,
+                                                               float* __restrict__ gam) {
+  __shared__ int s_first[kSeamBlock], s_last[kSeamBlock];  // the segment's first and last kept frame, -1: none
+  const int b = blockIdx.x, t = threadIdx.x;
+  const float* mrow = mask + (int64_t)b * T;
+  const double* srow = sums + (int64_t)b * (T + 1) * 3;
+  float* grow = gam + (int64_t)b * T;
+  const int64_t C = ((int64_t)T + kSeamBlock - 1) / kSeamBlock;
+  const int lo = (int)(t * C < T ? t * C : T), hi = (int)((t + 1) * C < T ? (t + 1) * C : T);
+  int first = -1, last = -1;
+  for (int f = lo; f < hi; ++f)
+    if (!(mrow[f] > 0.f)) {
+      if (first < 0) first = f;
+      last = f;
+    }
+  s_first[t] = first, s_last[t] = last;
+  __syncthreads();
+  // the nearest kept frame before the segment and after it; on a line the clip's ends stand in (edges 0 and T, whose
+  // sums are zero); on a ring the search goes on round the wrap, and a ring without a kept frame has no junction
+  int before = -1, after = T;
+  bool have = !Ring;
+  for (int u = t - 1; u >= 0; --u)
+    if (s_last[u] >= 0) {
+      before = s_last[u], have = true;
+      break;
+    }
+  for (int u = t + 1; u < kSeamBlock; ++u)
+    if (s_first[u] >= 0) {
+      after = s_first[u], have = true;
+      break;
+    }
+  if constexpr (Ring) {
+    if (before < 0)
+      for (int u = kSeamBlock - 1; u >= t; --u)
+        if (s_last[u] >= 0) {
+          before = s_last[u], have = true;
+          break;
+        }
+    if (after == T)
+      for (int u = 0; u <= t; ++u)
+        if (s_first[u] >= 0) {
+          after = s_first[u], have = true;
+          break;
+        }
+  }
+  int prev = before;
+  for (int f = lo; f < hi;) {
+    if (!(mrow[f] > 0.f)) {
+      grow[f] = 1.f;
+      prev = f++;
+      continue;
+    }
+    int g = f;
+    while (g < hi && mrow[g] > 0.f) ++g;
+    const int next = g < hi ? g : after;
+    float gain = 1.f;
+    if (have) {
+      int el = prev + 1, er = next;  // the run's edges; on a ring a kept frame exists, so prev and next are frames
+      if (Ring && el == T) el = 0;
+      const double sxx = srow[3 * el] + srow[3 * er], syy = srow[3 * el + 1] + srow[3 * er + 1];
+      if (sxx > 0.0 && syy > 0.0) {
+        const double v = sqrt(sxx / syy);
+        gain = (float)(v < 0.5 ? 0.5 : v > 2.0 ? 2.0 : v);
+      }
+    }
+    for (int q = f; q < g; ++q) grow[q] = gain;
+    f = g;
+  }
+}
+
+int seam_stats(const float* orig, const float* gen, const float* mask, int B, int64_t N, int64_t gen_start, int64_t Ng,
+               int T, int fs, int R, int ring, float* rho, float* gam, double* sums, hipStream_t s) {
+  const std::string f = "seam_stats: ";
+  if (const int rc = ring ? paste_check<true>(f, orig, gen, mask, true, orig, B, N, gen_start, Ng, T, fs, R)
+                          : paste_check<false>(f, orig, gen, mask, true, orig, B, N, gen_start, Ng, T, fs, R))
+    return rc;
+  if (!rho || !gam || !sums) return set_error(ALCM_E_INVALID, f + "null rho, gam or sums");
+  if (reinterpret_cast<uintptr_t>(sums) & 7) return set_error(ALCM_E_INVALID, f + "sums is not 8-byte aligned");
+  if (B == 0 || T == 0) return 0;
+  if ((int64_t)B * (T + 1ll) >= (1ll << 31)) return set_error(ALCM_E_INVALID, f + "problem too large");
+  const int reach = (int)((2 * (int64_t)R + fs - 1) / fs);
+  const dim3 grid((unsigned)((int64_t)B * (T + 1))), block(kSeamBlock);
+  const double edges = (double)B * (T + 1);
+  void* tok = prof_start(s);
+  if (ring)
+    hipLaunchKernelGGL(seam_sums_kernel<true>, grid, block, 0, s, orig, gen, mask, N, Ng, gen_start, T, fs, R, reach, rho,
+                       sums);
+  else
+    hipLaunchKernelGGL(seam_sums_kernel<false>, grid, block, 0, s, orig, gen, mask, N, Ng, gen_start, T, fs, R, reach,
+                       rho, sums);
+  // the zones' samples are not known on the host: the tables' traffic alone is counted
+  prof_stop(tok, s, ring ? "alcm::seam_sums_ring_kernel" : "alcm::seam_sums_kernel", 0.0, 36.0 * edges);
+  ALCM_HIP(hipGetLastError());
+  tok = prof_start(s);
+  if (ring)
+    hipLaunchKernelGGL(seam_gain_kernel<true>, dim3(B), block, 0, s, mask, sums, T, gam);
+  else
+    hipLaunchKernelGGL(seam_gain_kernel<false>, dim3(B), block, 0, s, mask, sums, T, gam);
+  prof_stop(tok, s, ring ? "alcm::seam_gain_ring_kernel" : "alcm::seam_gain_kernel", 0.0, 12.0 * B * T);
+  ALCM_HIP(hipGetLastError());
+  return 0;
 }
 
 // ---------------------------------------------------------------- loop crop and seam close
@@ -1310,6 +1594,18 @@ extern "C" int alcm_wave_paste_ring(const float* orig, const float* gen, const f
                                     int frame_samples, int R, alcm_stream_t stream) {
   return alcm::wave_paste_ring(orig, gen, mask, ramp, out, B, N, gen_start, Ng, T, frame_samples, R,
                                (hipStream_t)stream);
+}
+extern "C" int alcm_wave_paste_law(const float* orig, const float* gen, const float* mask, const float* ramp,
+                                   const float* rho, const float* gam, float* out, int B, int64_t N, int64_t gen_start,
+                                   int64_t Ng, int T, int frame_samples, int R, int ring, alcm_stream_t stream) {
+  return alcm::wave_paste_law(orig, gen, mask, ramp, rho, gam, out, B, N, gen_start, Ng, T, frame_samples, R, ring,
+                              (hipStream_t)stream);
+}
+extern "C" int alcm_seam_stats(const float* orig, const float* gen, const float* mask, int B, int64_t N,
+                               int64_t gen_start, int64_t Ng, int T, int frame_samples, int R, int ring, float* rho,
+                               float* gam, double* sums, alcm_stream_t stream) {
+  return alcm::seam_stats(orig, gen, mask, B, N, gen_start, Ng, T, frame_samples, R, ring, rho, gam, sums,
+                          (hipStream_t)stream);
 }
 extern "C" int alcm_sincos_embedding(const float* v, float vscale, const float* freqs, int B, int half,
                                      int cos_first, float* out, alcm_stream_t stream) {

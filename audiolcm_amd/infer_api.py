@@ -206,7 +206,7 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: Optional[float
                       true_peak: bool = False, joint: bool = False, extend_s: Optional[float] = None,
                       loop_from: bool = False, loop_seam_s: float = 1.0, loop_vary: bool = False,
                       loop_fade_ms: float = 32.0, limiter: bool = False, limiter_lookahead_ms: float = 5.0,
-                      limiter_release_ms: float = 100.0) -> str:
+                      limiter_release_ms: float = 100.0, fade_law: str = "linear", match_gain: bool = False) -> str:
     """Text-guided variation of ``init_audio`` (16 kHz mono PCM16 WAV) at ``strength`` (default 0.5), or, with ``mask_spans``
     ([(t0, t1)] in seconds), inpainting: the spans are regenerated and the rest of the latent is kept.  The whole
     clip is synthesised again from the latent, cropped to the DiT's 845 frames.  ``keep_original`` (needs
@@ -239,15 +239,20 @@ def AudioLCMEditInfer(ori_prompt: str, init_audio: str, strength: Optional[float
     (``AudioLCMPipeline.edit_loop``), and ``out_sample_rate``, the level and ``loop_fade_ms`` apply as for
     ``AudioLCMLongInfer(loop=True)``.  ``loop_from`` is refused with ``keep_original`` and ``extend_s``, without
     ``loop_vary`` also with a level or ``out_sample_rate``, for a recording shorter than two frames and for a seam
-    of more than half the recording.  Returns the WAV path (``<prompt-with-dashes>_0.wav``)."""
+    of more than half the recording.
+    ``fade_law`` ("linear", "equal-power" or "matched") and ``match_gain``: how the regenerated audio is faded into the
+    recording wherever one is kept (``keep_original``, ``extend_s``, ``loop_from`` without ``loop_vary``; refused
+    elsewhere): the linear crossfade, one that keeps the power for uncorrelated signals, or for the correlation
+    measured at each junction; and each regenerated run scaled to the recording's level at its junctions (DESIGN.md
+    §5, Fade laws).  Returns the WAV path (``<prompt-with-dashes>_0.wav``)."""
     from .pipeline import AudioLCMPipeline
     if strength is None:
         strength = 1.0 if loop_from and not loop_vary else 0.5
     plan = plan_edit(init_audio, mask_spans, keep_original, fade_ms, resample, out_sample_rate, loudness=loudness,
                      peak_dbfs=peak_dbfs, true_peak=true_peak, joint=joint, extend_s=extend_s, loop_from=loop_from,
                      loop_seam_s=loop_seam_s, loop_vary=loop_vary, loop_fade_ms=loop_fade_ms, limiter=limiter,
-                     limiter_lookahead_ms=limiter_lookahead_ms,
-                     limiter_release_ms=limiter_release_ms)  # before any model
+                     limiter_lookahead_ms=limiter_lookahead_ms, limiter_release_ms=limiter_release_ms,
+                     fade_law=fade_law, match_gain=match_gain)  # before any model
     _check_limiter_rate(None if plan.out_rate == SAMPLE_RATE else plan.out_rate, limiter, limiter_lookahead_ms,
                         limiter_release_ms)
     model, sampler, vocoder, orig_steps = _build(config_path, model_path, vocoder_path, synthetic_seed, split,

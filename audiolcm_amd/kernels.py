@@ -482,6 +482,73 @@ def _paste(name, orig, gen, mask, gen_start, fade_samples, frame_samples, out):
     return out
 
 
+def seam_stats(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_start: int, fade_samples: int,
+               frame_samples: int = 512, ring: bool = False):
+    """What ``wave_paste_law`` blends by, measured on the samples it is about to blend (alcm_seam_stats; the arguments
+    are ``wave_paste``'s, or ``wave_paste_ring``'s with ``ring``): per junction, an edge of a run of regenerated
+    frames, the sums Sxx, Syy and Sxy of orig and gen over the junction's fade zone in float64.  Returns
+    (rho (B, T + 1) fp32 per frame edge: the correlation clamped to [0, 1], 1 where there is nothing to measure;
+    gam (B, T) fp32 per frame: sqrt(Sxx / Syy) pooled over the run's junctions and clamped to [0.5, 2], 1 in kept
+    frames and where there is nothing to measure; sums (B, T + 1, 3) float64).  Two launches, no host round trip."""
+    B, N = orig.shape
+    assert orig.is_contiguous() and gen.is_contiguous() and mask.is_contiguous()
+    assert gen.shape[0] == B and mask.shape[0] == B and gen.dim() == 2 and mask.dim() == 2
+    T = mask.shape[1]
+    rho = torch.empty((B, T + 1), device=orig.device, dtype=torch.float32)
+    gam = torch.empty((B, T), device=orig.device, dtype=torch.float32)
+    sums = torch.empty((B, T + 1, 3), device=orig.device, dtype=torch.float64)
+    check(lib().alcm_seam_stats(ptr(orig), ptr(gen), ptr(mask), B, N, int(gen_start), gen.shape[1], T,
+                                int(frame_samples), int(fade_samples), int(bool(ring)), ptr(rho), ptr(gam), ptr(sums),
+                                stream_handle()), "seam_stats")
+    return rho, gam, sums
+
+
+def wave_paste_law(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_start: int, fade_samples: int,
+                   frame_samples: int = 512, out: Optional[torch.Tensor] = None, ring: bool = False,
+                   rho: Optional[torch.Tensor] = None, gam: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``wave_paste`` (``ring``: ``wave_paste_ring``) with the fade out = n * ((1 - g) * orig + g * gam * gen), n =
+    1 / sqrt((1 - g)^2 + g^2 + 2 (1 - g) g rho), in place of orig + g * (gen - orig) (alcm_wave_paste_law, which states
+    the fp32 operation order).  ``rho`` (B, T + 1) and ``gam`` (B, T) are ``seam_stats``' tables; ``rho`` None is 0
+    everywhere, the equal-power law, and ``gam`` None is 1.  g = 0 keeps orig's bits and g = 1 with ``gam`` None takes
+    gen's.  One launch."""
+    B, N = orig.shape
+    T = mask.shape[1]
+    assert orig.is_contiguous() and gen.is_contiguous() and mask.is_contiguous()
+    assert gen.shape[0] == B and mask.shape[0] == B and gen.dim() == 2 and mask.dim() == 2
+    assert rho is None or (rho.shape == (B, T + 1) and rho.is_contiguous() and rho.dtype == torch.float32)
+    assert gam is None or (gam.shape == (B, T) and gam.is_contiguous() and gam.dtype == torch.float32)
+    if out is None:
+        out = torch.empty_like(orig)
+    assert out.shape == orig.shape and out.is_contiguous()
+    ramp = paste_ramp(fade_samples, orig.device) if 0 < fade_samples <= PASTE_MAX_FADE_FRAMES * frame_samples else None
+    check(lib().alcm_wave_paste_law(ptr(orig), ptr(gen), ptr(mask), ptr(ramp), ptr(rho), ptr(gam), ptr(out), B, N,
+                                    int(gen_start), gen.shape[1], T, int(frame_samples), int(fade_samples),
+                                    int(bool(ring)), stream_handle()), "wave_paste_law")
+    return out
+
+
+def paste(orig: torch.Tensor, gen: torch.Tensor, mask: torch.Tensor, gen_start: int, fade_samples: int,
+          frame_samples: int = 512, out: Optional[torch.Tensor] = None, ring: bool = False, fade_law: str = "linear",
+          match_gain: bool = False) -> torch.Tensor:
+    """The paste of every edit that keeps a recording.  ``fade_law`` "linear" without ``match_gain`` is ``wave_paste``
+    (``ring``: ``wave_paste_ring``) itself, one launch.  Otherwise ``seam_stats`` measures on this ``orig`` and ``gen``
+    and ``wave_paste_law`` blends: "equal-power" with rho = 0, "matched" with the measured rho, "linear" (with
+    ``match_gain``) with rho = 1; ``match_gain`` passes the measured gam.  "equal-power" alone measures nothing."""
+    from .audio_in import check_fade_law
+    check_fade_law(fade_law, match_gain, True)
+    if fade_law == "linear" and not match_gain:
+        return (wave_paste_ring if ring else wave_paste)(orig, gen, mask, gen_start, fade_samples, frame_samples, out)
+    rho = gam = None
+    if fade_law == "matched" or match_gain:
+        rho, gam, _ = seam_stats(orig, gen, mask, gen_start, fade_samples, frame_samples, ring)
+    if fade_law == "linear":
+        rho = torch.ones_like(rho)
+    elif fade_law == "equal-power":
+        rho = None
+    return wave_paste_law(orig, gen, mask, gen_start, fade_samples, frame_samples, out, ring, rho,
+                          gam if match_gain else None)
+
+
 def wave_loop(ext: torch.Tensor, start: int, N: int, fade_samples: int = 0) -> torch.Tensor:
     """One period of a looping clip from ``ext`` (B, Next), the decode of the ring's latent padded circularly: the N
     samples from ``start`` on, with the seam closed over the first R = ``fade_samples`` of them (alcm_wave_loop).

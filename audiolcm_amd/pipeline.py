@@ -113,7 +113,8 @@ class AudioLCMPipeline:
                   unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0, keep_original: bool = False,
                   fade_samples: Optional[int] = None, halo_frames: int = 32,
                   rate: int = SAMPLE_RATE, joint: bool = False,
-                  joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
+                  joint_clips_per_call: int = 1, fade_law: str = "linear",
+                  match_gain: bool = False) -> Dict[str, torch.Tensor]:
         """``edit`` for a clip of any length, optionally keeping the input waveform outside the regenerated frames.
 
         The input is exactly one of ``wav`` (B, N), N a multiple of 512, encoded once as a whole (z = the scaled
@@ -149,8 +150,14 @@ class AudioLCMPipeline:
         the fade in 16 kHz samples + |first| + 1 (``first`` of the 16000 -> rate filter, ``resample.plan``), whatever
         the regions, so that the upsampler's transient at a region's edges stays outside the fade too.  The default of
         32 frames (1 s) also keeps the fade away from the zero-padded edges of the region's decode; it is a choice,
-        not a measurement (no trained weights here to listen to)."""
+        not a measurement (no trained weights here to listen to).
+
+        ``fade_law`` and ``match_gain`` (with ``keep_original``; DESIGN.md §5, Fade laws): "linear" is the fade above;
+        "equal-power" and "matched" keep the power through the fade for uncorrelated signals, or for the correlation
+        measured at each junction; ``match_gain`` scales each regenerated run to the level of the recording at its
+        junctions.  Each region is measured on its own decode (``kernels.paste``)."""
         from . import kernels, resample as rs
+        self._check_law(fade_law, match_gain, keep_original)
         if (wav is None) == (latent is None):
             raise ValueError("pass exactly one of `wav` and `latent`")
         if keep_original and wav is None:
@@ -192,8 +199,14 @@ class AudioLCMPipeline:
             return dict(latent=z, **self.decode(z))
         out = wav.clone()
         pm = torch.ones((B, L), device=dev) if mask is None else mask.to(dev).contiguous()
-        self._paste_regions(out, z, pm, regions, fade_samples, rate, F)
+        self._paste_regions(out, z, pm, regions, fade_samples, rate, F, fade_law, match_gain)
         return dict(latent=z, wav=out, regions=regions)
+
+    @staticmethod
+    def _check_law(fade_law: str, match_gain: bool, pastes: bool = True):
+        """``audio_in.check_fade_law``: a known law, and anything but the defaults needs a paste to act on."""
+        from .audio_in import check_fade_law
+        check_fade_law(fade_law, match_gain, pastes)
 
     @staticmethod
     def _check_fade(fade: int, frame_samples: int, halo_frames: int, reach: int, inside: bool):
@@ -282,18 +295,19 @@ class AudioLCMPipeline:
         return z
 
     def _paste_regions(self, out, z, pm, regions, fade_samples, rate: int = SAMPLE_RATE,
-                       frame_samples: int = FRAME_SAMPLES):
+                       frame_samples: int = FRAME_SAMPLES, fade_law: str = "linear", match_gain: bool = False):
         """The paste of ``edit_long(keep_original=True)``: each region [a, b) of latent frames is decoded, resampled
         from 16 kHz to ``rate`` when that is another one ((b - a) * frame_samples samples exactly) and blended into
-        ``out`` (B, N at ``rate``) in place by one ``kernels.wave_paste``."""
+        ``out`` (B, N at ``rate``) in place by one ``kernels.paste``: ``kernels.wave_paste`` by default, else the
+        region's own ``kernels.seam_stats`` and ``kernels.wave_paste_law``."""
         from . import kernels
         for a, b in regions:
             gen = self.decode(z[:, :, a:b].contiguous())["wav"].contiguous()
             if rate != SAMPLE_RATE:
                 gen = kernels.resample(gen, SAMPLE_RATE, rate)
                 assert gen.shape[1] == (b - a) * frame_samples
-            kernels.wave_paste(out, gen, pm, gen_start=a * frame_samples, fade_samples=fade_samples,
-                               frame_samples=frame_samples, out=out)
+            kernels.paste(out, gen, pm, gen_start=a * frame_samples, fade_samples=fade_samples,
+                          frame_samples=frame_samples, out=out, fade_law=fade_law, match_gain=match_gain)
 
     @torch.no_grad()
     def run_edit(self, plan: EditPlan, cond: torch.Tensor, seeds: Optional[Sequence[int]], strength: float = 0.5):
@@ -316,19 +330,22 @@ class AudioLCMPipeline:
             wav = np.broadcast_to(plan.samples, (B, plan.samples.size)).copy()
             if plan.mode == "loop_from":
                 mask = None if plan.mask is None else np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
-                out = self.loop_from(cond, seeds, wav, plan.seam_frames, strength, mask, fade_samples=plan.fade)
+                out = self.loop_from(cond, seeds, wav, plan.seam_frames, strength, mask, fade_samples=plan.fade,
+                                     fade_law=plan.fade_law, match_gain=plan.match_gain)
                 return out["wav"], plan.out_rate, None
             if plan.mode == "loop_vary":
                 out = self.edit_loop(cond, seeds, wav=wav, strength=strength, level=plan.level,
                                      out_sample_rate=plan.out_rate, loop_fade_samples=plan.loop_fade)
                 return out["wav"], out["rate"], out["mel"]
             if plan.mode == "extend":
-                out = self.extend(cond, seeds, wav, plan.extend_frames, fade_samples=plan.fade)
+                out = self.extend(cond, seeds, wav, plan.extend_frames, fade_samples=plan.fade,
+                                  fade_law=plan.fade_law, match_gain=plan.match_gain)
                 return out["wav"][:, :plan.n_out], plan.out_rate, None
             if plan.mode == "keep_original":
                 mask = np.broadcast_to(plan.mask, (B, plan.mask.size)).copy()
                 out = self.edit_long(cond, seeds, wav=wav, mask=mask, strength=strength, keep_original=True,
-                                     rate=plan.rate, fade_samples=plan.fade, joint=plan.joint)
+                                     rate=plan.rate, fade_samples=plan.fade, joint=plan.joint,
+                                     fade_law=plan.fade_law, match_gain=plan.match_gain)
                 return out["wav"][:, :plan.n_samples], plan.out_rate, None
             out = self.edit_long(cond, seeds, wav=wav, mask=span_mask(plan.samples.size // plan.frame_samples),
                                  strength=strength, joint=True)
@@ -344,7 +361,8 @@ class AudioLCMPipeline:
     def extend(self, cond: torch.Tensor, seeds: Optional[Sequence[int]], wav, extra_frames: int,
                context_frames: Optional[int] = None, window: Optional[int] = None, overlap: Optional[int] = None,
                fade_samples: Optional[int] = None, halo_frames: int = 32, steps: Optional[int] = None,
-               joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
+               joint_clips_per_call: int = 1, fade_law: str = "linear",
+               match_gain: bool = False) -> Dict[str, torch.Tensor]:
         """Continues a recording: ``wav`` (B, N) at 16 kHz, N = L0 * 512, comes back followed by ``extra_frames`` new
         latent frames that continue it.
 
@@ -359,7 +377,7 @@ class AudioLCMPipeline:
         ``kernels.wave_paste``: the recording's samples are its own bit for bit up to ``fade_samples`` (default 512)
         before the junction at sample N, the raised-cosine fade closes the junction, and from the junction on
         everything is generated.  ``halo_frames`` * 512 >= ``fade_samples`` is required unless the decode starts at
-        frame 0.
+        frame 0.  ``fade_law`` and ``match_gain`` are ``edit_long``'s; the one run has one junction, at sample N.
 
         Returns latent (B, C, L0 + extra; the first L0 frames are z_rec), wav (B, (L0 + extra) * 512) and region
         (a, L0 + extra).  ValueError for ``extra_frames`` < 1, an empty recording, or a region of more than 32
@@ -367,6 +385,7 @@ class AudioLCMPipeline:
         from . import kernels
         dev = torch.device("cuda")
         S = steps or self.steps
+        self._check_law(fade_law, match_gain)
         wav = torch.as_tensor(wav, dtype=torch.float32).to(dev).contiguous()
         if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES or wav.shape[1] < FRAME_SAMPLES:
             raise ValueError(f"`wav` is (B, N) with N a multiple of {FRAME_SAMPLES} and at least one frame")
@@ -394,7 +413,8 @@ class AudioLCMPipeline:
                            guidance_scale=self.guidance_scale, original_inference_steps=self.original_inference_steps)
         gen = self.decode(z[:, :, h0:].contiguous())["wav"].contiguous()
         out = torch.cat([wav, torch.zeros((B, extra * FRAME_SAMPLES), device=dev)], 1)
-        kernels.wave_paste(out, gen, m, gen_start=h0 * FRAME_SAMPLES, fade_samples=fade, out=out)
+        kernels.paste(out, gen, m, gen_start=h0 * FRAME_SAMPLES, fade_samples=fade, out=out, fade_law=fade_law,
+                      match_gain=match_gain)
         return dict(latent=z, wav=out, region=(a, L))
 
     @torch.no_grad()
@@ -404,7 +424,8 @@ class AudioLCMPipeline:
                   fade_samples: Optional[int] = None, halo_frames: int = 32, out_sample_rate: Optional[int] = None,
                   level=None, loop_fade_samples: Optional[int] = None, sample_posterior: bool = True,
                   steps: Optional[int] = None, unconditional: Optional[torch.Tensor] = None, cfg_scale: float = 1.0,
-                  joint_clips_per_call: int = 1) -> Dict[str, torch.Tensor]:
+                  joint_clips_per_call: int = 1, fade_law: str = "linear",
+                  match_gain: bool = False) -> Dict[str, torch.Tensor]:
         """A loop from a recording: ``edit_long(joint=True)`` on a ring.  The input is exactly one of ``wav`` (B, N) at
         16 kHz, N = L * 512, encoded as the periodic signal it is about to become (``_encode_ring``), and ``latent``
         (B, C, L); its L >= 2 frames are one period, frame L - 1 the left neighbour of frame 0.  ``mask`` (B, L), 1 =
@@ -435,8 +456,11 @@ class AudioLCMPipeline:
         regenerated, or only short gaps) a = 0: the centre N samples at gen_start = 0, whose two ends meet at the
         wrap as two renderings that agree to the halo's accuracy.  Samples further than ``fade_samples`` (default 512) from a
         regenerated frame, measured round the ring, keep the input's bits.  ``halo_frames`` * 512 >= ``fade_samples``
-        always: a ring has no clip end that would exempt a region.  Returns latent, wav (B, N) and regions."""
+        always: a ring has no clip end that would exempt a region.  ``fade_law`` and ``match_gain`` are
+        ``edit_long``'s, with ``keep_original`` only; junctions, zones and runs are taken round the ring, for a region as
+        for the ring cut open.  Returns latent, wav (B, N) and regions."""
         from . import kernels
+        self._check_law(fade_law, match_gain, keep_original)
         if (wav is None) == (latent is None):
             raise ValueError("pass exactly one of `wav` and `latent`")
         if keep_original and wav is None:
@@ -511,8 +535,8 @@ class AudioLCMPipeline:
             else:
                 a, n = region
                 gen = self.decode(z[:, :, ((a + torch.arange(n, device=dev)) % L)].contiguous())["wav"]
-            kernels.wave_paste_ring(out, gen.contiguous(), pm, gen_start=a * FRAME_SAMPLES, fade_samples=fade,
-                                    out=out)
+            kernels.paste(out, gen.contiguous(), pm, gen_start=a * FRAME_SAMPLES, fade_samples=fade, out=out,
+                          ring=True, fade_law=fade_law, match_gain=match_gain)
         return dict(latent=z, wav=out, regions=regions)
 
     @torch.no_grad()
@@ -523,7 +547,7 @@ class AudioLCMPipeline:
         conditioned on the recording across the wrap on both sides; every other sample is the recording's own, bit for
         bit, up to the paste's fade.  The defaults are choices, not measurements (no trained weights here to listen
         to): a seam of 32 frames, about 1 s either side, and strength 1.0, so the seam frames start from pure noise.
-        ``kw`` are ``edit_loop``'s further arguments.  ValueError unless 1 <= seam_frames and 2 * seam_frames <= L."""
+        ``kw`` are ``edit_loop``'s further arguments, ``fade_law`` and ``match_gain`` among them.  ValueError unless 1 <= seam_frames and 2 * seam_frames <= L."""
         wav = torch.as_tensor(wav, dtype=torch.float32)
         if wav.dim() != 2 or wav.shape[1] % FRAME_SAMPLES:
             raise ValueError(f"`wav` is (B, N) with N a multiple of {FRAME_SAMPLES}")

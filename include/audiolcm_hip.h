@@ -445,6 +445,51 @@ int alcm_wave_paste(const float* orig, const float* gen, const float* mask, cons
 int alcm_wave_paste_ring(const float* orig, const float* gen, const float* mask, const float* ramp, float* out, int B,
                          int64_t N, int64_t gen_start, int64_t Ng, int T, int frame_samples, int R,
                          alcm_stream_t stream);
+/* alcm_seam_stats: the correlation and the level ratio of orig and gen where alcm_wave_paste_law is about to blend
+ * them, two launches, nothing read back on the host (no reference counterpart).  orig, gen, mask, B, N, gen_start, Ng,
+ * T, frame_samples and R are the paste's (alcm_wave_paste; ring != 0: alcm_wave_paste_ring's).
+ *   A junction is a frame edge e (between the frames e - 1 and e, e = 0 .. T) of which exactly one is regenerated: an
+ *   end of a maximal run of regenerated frames.  Frames outside 0 .. T - 1 count as kept on a line; on a ring frames and
+ *   edges are taken modulo T, so edge T is edge 0.
+ *   The zone of a junction: the samples of 0 < d < R that lie inside gen and whose d the paste measures from that
+ *   junction.  A kept sample with dl samples to the last regenerated sample on its left and dr to the first on its
+ *   right belongs to the left junction where dl < dr and to the right one otherwise (a tie goes right, as in the
+ *   paste), so a kept gap shorter than 2 R is split exactly as the fade splits it.
+ *   Per zone, in fp64 (the fp32 products are exact there), in a fixed order without atomics:
+ *     Sxx = sum orig^2, Syy = sum gen^2, Sxy = sum orig * gen.
+ *   rho = clamp(Sxy / (sqrt(Sxx) * sqrt(Syy)), 0, 1), and 1 where Sxx or Syy is zero (an empty or a silent zone) and
+ *   at an edge that is no junction.
+ *   gam of a run = clamp(sqrt((Sxx + Sxx') / (Syy + Syy')), 0.5, 2) over the run's two junctions (a run that touches
+ *   the end of a line has an empty zone there; a run across the wrap of a ring is one run), and 1 where either pooled
+ *   sum is zero or the run has no junction (a ring regenerated all round).
+ * Outputs (device):
+ *   rho  (B, T + 1) fp32, indexed by the edge; on a ring rho[b][T] = rho[b][0].
+ *   gam  (B, T) fp32: the run's value in each of its frames, 1 in a kept frame.
+ *   sums (B, T + 1, 3) fp64, 8-byte aligned: Sxx, Syy, Sxy per edge, zero at an edge that is no junction; on a ring
+ *        entry T repeats entry 0.  gam is computed from these.
+ * ALCM_E_INVALID under the paste's conditions in the paste's words (orig stands for out; no ramp is taken), and for a
+ * null rho, gam or sums, or sums not 8-byte aligned.  B or T of 0: no launch. */
+int alcm_seam_stats(const float* orig, const float* gen, const float* mask, int B, int64_t N, int64_t gen_start,
+                    int64_t Ng, int T, int frame_samples, int R, int ring, float* rho, float* gam, double* sums,
+                    alcm_stream_t stream);
+/* alcm_wave_paste_law: alcm_wave_paste (ring != 0: alcm_wave_paste_ring) under a power-preserving fade law and a
+ * per-run gain, one launch: the same tiling, mask search, g, in-place rule and conditions for 16-byte accesses.
+ *   rho (B, T + 1) per frame edge and gam (B, T) per regenerated frame, as alcm_seam_stats writes them; rho NULL: 0
+ *   everywhere (the equal-power law), gam NULL: 1.  A table of ones for rho gives the linear law up to rounding.
+ *   y = gen where gam is NULL, else fl(gam * gen) with the gam of the sample's own frame at d = 0 and of the
+ *   regenerated frame its d is measured from at d > 0 (dl < dr: the run on the left, else the one on the right); rho
+ *   is the entry of the edge between that frame and the kept gap.
+ *   out = orig where g = 0 (in place neither read nor written) and y where g = 1, both bit for bit; else, with every
+ *   operation rounded to fp32 on its own, none contracted, in this order:
+ *     a = 1 - g;  s = (a * orig) + (g * y);  p = ((a * a) + (g * g)) + (((a + a) * g) * rho);
+ *     out = (1 / sqrt(p)) * s          (sqrt and the division correctly rounded)
+ *   The 16-byte path and the element path run the same operations and give the same bits.  1 / sqrt(p) restores the
+ *   power of two signals of equal power and correlation rho; with unequal powers it is the equal-sigma approximation,
+ *   which gam makes good when it is used.
+ * ALCM_E_INVALID as alcm_wave_paste (alcm_wave_paste_ring), under the name wave_paste_law. */
+int alcm_wave_paste_law(const float* orig, const float* gen, const float* mask, const float* ramp, const float* rho,
+                        const float* gam, float* out, int B, int64_t N, int64_t gen_start, int64_t Ng, int T,
+                        int frame_samples, int R, int ring, alcm_stream_t stream);
 /* alcm_resample: band-limited rational resampling of a batch of clips with the mean over the channels folded into
  * the read, one launch (no reference counterpart: the reference labels its 16 kHz samples with any rate it is given).
  *   x (B, N_in, channels), interleaved as a WAV file stores it; y (B, N_out), N_out = ceil(N_in * up / down);

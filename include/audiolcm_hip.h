@@ -75,7 +75,11 @@ typedef struct alcm_operand {
   const void* ptr;
   /* ACT: element (b, t, c) at ptr + b*sb + t*st + c*sc; K index k = tap*Cpad + ci, source time
    *      t_src = t + tap*dil - pad (up == 2: nearest-x2 upsampled input, t_up = t + tap*dil - pad,
-   *      t_src = t_up/2), zero outside [0, T_in) / ci >= C_in / k >= ksize*Cpad.
+   *      t_src = t_up/2, valid for t_up in [0, 2*T_in)), zero outside [0, T_in) / ci >= C_in / k >= ksize*Cpad.
+   *      With C_in < Cpad (the scalar loader) the zero of the lanes ci >= C_in is the WEIGHT operand's: a norm
+   *      prologue leaves (0 - mean)*rstd in those lanes of A, and alcm_pack_conv_weight writes exact zeros at
+   *      ci >= C_in of every tap, so the product is the defined one.  A WEIGHT operand packed any other way must keep
+   *      those columns zero (tests/test_gpu_gemm_forms.py, case ln_k9_C20: rows of mean ~ 5 std).
    * ACT_T: element (n, k) at ptr + k*st + n*sc, valid k < T_in, n < rows.
    * WEIGHT: packed [rows][Kpad] planes: bf16 hi at ptr, bf16 lo at ptr + w_lo_off, fp16 hi at
  *         ptr + 2*w_lo_off, fp16 lo at ptr + 3*w_lo_off (elements; w_lo_off = rows*Kpad as written by

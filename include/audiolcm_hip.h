@@ -729,6 +729,17 @@ int alcm_debug_tconv_trace(unsigned long long* out8, int reset);
  * workgroups); returns the count copied (0 before the first alcm_debug_tconv_trace call).  Synchronizes the device. */
 int alcm_debug_tconv_wg_times(unsigned long long* out, int n_wg);
 
+/* ---------------------------------------------------------------- model entry points and their workspaces
+ * Every model entry point below takes a caller workspace `ws` of `ws_bytes` bytes of device memory, 256-byte aligned;
+ * the alcm_*_workspace_bytes query next to it gives the size for the handle's precision policy and the shape
+ * (alcm_dit_embed_context: alcm_dit_workspace_bytes(m, B, 1) is enough).  A smaller or null workspace is refused
+ * with ALCM_E_WORKSPACE before anything is launched or written.  The workspace contract, for all of them:
+ *   - contents on entry are irrelevant: the result does not depend on what [ws, ws + ws_bytes) holds, so one arena may
+ *     serve calls of any shapes, policies and models, one after the other on a stream, without being cleared;
+ *   - nothing outside [ws, ws + ws_bytes) is written, apart from the output tensor (the inputs are only read);
+ *   - contents on exit are unspecified.
+ * (tests/test_gpu_workspace.py: guarded workspaces of exactly the queried size, filled with NaN patterns.) */
+
 /* DiT.  x (B,C_lat,T) NCT, t (B,) int64, ctx (B,154,1024), w_emb (B,256) -> eps (B,C_lat,T) NCT.
  * cemb_cache: (B,154,hidden) device buffer filled by alcm_dit_embed_context (step-invariant, hoisted). */
 size_t alcm_dit_workspace_bytes(const alcm_model* m, int B, int T);

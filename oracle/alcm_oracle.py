@@ -183,7 +183,7 @@ def _temporal_transformer(W: W_t, p: str, x: Tensor, heads: int) -> Tensor:
 
 def dit_time_embed(W: W_t, t: Tensor, w_cond: Optional[Tensor]) -> Tensor:
     """``TimestepEmbedder.forward`` (concatDiT.py:69-74) -> (B, hidden)."""
-    tf = timestep_embedding(t, 256)
+    tf = timestep_embedding(t, 256).to(W["t_embedder.mlp.0.weight"].dtype)  # fp32 by construction, as the reference's
     if w_cond is not None:
         tf = tf + F.linear(w_cond, W["t_embedder.proj_w.weight"])
     h = F.silu(F.linear(tf, W["t_embedder.mlp.0.weight"], W["t_embedder.mlp.0.bias"]))
@@ -441,7 +441,7 @@ def _mha(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, bias: Option
     s = torch.matmul(q, k.transpose(-1, -2)) * scale
     if bias is not None:
         s = s + bias
-    p = s.float().softmax(-1)
+    p = s.softmax(-1, dtype=torch.promote_types(s.dtype, torch.float32))  # fp32 at least; float64 weights stay float64
     return torch.matmul(p, v).permute(0, 2, 1, 3).reshape(B, L, I)
 
 
